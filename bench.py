@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — the headline benchmark of BASELINE.json on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: model and pool set-up, the prompt phase, W warm-up steps, the K timed
+steps, and the JSON line (metric, value, unit, higher_is_better, dtype, ms_per_step, the prompt phase, step_roofline,
+config). Every other measurement listed under "Extra objects" below runs only with --full. --dump-outputs DIR writes what
+the last timed step returned to its caller (rank 0's next-token ids, DIR/tokens.npy, float64) for output-for-output
+comparisons of two builds: with the same arguments the inputs are the same from run to run.
 
 With --gpus N and no launcher environment (WORLD_SIZE unset) the script starts the N ranks itself, one process per GPU
 (HIP_VISIBLE_DEVICES=i), and rank 0 prints the line.
@@ -19,12 +25,12 @@ path) with everything resident in HBM. The K timed steps always sit in the MIDDL
 contexts 1025 + (128-K)/2 ... whatever --steps is, so their mean context is the mean context of a full
 1024-in/128-out run (1088.5) and `value` is on the workload the config names, not on a lighter one: after the real
 prefill the sequences are advanced to the first warm-up context directly (their KV slots for the skipped positions
-hold the N(0,1) data the pool was filled with). The prompt phase (one 32x1024-token prefill forward) runs before
+hold seeded N(0,1) data, `seed_skipped_kv`). The prompt phase (one 32x1024-token prefill forward) runs before
 the timed region and is reported separately as `prefill_tok_s`. `value` = decode tokens/s of the whole job =
 n_gpus * batch * K / max-over-ranks time of the K timed steps (request-sharded replicas, weak scaling, no
 collective on the data path). Each rank pins itself to the NUMA-local cores of its GPU.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full only; --no-extras, --no-cpu-baseline and --no-reference drop some of them):
   roofline        the kernel with the largest share of the decode step, timed live with HIP events on the launch
                   stream over launches that cycle through all layers' weights / KV (far past the 256 MiB Infinity
                   Cache), at the decode loop's exact entry point, shapes and launch geometry: algorithmic bytes per
@@ -94,7 +100,15 @@ def parse_args():
     ap.add_argument("--kv-placement", default="top", choices=["top", "bottom"],
                     help="top: filler sequences occupy the low block ids, the run's sequences get the highest ones")
     ap.add_argument("--no-reference", action="store_true", help="skip the reference-Triton child run")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements: kernel rooflines, eager, other configs / batch sizes / precisions, "
+                         "long prompts, the reference's path, the CPU baseline (a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (DIR/tokens.npy, float64) after the timed steps")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 MODEL_DIMS = {
@@ -306,6 +320,38 @@ class DecodeRun:
     def release(self):
         self.model.free_seqs_resources(self.seq_ids)
         self.lens = [0] * self.batch
+
+
+def seed_skipped_kv(run, lo, seed):
+    """Positions lo .. len-1 of the run's sequences (those `jump_to` skipped over) get seeded N(0, 1) K and V of their own.
+    Left alone they would hold what the pool fill put in the blocks the run is handed, and which blocks those are and what
+    the fill put there follow from the pool's size, which profile_num_blocks() reads off the device's free memory: two
+    builds would decode different contexts. The blocks are taken by the same call the next step would make, so the run
+    sits where it did."""
+    import torch
+    model = run.model
+    hi = run.lens[0]
+    if hi <= lo:
+        return
+    mgr = model.gpu_block_manager
+    mgr.allocate_blocks_for_seqs(run.seq_ids, [n + 1 for n in run.lens])
+    bs = model.engine_config.block_size
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    with torch.inference_mode():
+        for sid in run.seq_ids:
+            blocks = mgr.get_block_ids_host(sid)
+            for j in range(lo // bs, -(-hi // bs)):
+                a, b = max(lo - j * bs, 0), min(hi - j * bs, bs)
+                for cache in (model.k_cache, model.v_cache):
+                    cache[blocks[j], :, :, a:b].normal_(0.0, 1.0, generator=g)
+
+
+def dump_outputs(out_dir, arrays):
+    """`arrays`: name -> what the timed path returned; written as out_dir/<name>.npy in float64."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, value in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray(value, dtype=np.float64))
 
 
 def _event_time(launch, iters, warm):
@@ -770,6 +816,7 @@ def _run(args):
 
     # ---- decode: W warm-up steps, then exactly K timed steps, centred in the generation --------------------------
     run.jump_to(max(S + 1, first_timed - Wm))
+    seed_skipped_kv(run, 0 if args.skip_prefill else S, 4321 + rank)
     local_s, first_ctx, last_ctx = run.timed_steps(Wm, K, dp.barrier)
     pool = pool_report(model)
     units, max_s = dp.reduce_job(B * K, local_s)
@@ -780,6 +827,8 @@ def _run(args):
 
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"tokens": run.toks})
     ms_per_step = max_s / K * 1e3
     mean_ctx = (first_ctx + last_ctx) / 2
     result = {
@@ -819,6 +868,8 @@ def _run(args):
             "dominant_kernel": "hipBLASLt Cijk_* MT256x256x64 (F.linear, the reference's own call, kernels/linear.py:3-12): "
                                "~90 % of the pass — profiles/r03_kernel_trace_configs2.md; the hand-written attention kernel "
                                "is priced separately in prefill_attention_roofline"}
+    if not args.full:
+        return result
     # `roofline` = the kernel with the largest share of the step; the other hand-written heavyweight next to it
     attn = attention_roofline(model, run.lens, args.kernel_iters)
     gemm = gemm_roofline(model, B, args.kernel_iters)
