@@ -381,7 +381,9 @@ int swl_paged_attn_decode_qkv_rs(void *o, const float *qkv_slabs, int32_t k_spli
  *   swl_gemm_tiny_partial_from_attn: o_proj (transformer_layer.py:117) on those partials — every workgroup merges the
  *     partials of its K-chunk of heads itself (phase 2's LSE-weighted sum, paged_attn.py:108-150, rounded to the storage
  *     dtype as phase 2 stores it) and writes slabs_out[k_splits_out][M][N]; K = num_q_heads * head_dim. Replaces the
- *     phase-2 launch of a batch of <= 4 sequences. */
+ *     phase-2 launch of a batch of <= 4 sequences. A row with seq_lens[row] <= 0 is inert, as in phase 1 and 2: its
+ *     activations are exactly 0 (its slab rows come out 0), none of its partials is read, and the other rows are
+ *     bit-identical to a launch without it. */
 int swl_paged_attn_decode_qkv_rs_partials(void *o, const float *qkv_slabs, int32_t k_splits, const float *row_ssq,
                                           int32_t ssq_parts, int32_t hidden, float eps, const void *cos_table,
                                           const void *sin_table, const int32_t *pos_idx, void *k_cache, void *v_cache,

@@ -101,6 +101,15 @@ __global__ __launch_bounds__(kTinyWaves * 64, 2) void gemm_tiny_kernel(TinyArgs 
             const int head = col / a.D, d = col - head * a.D;
             const int n = (a.seq_lens[row] + a.seq_block_size - 1) / a.seq_block_size;
             const int64_t base = (static_cast<int64_t>(row) * a.H + head) * a.num_seq_blocks;
+            if (n <= 0) {
+                // a length-0 row (a padded decode slot) is inert, as in phase 1 and 2: x = 0, no partial is read
+                // (the clamp below would index split -1, before the row's scratch)
+                vec8_t<T> zv;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) zv[j] = to_t<T>(0.f);
+                *reinterpret_cast<vec8_t<T> *>(&xres[row][8 * c8]) = zv;
+                continue;
+            }
             float acc8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             float lsum = 0.f;
             if (n <= 16) {
