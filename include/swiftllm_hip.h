@@ -135,6 +135,18 @@ size_t swl_argmax_scratch_bytes(int64_t num_rows);
 int swl_argmax(int64_t *out, const void *x, void *scratch, size_t scratch_bytes, int64_t num_rows, int32_t n,
                int64_t row_stride, int32_t dtype, swl_stream_t stream);
 
+/* ---- Seeded sampling (temperature / top-k / top-p) -------------------------------------------
+ * reference: post_layer.py:40 (`torch.argmax(logits, dim=1)`); the reference samples greedily only, this is an addition.
+ * out[r] = one token drawn from row r of x[num_rows, n] (row stride row_stride elements), any n >= 1. Per-row
+ * parameters are device arrays (one captured graph serves every replay): temperature[r] (not > 0: exactly swl_argmax),
+ * top_k[r] (1 <= k < n: keep the k largest, ties kept; otherwise off), top_p[r] (0 < p < 1: nucleus over what top-k
+ * kept, ties kept; otherwise off), seed[r][2] (Philox4x32-10 key: lo, hi), pos[r] (index the token takes in its
+ * sequence; the Philox counter of element i is (i >> 2, pos, 0, 0)). The draw is Gumbel-max; the exact contract is
+ * in csrc/sampling.hip. No scratch, no allocation, no atomics: bit-reproducible and independent of the batch. */
+int swl_sample(int64_t *out, const void *x, int64_t num_rows, int32_t n, int64_t row_stride, int32_t dtype,
+               const float *temperature, const int32_t *top_k, const float *top_p, const uint32_t *seed,
+               const int32_t *pos, swl_stream_t stream);
+
 /* ---- Paged attention, decode (flash-decoding, "paged attention v2") --------------------------
  * reference: paged_attn.py:9-108 (phase 1), :111-149 (phase 2), launcher :152-222
  * q[Bd, H, D] (token stride q_tok_stride), o[Bd, H, D] (token stride o_tok_stride).

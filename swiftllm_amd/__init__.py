@@ -2,13 +2,14 @@
 
 Public names match the reference package (swiftllm/__init__.py:1-9): `EngineConfig`,
 `LlamaModel`, and — imported lazily because they pull in the serving stack — `Engine`,
-`RawRequest`.
+`RawRequest`. `SamplingParams` is an addition (the reference samples greedily only).
 """
 from swiftllm_amd.engine_config import EngineConfig
 from swiftllm_amd.model_config import LlamaModelConfig
+from swiftllm_amd.sampling_params import SamplingParams
 from swiftllm_amd.worker.model import LlamaModel
 
-__all__ = ["EngineConfig", "LlamaModelConfig", "LlamaModel", "Engine", "RawRequest"]
+__all__ = ["EngineConfig", "LlamaModelConfig", "LlamaModel", "SamplingParams", "Engine", "RawRequest"]
 
 
 def __getattr__(name):

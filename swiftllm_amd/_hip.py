@@ -41,6 +41,7 @@ SIGNATURES = {
                                     _I32, _I32, _I32, _I64, _I64, _I64, _I32, _P],
     "swl_silu_mul": [_P, _I64, _I32, _I32, _P],
     "swl_argmax": [_P, _P, _P, ctypes.c_size_t, _I64, _I32, _I64, _I32, _P],
+    "swl_sample": [_P, _P, _I64, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P],
     "swl_paged_attn_decode": [_P, _P, _P, _P, _P, _P, _P, _P, _F32, _I32, _I32, _I32, _I32, _I32,
                               _I32, _I32, _I32, _I32, _I32, _I64, _I64, _I32, _P],
     "swl_paged_attn_phase1": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F32, _I32, _I32, _I32, _I32,

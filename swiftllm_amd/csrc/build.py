@@ -28,6 +28,7 @@ SOURCES = [
     "gemm_wide.hip",
     "gemm_rows.hip",
     "argmax.hip",
+    "sampling.hip",
     "decode_engine.hip",
 ]
 HEADERS = ["swl_common.h", "attend_block.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]

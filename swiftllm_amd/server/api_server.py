@@ -3,13 +3,15 @@
     python -m swiftllm_amd.server.api_server --model-path DIR [--port 8000] [engine flags]
 
 `POST /generate` with JSON {prompt | prompt_token_ids, output_len, stream?, decode?} — the request
-format of the reference's swiftllm/server/api_server.py:16-84: non-streaming answers
+format of the reference's swiftllm/server/api_server.py:16-84, plus optional sampling fields (temperature,
+top_k, top_p, seed; absent = greedy, as in the reference): non-streaming answers
 {"output_token_ids": [...]} (or {"output": text} with decode), streaming sends one line per token.
 `GET /load` reports outstanding tokens (used by the replica router). Any engine failure takes the
 process down (reference api_server.py:114-119) so a supervisor can restart the replica.
 """
 import argparse
 import asyncio
+import math
 import os
 import traceback
 
@@ -18,6 +20,7 @@ import uvicorn
 from fastapi.responses import JSONResponse, StreamingResponse
 
 from swiftllm_amd.engine_config import EngineConfig
+from swiftllm_amd.sampling_params import SamplingParams
 from .engine import Engine
 from .structs import RawRequest
 
@@ -41,7 +44,35 @@ def _validate_body(body) -> "str | None":
             return "prompt_token_ids out of range"
     if not isinstance(body.get("prompt", ""), str):    # also when token ids are given: the handler still touches it
         return "prompt must be a string"
+    return _validate_sampling(body)
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _validate_sampling(body) -> "str | None":
+    t = body.get("temperature")
+    if t is not None and (not (_is_int(t) or isinstance(t, float)) or not math.isfinite(t) or t < 0):
+        return "temperature must be a finite number >= 0"
+    k = body.get("top_k")
+    if k is not None and (not _is_int(k) or k < 0 or k >= 2 ** 31):
+        return "top_k must be an integer >= 0"
+    p = body.get("top_p")
+    if p is not None and (not (_is_int(p) or isinstance(p, float)) or not 0 < p <= 1):
+        return "top_p must be a number in (0, 1]"
+    s = body.get("seed")
+    if s is not None and (not _is_int(s) or not 0 <= s < 2 ** 64):
+        return "seed must be an integer in [0, 2**64)"
     return None
+
+
+def _sampling_params(body) -> "SamplingParams | None":
+    if all(body.get(f) is None for f in ("temperature", "top_k", "top_p", "seed")):
+        return None
+    return SamplingParams(temperature=float(body.get("temperature") or 0.0), top_k=int(body.get("top_k") or 0),
+                          top_p=float(body.get("top_p") if body.get("top_p") is not None else 1.0),
+                          seed=body.get("seed"))
 
 
 def build_app(engine: Engine) -> fastapi.FastAPI:
@@ -57,7 +88,8 @@ def build_app(engine: Engine) -> fastapi.FastAPI:
         problem = _validate_body(body)
         if problem is not None:
             return JSONResponse({"error": problem}, status_code=400)
-        raw = RawRequest(body.get("prompt", ""), body["output_len"], body.get("prompt_token_ids"))
+        raw = RawRequest(body.get("prompt", ""), body["output_len"], body.get("prompt_token_ids"),
+                         sampling_params=_sampling_params(body))
         want_text = bool(body.get("decode", False))
         cost = raw.output_len + len(raw.prompt_token_ids or raw.prompt.split())
         state["outstanding_tokens"] += cost

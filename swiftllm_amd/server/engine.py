@@ -207,8 +207,12 @@ class Engine:
             input_ids = [r.prompt_token_ids if r.is_prefill_stage() else [r.output_token_ids[-1]] for r in batch]
             seq_ids = [r.request_id for r in batch]
             decoding_lens = [r.num_tokens() for r in batch if not r.is_prefill_stage()]
+            sampling = [r.sampling_params for r in batch]
             try:
-                tokens = self.model.forward(input_ids, seq_ids, decoding_lens)
+                if any(sp is not None for sp in sampling):     # (all-greedy: the reference's three-argument call)
+                    tokens = self.model.forward(input_ids, seq_ids, decoding_lens, sampling_params=sampling)
+                else:
+                    tokens = self.model.forward(input_ids, seq_ids, decoding_lens)
             finally:
                 self._post_undelivered()    # (a data plane without the hook, or a forward that raised before launching)
             self.num_forwards += 1

@@ -4,6 +4,8 @@ import asyncio
 import dataclasses
 from typing import List, Optional
 
+from swiftllm_amd.sampling_params import SamplingParams
+
 
 @dataclasses.dataclass
 class StepOutput:
@@ -14,12 +16,15 @@ class StepOutput:
 
 class RawRequest:
     """What a user submits: a prompt and how many tokens to generate. `prompt_token_ids` may be given
-    instead of text (tokenizer-less use: benchmarks, synthetic checkpoints)."""
+    instead of text (tokenizer-less use: benchmarks, synthetic checkpoints). `sampling_params` (an addition to the
+    reference): None or temperature 0 = greedy."""
 
-    def __init__(self, prompt: str, output_len: int, prompt_token_ids: Optional[List[int]] = None):
+    def __init__(self, prompt: str, output_len: int, prompt_token_ids: Optional[List[int]] = None, *,
+                 sampling_params: Optional[SamplingParams] = None):
         self.prompt = prompt
         self.output_len = output_len
         self.prompt_token_ids = prompt_token_ids
+        self.sampling_params = sampling_params
 
 
 class Request:
@@ -34,6 +39,10 @@ class Request:
         self.request_id = -1            # row of the block table, assigned when the request is admitted
         self.output_token_ids: List[int] = []
         self.error: Optional[str] = None    # set instead of scheduling when the request can never be served
+        # None = greedy. A None seed is resolved here, once: the stream depends on (seed, position) only, so the request
+        # draws the same tokens through preemption, swap-out and swap-in, in any batch, on any replica
+        sp = getattr(raw_request, "sampling_params", None)
+        self.sampling_params: Optional[SamplingParams] = None if sp is None or sp.greedy else sp.with_seed()
 
     def is_finished(self) -> bool:
         return len(self.output_token_ids) >= self.output_len

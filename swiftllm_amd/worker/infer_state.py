@@ -1,7 +1,7 @@
 """LlamaInferState — the per-forward metadata bundle handed to every operator.
 
 Field-compatible with the reference's swiftllm/worker/infer_state.py:4-29 (same names and meaning:
-this is the kernel-argument contract), plus three optional fields this implementation uses to keep
+this is the kernel-argument contract), plus four optional fields this implementation uses to keep
 the hot path free of extra launches.
 """
 import dataclasses
@@ -45,3 +45,6 @@ class LlamaInferState:
     last_token_indices: Optional[torch.Tensor] = None   # [batch_size] int32
     # Preallocated fp32 scratch for the flash-decoding partials.
     paged_attn_scratch: Optional[torch.Tensor] = None
+    # A sampled step (some row not greedy): the per-row parameters and `pos` (= the plan's seq_lengths view, the index
+    # the sampled token takes) as kernels/sampling.SampleArgs. None: every row is greedy (argmax).
+    sampling: Optional[object] = None

@@ -1,9 +1,10 @@
-"""Final norm, lm_head and greedy sampling. Reference: swiftllm/worker/layers/post_layer.py:9-40."""
+"""Final norm, lm_head and sampling (greedy, or seeded when the step is sampled). Reference:
+swiftllm/worker/layers/post_layer.py:9-40."""
 import torch
 
 from ..kernels.rmsnorm import rmsnorm_inplace
 from ..kernels.linear import linear
-from ..kernels.sampling import argmax_rows
+from ..kernels.sampling import argmax_rows, sample_rows
 
 
 class LlamaPostLayer:
@@ -27,13 +28,16 @@ class LlamaPostLayer:
                              device=input_embds.device, dtype=torch.int32)))
         last_input = input_embds.index_select(0, idx)    # fresh [batch, hidden] copy
         rmsnorm_inplace(last_input, self.weights.final_norm, self.model_config.rms_norm_eps)
-        return self.forward_normed(last_input)
+        return self.forward_normed(last_input, sampling=infer_state.sampling)
 
-    def forward_normed(self, last_input: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
-        """lm_head + greedy sampling on rows that already went through the final norm (a pure-decode batch whose
-        last add + norm ran fused on the split-K partials of the last down projection: every row is a last token)."""
+    def forward_normed(self, last_input: torch.Tensor, out: torch.Tensor = None, sampling=None) -> torch.Tensor:
+        """lm_head + sampling on rows that already went through the final norm (a pure-decode batch whose
+        last add + norm ran fused on the split-K partials of the last down projection: every row is a last token).
+        `sampling`: the step's kernels/sampling.SampleArgs, or None for an all-greedy step (argmax, as before)."""
         logits = linear(last_input, self.weights.lm_head, self.skinny)   # [batch, vocab]
         self.last_logits = logits
         if self.logits_tap is not None:
             self.logits_tap.append(logits)
+        if sampling is not None:
+            return sample_rows(logits, sampling, None, out)
         return argmax_rows(logits, out)

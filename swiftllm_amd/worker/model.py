@@ -22,13 +22,14 @@ The compute backend is libswiftllm_hip.so only; without a HIP device this class 
 import math
 import os
 import time
-from typing import List
+from typing import List, Optional
 
 import torch
 
 from swiftllm_amd import _hip
 from swiftllm_amd.engine_config import EngineConfig
 from swiftllm_amd.model_config import LlamaModelConfig
+from swiftllm_amd.sampling_params import SamplingParams, is_greedy
 from swiftllm_amd.utils import GB
 
 from .batch_plan import BatchPlan, plan_batch
@@ -38,6 +39,7 @@ from .infer_state import LlamaInferState
 from .kernels.block_swapping import swap_blocks
 from .kernels.linear import RawResidual
 from .kernels.rmsnorm import fused_add_rmsnorm_from_splitk, rmsnorm_inplace
+from .kernels.sampling import device_args, pack_params
 from .layers.pre_layer import LlamaPreLayer
 from .layers.transformer_layer import LlamaTransformerLayer
 from .layers.post_layer import LlamaPostLayer
@@ -62,7 +64,7 @@ class _DecodeGraph:
 
 class _DecodeLookahead:
     """Everything the NEXT decode step of the same batch needs, prepared while the GPU was still busy with this one."""
-    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev")
+    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev", "sampling")
 
 
 class LlamaModel:
@@ -110,6 +112,9 @@ class LlamaModel:
         self.graph_captures = 0      # hipGraph captures so far (the first at a batch bucket = one warm-up forward + one capture)
         self.graph_capture_s = 0.0   # host seconds spent in them: serving reports both
         self._warmed_buckets = set()
+        # per-row sampling parameters of a sampled step: pinned staging + its device twin (fixed address: a sampled
+        # hipGraph reads it on every replay), laid out by kernels/sampling.pack_params; one H2D copy per sampled step
+        self._sample_host = self._sample_host_np = self._sample_dev = self._sample_done = None
 
     # ------------------------------------------------------------------------------------------------
     @torch.inference_mode()
@@ -132,6 +137,9 @@ class LlamaModel:
         ]
         self.post_layer = LlamaPostLayer(self.model_config, self.weight)
         self.post_layer.skinny = bool(getattr(self.engine_config, "use_skinny_gemm", False))
+        # (allocated before profile_num_blocks measures: the largest replay bucket's rows)
+        ecfg = self.engine_config
+        self._ensure_sampling_rows(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
 
     def _tune_routes(self):
         """Which side serves the 65..256-token decode projections of THIS model on THIS device is decided here, once, before
@@ -344,7 +352,27 @@ class LlamaModel:
         self._meta_done.record()
         return {name: self._meta_dev[off:off + n] for name, off, n in layout}
 
-    def _make_infer_state(self, plan: BatchPlan, dev: dict, ignore_kvcache: bool) -> LlamaInferState:
+    def _ensure_sampling_rows(self, rows: int):
+        cap = 0 if self._sample_dev is None else self._sample_dev.numel() // 5
+        if cap >= rows:
+            return
+        cap = max(rows, 2 * cap)
+        self._sample_host = torch.empty(5 * cap, dtype=torch.int32, pin_memory=True)
+        self._sample_host_np = self._sample_host.numpy()
+        self._sample_dev = torch.zeros(5 * cap, dtype=torch.int32, device=self.device)
+        self._sample_done = torch.cuda.Event()
+        self._drop_decode_graphs()     # captured sampled graphs point into the old buffer
+
+    def _upload_sampling(self, params: List[Optional[SamplingParams]], rows: int):
+        """One async H2D copy of the step's per-row parameters (seeds resolved; rows past the caller's batch: greedy)."""
+        self._ensure_sampling_rows(rows)
+        self._sample_done.synchronize()     # (the previous step's copy out of the pinned buffer: long done)
+        pack_params(params, self._sample_host_np)
+        self._sample_dev.copy_(self._sample_host, non_blocking=True)
+        self._sample_done.record()
+
+    def _make_infer_state(self, plan: BatchPlan, dev: dict, ignore_kvcache: bool,
+                          sampled: bool = False) -> LlamaInferState:
         nsb = plan.num_seq_blocks
         if nsb > 1:
             need = _hip.scratch_bytes(plan.num_decoding_seqs, self.model_config.num_q_heads,
@@ -365,7 +393,8 @@ class LlamaModel:
             position_cos=self._cos_cached, position_sin=self._sin_cached,
             ignore_kvcache=ignore_kvcache,
             position_indices=dev["position_indices"], last_token_indices=dev["last_token_indices"],
-            paged_attn_scratch=self._scratch if nsb > 1 else None)
+            paged_attn_scratch=self._scratch if nsb > 1 else None,
+            sampling=device_args(self._sample_dev, dev["seq_lengths"]) if sampled else None)
 
     @torch.inference_mode()
     def _forward(self, input_ids: torch.Tensor, infer_state: LlamaInferState) -> torch.Tensor:
@@ -377,7 +406,7 @@ class LlamaModel:
                                   infer_state.seq_ids, infer_state.decoding_seq_lens, self._cos_cached, self._sin_cached,
                                   self.engine_config.max_blocks_per_seq)
             rmsnorm_inplace(x, self.weight.final_norm, self.model_config.rms_norm_eps)
-            return self.post_layer.forward_normed(x, out=self._engine.tok_err[:1])
+            return self.post_layer.forward_normed(x, out=self._engine.tok_err[:1], sampling=infer_state.sampling)
         x = self.pre_layer.forward(input_ids)
         residual = torch.zeros_like(x)
         block_table = None if infer_state.ignore_kvcache else self.gpu_block_manager.block_table
@@ -386,12 +415,12 @@ class LlamaModel:
         if isinstance(x, RawResidual):          # the last down projection added itself into the residual (rows_decode):
             x = residual.clone()                # pure decode, every row a last token — final norm of the residual rows
             rmsnorm_inplace(x, self.weight.final_norm, self.model_config.rms_norm_eps)
-            return self.post_layer.forward_normed(x)
+            return self.post_layer.forward_normed(x, sampling=infer_state.sampling)
         if not isinstance(x, torch.Tensor):     # the last down projection left as split-K partials
             if infer_state.num_prefill_seqs == 0:
                 # pure decode: every row is a last token — reduce + residual add + final norm in one launch
                 x = fused_add_rmsnorm_from_splitk(x, residual, self.weight.final_norm, self.model_config.rms_norm_eps)
-                return self.post_layer.forward_normed(x)
+                return self.post_layer.forward_normed(x, sampling=infer_state.sampling)
             x = x.materialize()
         x += residual
         return self.post_layer.forward(x, infer_state)
@@ -484,24 +513,26 @@ class LlamaModel:
         plan.num_real_seqs = b
         return plan
 
-    def _forward_decode_graph(self, plan: BatchPlan, dev: dict) -> torch.Tensor:
+    def _forward_decode_graph(self, plan: BatchPlan, dev: dict, sampled: bool = False) -> torch.Tensor:
         sbs, nsb_cap = self._graph_bucket(plan)
         use_engine = self._engine is not None and plan.batch_size == 1
         tap = self.post_layer.logits_tap
         tap_len = len(tap) if tap is not None else 0
         # (the engine has one launch geometry; a graph captured while a test taps the logits keeps its [B, vocab] tensor
         # alive in the shared pool, one captured without the tap does not — up to 65 MB per graph at 256 sequences)
-        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None,)
+        # (a sampled step is a graph of its own: its sampler reads the persistent parameter buffer; greedy graphs are as
+        # they were)
+        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None, sampled)
         entry = self._decode_graphs.pop(key, None)
         plan.seq_block_size, plan.num_seq_blocks = sbs, nsb_cap
         if entry is None:
             self.graph_captures += 1
             t_cap = time.perf_counter()
-            state = self._make_infer_state(plan, dev, False)
+            state = self._make_infer_state(plan, dev, False, sampled)
             # one eager run on a side stream first (library handles, workspaces, allocator pools): nothing may be lazily
             # initialised while the stream is capturing. Once per BATCH BUCKET (r06b): a new split geometry at a batch size
             # that has been captured before launches the same kernels on the same shapes — only the attention grid moves.
-            warm_key = (key[0], use_engine, tap is not None)
+            warm_key = (key[0], use_engine, tap is not None, sampled)
             if warm_key not in self._warmed_buckets:
                 warm = torch.cuda.Stream()
                 warm.wait_stream(torch.cuda.current_stream())
@@ -535,7 +566,7 @@ class LlamaModel:
         return entry.out_tokens[:n]
 
     # ---- decode look-ahead: the host side of step k+1 runs while the GPU executes step k ---------------------------------
-    def _prepare_next_decode(self, plan: BatchPlan, seq_ids_list: List[int], tokens_dev: torch.Tensor):
+    def _prepare_next_decode(self, plan: BatchPlan, seq_ids_list: List[int], tokens_dev: torch.Tensor, sampling=None):
         """Called right after the graph of a pure-decode step was launched, before the host blocks on its tokens. A
         generation loop calls forward again with the same sequences, every length + 1 and the tokens just sampled: plan
         that step now (numpy) and enqueue — behind the running graph, on the same stream — the H2D copy of its metadata and
@@ -563,15 +594,17 @@ class LlamaModel:
         dev["input_ids"][:b].copy_(tokens_dev)  # int64 -> int32 on the device: the host has not seen them yet (inert rows: 0)
         la = _DecodeLookahead()
         la.seq_ids, la.lens, la.plan, la.dev, la.tokens = list(seq_ids_list), next_lens, nxt, dev, None
+        la.sampling = sampling      # (the parameter buffer keeps this step's rows: the next step may reuse it as it is)
         return la
 
-    def _take_lookahead(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache):
-        """The prepared step, if this call is it (any other call drops the preparation)."""
+    def _take_lookahead(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None):
+        """The prepared step, if this call is it (any other call drops the preparation). A sampled step hits only with
+        the per-row parameters (seeds resolved) of the step it was prepared after: those are still on the device."""
         la, self._lookahead = self._lookahead, None
         if (la is None or la.tokens is None or ignore_kvcache or not self._decode_lookahead
                 or not getattr(self.engine_config, "use_hip_graph", False)
                 or len(input_ids_list) != len(la.lens) or list(decoding_seq_lens_list) != la.lens
-                or list(seq_ids_list) != la.seq_ids):
+                or list(seq_ids_list) != la.seq_ids or sampling != getattr(la, "sampling", None)):
             return None
         for ids, tok in zip(input_ids_list, la.tokens):
             if len(ids) != 1 or ids[0] != tok:
@@ -592,29 +625,39 @@ class LlamaModel:
 
     @torch.inference_mode()
     def forward(self, input_ids_list: List[List[int]], seq_ids_list: List[int],
-                decoding_seq_lens_list: List[int], ignore_kvcache: bool = False) -> List[int]:
+                decoding_seq_lens_list: List[int], ignore_kvcache: bool = False,
+                sampling_params: Optional[List[Optional[SamplingParams]]] = None) -> List[int]:
         """One iteration: prefill sequences first, then decoding sequences (one token each, their
-        lengths in `decoding_seq_lens_list` INCLUDE that token). Returns the greedy next token of
-        every sequence. Reference: model.py:252-359."""
+        lengths in `decoding_seq_lens_list` INCLUDE that token). Returns the next token of every
+        sequence: greedy (the reference, model.py:252-359), or — for the entries of `sampling_params`
+        (aligned with `input_ids_list`) that are not greedy — a seeded draw at the position the token
+        takes (a None seed draws a fresh one for this call). All-greedy steps launch what they always did."""
         if len(input_ids_list) == 0:
             return []   # the reference's idle engine calls forward([], [], []) in a loop
         _require_hip_device()
+        sampling = None
+        if sampling_params is not None:
+            if len(sampling_params) != len(input_ids_list):
+                raise ValueError("sampling_params must be aligned with input_ids_list")
+            if not all(is_greedy(p) for p in sampling_params):
+                sampling = [None if is_greedy(p) else p.with_seed() for p in sampling_params]
         try:
-            return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache)
+            return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling)
         except _decode_engine.DecodeEngineError as exc:
             # bounded hand-off timed out inside the persistent one-sequence step: its KV writes are re-done below with the
             # same values by the multi-launch HIP path, which serves one-sequence steps from here on
             self._engine_failed(int(str(exc)))
-            return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache)
+            return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling)
 
-    def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache):
+    def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None):
         prof = self._host_prof
         t0 = time.perf_counter() if prof is not None else 0.0
-        la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache)
+        sampled = sampling is not None
+        la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling)
         if la is not None:      # the step that was prepared while the previous one ran: blocks, then the launch
             self.gpu_block_manager.allocate_blocks_for_seqs(la.seq_ids, la.lens)   # (the real sequences only)
-            tokens = self._forward_decode_graph(la.plan, la.dev)
-            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens)
+            tokens = self._forward_decode_graph(la.plan, la.dev, sampled)
+            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens, sampling)
             if self.after_launch_hook is not None:
                 self.after_launch_hook()
             t4 = time.perf_counter() if prof is not None else 0.0
@@ -648,17 +691,19 @@ class LlamaModel:
             self.gpu_block_manager.allocate_blocks_for_seqs(seq_ids_list, plan.seq_lengths_list[:num_real])
         t2 = time.perf_counter() if prof is not None else 0.0
         dev = self._upload_plan(plan)
+        if sampled:
+            self._upload_sampling(sampling, plan.batch_size)
         t3 = time.perf_counter() if prof is not None else 0.0
         pure_decode = plan.num_prefill_seqs == 0
         nxt = None
         if (pure_decode and not ignore_kvcache and getattr(self.engine_config, "use_hip_graph", False)):
-            tokens = self._forward_decode_graph(plan, dev)
+            tokens = self._forward_decode_graph(plan, dev, sampled)
             if self._decode_lookahead:
-                nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens)
+                nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens, sampling)
         else:
             if pure_decode and not ignore_kvcache and self._eager_uses_graph_buckets:
                 plan.seq_block_size, plan.num_seq_blocks = self._graph_bucket(plan)
-            tokens = self._forward(dev["input_ids"], self._make_infer_state(plan, dev, ignore_kvcache))[:num_real]
+            tokens = self._forward(dev["input_ids"], self._make_infer_state(plan, dev, ignore_kvcache, sampled))[:num_real]
             tap = self.post_layer.logits_tap
             if tap and plan.batch_size > num_real:      # (tests) a padded eager step: the real rows only, as on replay
                 tap[-1] = tap[-1][:num_real]
