@@ -96,6 +96,26 @@ int swl_rotary_store_kv_prefill(void *q, void *k, const void *v, const void *cos
                                 int32_t num_q_heads, int32_t num_kv_heads, int32_t block_size, int32_t head_dim,
                                 int32_t max_blocks_per_seq, int64_t q_tok_stride, int64_t k_tok_stride,
                                 int64_t v_tok_stride, int32_t dtype, swl_stream_t stream);
+/* Stores at an offset (chunked prefill; an addition, the reference always writes a prompt from position 0): the two
+ * entries above plus ctx_lens (int32 [Bp], device). Sequence s already holds c = ctx_lens[s] tokens; token t of its chunk
+ * goes to logical position c + t: pool[block_table[seq_id, (c + t) / bs], layer, kvh, (c + t) % bs, :]. A chunk may start
+ * and end inside a block; no other slot of the pool is written. The caller guarantees that the sequence's table row
+ * holds ceil((c + n) / bs) blocks. pos_idx == NULL: the rope row of token t is c + t. All ctx_lens zero: the bits of the
+ * twin entry. head_dim % 8 != 0 (store) / not in {32, 64, 128, 256} (rotary + store): SWL_ERR_UNSUPPORTED. */
+int swl_store_kv_prefill_at(void *k_cache, void *v_cache, const void *k, const void *v,
+                            const int32_t *block_table, const int32_t *seq_ids, const int32_t *start_locs,
+                            const int32_t *seq_lens, const int32_t *ctx_lens, int32_t num_prefill_seqs,
+                            int32_t max_prefill_len, int32_t cur_layer, int32_t num_layers, int32_t num_kv_heads,
+                            int32_t block_size, int32_t head_dim, int32_t max_blocks_per_seq, int64_t k_tok_stride,
+                            int64_t v_tok_stride, int32_t dtype, swl_stream_t stream);
+int swl_rotary_store_kv_prefill_at(void *q, void *k, const void *v, const void *cos_table, const void *sin_table,
+                                   const int32_t *pos_idx, void *k_cache, void *v_cache, const int32_t *block_table,
+                                   const int32_t *seq_ids, const int32_t *start_locs, const int32_t *seq_lens,
+                                   const int32_t *ctx_lens, int32_t num_prefill_seqs, int32_t max_prefill_len,
+                                   int32_t cur_layer, int32_t num_layers, int32_t num_q_heads, int32_t num_kv_heads,
+                                   int32_t block_size, int32_t head_dim, int32_t max_blocks_per_seq, int64_t q_tok_stride,
+                                   int64_t k_tok_stride, int64_t v_tok_stride, int32_t dtype, swl_stream_t stream);
+
 /* reference: kvcache_mgmt.py:50-79 (_fwd_kvcache_mgmt_decoding_kernel), launcher :111-122
  * For decoding seq i (length len_i INCLUDING the new token): token i of k/v goes to slot
  * (block_table[seq_id, (len-1)/bs], (len-1)%bs). */
@@ -194,6 +214,24 @@ int swl_prefill_attn_varlen(void *o, const void *q, const void *k, const void *v
                             int32_t head_dim, float softmax_scale, int64_t q_tok_stride,
                             int64_t k_tok_stride, int64_t v_tok_stride, int64_t o_tok_stride,
                             int32_t dtype, swl_stream_t stream);
+
+/* ---- Prefill attention over the paged pool (chunked prefill; an addition, no reference counterpart) -------------
+ * Sequence s (block-table row seq_ids[s]) has c = ctx_lens[s] tokens in the pool and n = cu_seqlens[s+1] - cu_seqlens[s]
+ * new ones, rows [cu[s], cu[s+1]) of q[P, H, D] / o[P, H, D]; their rotated K and V were stored at logical positions
+ * [c, c + n) by the _at store that precedes this call on the same stream. Row i (absolute position c + i) attends to
+ * keys j <= c + i; ALL K/V, the chunk's own included, is read from the pools through block_table. c is any value >= 0
+ * (c = 0: a plain causal prefill), n = 0 sequences are inert. Slots past c + n and blocks outside the table are never
+ * read (they may hold NaN / Inf). Arithmetic and error bounds are those of swl_prefill_attn_varlen.
+ * max_new_len >= every n, max_total_len >= every c + n and ceil(max_total_len / 16) <= max_blocks_per_seq (checked: the
+ * kernel reads that many entries of a table row). D in {32, 64, 128}; block_size == 16 (else SWL_ERR_UNSUPPORTED);
+ * q, o and the pools 16-byte aligned, q/o token strides multiples of 8 elements and >= H * D. */
+int swl_prefill_attn_paged(void *o, const void *q, const void *k_cache, const void *v_cache,
+                           const int32_t *block_table, const int32_t *seq_ids, const int32_t *cu_seqlens,
+                           const int32_t *ctx_lens, int32_t num_prefill_seqs, int32_t max_new_len,
+                           int32_t max_total_len, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim,
+                           int32_t num_layers, int32_t block_size, int32_t cur_layer, int32_t max_blocks_per_seq,
+                           float softmax_scale, int64_t q_tok_stride, int64_t o_tok_stride, int32_t dtype,
+                           swl_stream_t stream);
 
 /* ---- Block-table maintenance ------------------------------------------------------------------
  * reference: block_mgmt.py:5-46 (set), :49-80 (unset), :83-127 (gather + unset)

@@ -39,6 +39,10 @@ SIGNATURES = {
                             _I64, _I64, _I32, _P],
     "swl_rotary_store_kv_prefill": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32,
                                     _I32, _I32, _I32, _I64, _I64, _I64, _I32, _P],
+    "swl_store_kv_prefill_at": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32,
+                                _I32, _I32, _I64, _I64, _I32, _P],
+    "swl_rotary_store_kv_prefill_at": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32,
+                                       _I32, _I32, _I32, _I32, _I64, _I64, _I64, _I32, _P],
     "swl_silu_mul": [_P, _I64, _I32, _I32, _P],
     "swl_argmax": [_P, _P, _P, ctypes.c_size_t, _I64, _I32, _I64, _I32, _P],
     "swl_sample": [_P, _P, _I64, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P],
@@ -51,6 +55,8 @@ SIGNATURES = {
     "swl_paged_attn_phase2": [_P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _P],
     "swl_prefill_attn_varlen": [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _F32, _I64, _I64,
                                 _I64, _I64, _I32, _P],
+    "swl_prefill_attn_paged": [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,
+                               _I32, _F32, _I64, _I64, _I32, _P],
     "swl_block_table_set": [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P],
     "swl_block_table_unset": [_P, _P, _P, _P, _I32, _I32, _P],
     "swl_block_table_gather": [_P, _P, _P, _P, _P, _P, _I32, _I32, _P],

@@ -21,6 +21,7 @@ SOURCES = [
     "silu_mul.hip",
     "paged_attn.hip",
     "prefill_attn.hip",
+    "prefill_attn_paged.hip",
     "block_table.hip",
     "swap_blocks.hip",
     "gemm_skinny.hip",

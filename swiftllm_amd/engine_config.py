@@ -54,6 +54,11 @@ class EngineConfig:
     # one of them selects between two parity-tested implementations of the same arithmetic and defaults to the faster one;
     # they exist so that tests and A/B measurements can hold one path against the other, not as deployment knobs.
     tuning: dict = None
+    # Chunked prefill: > 0 caps the PROMPT tokens of one step at min(max_prefill_chunk, max_tokens_in_batch) in total; a
+    # longer prompt is fed over several steps (each chunk attends to the paged KV cache: csrc/prefill_attn_paged.hip),
+    # running decodes ride along with every chunk step when the scheduler piggybacks, and a prompt longer than
+    # max_tokens_in_batch becomes servable. 0 (default): off — a prompt is one forward, as in the reference.
+    max_prefill_chunk: int = 0
 
     # Internal switches (all on): set through `tuning`, read by the layer code as plain attributes.
     TUNING_DEFAULTS = dict(
@@ -103,6 +108,8 @@ class EngineConfig:
                 f"{self.SUPPORTED_BLOCK_SIZE}-token KV blocks (pass --block-size {self.SUPPORTED_BLOCK_SIZE})")
         if self.dtype not in ("float16", "bfloat16"):
             raise ValueError(f"dtype must be 'float16' or 'bfloat16', got {self.dtype!r}")
+        if int(self.max_prefill_chunk) < 0:
+            raise ValueError(f"max_prefill_chunk must be >= 0 (0 = off), got {self.max_prefill_chunk}")
         unknown = set(self.tuning or ()) - set(self.TUNING_DEFAULTS)
         if unknown:
             raise ValueError(f"unknown tuning switches {sorted(unknown)}; known: {sorted(self.TUNING_DEFAULTS)}")
@@ -136,3 +143,5 @@ class EngineConfig:
                        help="(default) replay captured hipGraphs for pure-decode steps")
         g.add_argument("--no-hip-graph", dest="use_hip_graph", action="store_false")
         g.add_argument("--no-skinny-gemm", dest="use_skinny_gemm", action="store_false")
+        g.add_argument("--max-prefill-chunk", type=int, default=0,
+                       help="Chunked prefill: prompt tokens per forward, at most (0 = off: a prompt is one forward)")

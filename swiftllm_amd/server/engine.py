@@ -204,20 +204,33 @@ class Engine:
         if batch:
             # prefill sequences first (the scheduler orders them so), their whole prompt; decoding ones
             # bring their last token and their length INCLUDING it
-            input_ids = [r.prompt_token_ids if r.is_prefill_stage() else [r.output_token_ids[-1]] for r in batch]
+            # (chunked prefill: a prefill sequence brings the next `prefill_take` tokens of its prompt and the number of
+            # tokens already resident; without chunking that is the whole prompt behind a context of 0)
+            prefills = [r for r in batch if not r.is_prompt_resident()]
+            takes = {id(r): (r.prefill_take or r.prompt_len - r.num_prefilled) for r in prefills}
+            input_ids = [[r.output_token_ids[-1]] if r.is_prompt_resident() else
+                         r.prompt_token_ids if r.num_prefilled == 0 and takes[id(r)] == r.prompt_len else
+                         r.prompt_token_ids[r.num_prefilled:r.num_prefilled + takes[id(r)]] for r in batch]
             seq_ids = [r.request_id for r in batch]
-            decoding_lens = [r.num_tokens() for r in batch if not r.is_prefill_stage()]
+            decoding_lens = [r.num_tokens() for r in batch if r.is_prompt_resident()]
             sampling = [r.sampling_params for r in batch]
+            kwargs = {}
+            if any(sp is not None for sp in sampling):     # (all-greedy: the reference's three-argument call)
+                kwargs["sampling_params"] = sampling
+            if any(r.num_prefilled for r in prefills):      # (no resident context: the call of always)
+                kwargs["prefill_ctx_lens"] = [r.num_prefilled for r in prefills]
             try:
-                if any(sp is not None for sp in sampling):     # (all-greedy: the reference's three-argument call)
-                    tokens = self.model.forward(input_ids, seq_ids, decoding_lens, sampling_params=sampling)
-                else:
-                    tokens = self.model.forward(input_ids, seq_ids, decoding_lens)
+                tokens = self.model.forward(input_ids, seq_ids, decoding_lens, **kwargs)
             finally:
                 self._post_undelivered()    # (a data plane without the hook, or a forward that raised before launching)
             self.num_forwards += 1
             outputs, finished = [], []
             for req, tok in zip(batch, tokens):
+                if id(req) in takes:
+                    req.num_prefilled += takes[id(req)]
+                    req.prefill_take = 0
+                    if req.num_prefilled < req.prompt_len:
+                        continue        # not the last chunk: its token is discarded — nothing appended, nothing delivered
                 req.output_token_ids.append(tok)
                 done = req.is_finished()
                 outputs.append((req, tok, done))

@@ -5,6 +5,9 @@ batch is admitted while it fits the sequence/token/block budgets; otherwise ever
 decodes one token; when the pool cannot hold the running set the most recent requests are swapped out,
 and swapped requests return (oldest first) before any new prompt is admitted.
 
+Chunked prefill (`EngineConfig.max_prefill_chunk > 0`, an addition): a step carries at most that many prompt tokens, a
+longer prompt is fed over several steps while it sits in the running queue (`_get_next_batch_chunked`).
+
 Two deliberate differences:
   * `piggyback=True` lets the running (decoding) requests ride along with an admitted prefill batch in
     ONE forward (prefill sequences first, as LlamaModel.forward requires) — the SARATHI-style batch the
@@ -82,7 +85,7 @@ class Scheduler:
         if self.max_seq_len is not None and req.prompt_len + req.output_len > self.max_seq_len:
             return (f"prompt ({req.prompt_len}) + output_len ({req.output_len}) exceeds the model's "
                     f"{self.max_seq_len} rotary positions")
-        if req.prompt_len > ecfg.max_tokens_in_batch:
+        if req.prompt_len > ecfg.max_tokens_in_batch and self._chunk_cap() == 0:   # (chunked prefill feeds it in pieces)
             return f"prompt of {req.prompt_len} tokens exceeds max_tokens_in_batch ({ecfg.max_tokens_in_batch})"
         blocks = cdiv(req.prompt_len + req.output_len, ecfg.block_size)
         if blocks > ecfg.max_blocks_per_seq:
@@ -97,6 +100,8 @@ class Scheduler:
     def get_next_batch(self) -> Tuple[List[Request], List[Request], List[Request]]:
         """(batch to forward, requests to swap in first, requests to swap out first)."""
         ecfg = self.engine_config
+        if self._chunk_cap() > 0:
+            return self._get_next_batch_chunked()
         if not self.swapped_q:
             admitted = self._admit_prefills()
             if admitted:
@@ -126,6 +131,78 @@ class Scheduler:
                 used += need
                 swapped_in.append(cand)
         return list(self.running_q), swapped_in, swapped_out[::-1]
+
+    # ---- chunked prefill (EngineConfig.max_prefill_chunk > 0) ------------------------------------------------
+    def _chunk_cap(self) -> int:
+        """Prompt tokens one step may carry in total; 0 = chunking off (a prompt is one forward)."""
+        ecfg = self.engine_config
+        chunk = int(getattr(ecfg, "max_prefill_chunk", 0) or 0)
+        return min(chunk, ecfg.max_tokens_in_batch) if chunk > 0 else 0
+
+    def _get_next_batch_chunked(self) -> Tuple[List[Request], List[Request], List[Request]]:
+        """The same policy with a prompt fed in pieces. A request whose prompt is partly resident stays in running_q: it
+        holds its block-table row and its blocks (reserved for the WHOLE prompt at admission, as without chunking) and
+        counts towards max_batch_size, but it is not a decode rider. Every step: make room / swap in exactly as the
+        decode step does; hand the step's prompt-token budget to the partly prefilled requests in arrival order, then —
+        only when nobody waits swapped out and budget is left — to new prompts from the head of the queue (strict FCFS:
+        a partly fed prompt leaves no budget, so nothing overtakes it); the running decodes ride along when
+        piggybacking and their tokens and blocks fit, and decode alone in a step that carries no prompt tokens."""
+        ecfg = self.engine_config
+        swapped_out: List[Request] = []
+        used = self._running_blocks()
+        while len(self.running_q) > ecfg.max_batch_size or used > self.num_gpu_blocks:
+            victim = self.running_q.pop()           # the most recently admitted request yields, partly prefilled or not
+            used -= self._blocks(victim)
+            swapped_out.append(victim)
+        swapped_in: List[Request] = []
+        if swapped_out:
+            self.swapped_q.extendleft(swapped_out)
+        else:
+            while self.swapped_q:
+                cand = self.swapped_q[0]
+                need = self._blocks(cand)
+                if len(self.running_q) + 1 > ecfg.max_batch_size or used + need > self.num_gpu_blocks:
+                    break
+                self.running_q.append(self.swapped_q.popleft())     # (it continues at its num_prefilled)
+                used += need
+                swapped_in.append(cand)
+
+        budget = self._chunk_cap()
+        chunks: List[Request] = []
+        for req in self.running_q:
+            if req.is_prompt_resident():
+                continue
+            take = min(budget, req.prompt_len - req.num_prefilled)
+            if take <= 0:
+                break
+            req.prefill_take = take
+            chunks.append(req)
+            budget -= take
+        if not self.swapped_q:
+            while budget > 0 and self.waiting_q:
+                cand = self.waiting_q[0]
+                need = self._blocks(cand)
+                if len(self.running_q) + 1 > ecfg.max_batch_size or used + need > self.num_gpu_blocks:
+                    break       # strict FCFS: nothing may overtake the head of the queue
+                self.waiting_q.popleft()
+                cand.request_id = self.request_id_manager.get_id()
+                cand.prefill_take = min(budget, cand.prompt_len)
+                budget -= cand.prefill_take
+                used += need
+                self.running_q.append(cand)
+                chunks.append(cand)
+        decoders = [r for r in self.running_q if r.is_prompt_resident()]
+        if not chunks:
+            return decoders, swapped_in, swapped_out[::-1]
+        riders: List[Request] = []
+        if self.piggyback and decoders:
+            # blocks: `used` above already holds every decoder at the length this step leaves it with (num_tokens()
+            # counts the token it stores now) and every partly fed prompt whole; a decoder that outgrows the pool while a
+            # prompt is being fed makes the NEXT step swap out the most recent request — possibly that prompt, which
+            # then continues at its num_prefilled after swap-in
+            if sum(r.prefill_take for r in chunks) + len(decoders) <= ecfg.max_tokens_in_batch:
+                riders = decoders
+        return chunks + riders, swapped_in, swapped_out[::-1]
 
     def _admit_prefills(self) -> List[Request]:
         ecfg = self.engine_config

@@ -44,6 +44,11 @@ class Request:
         sp = getattr(raw_request, "sampling_params", None)
         self.sampling_params: Optional[SamplingParams] = None if sp is None or sp.greedy else sp.with_seed()
 
+        # chunked prefill: prompt tokens whose KV is resident (forwarded in earlier steps), and the tokens the scheduler
+        # gave this request in the step being built (0: not a prompt chunk / the whole rest of the prompt)
+        self.num_prefilled = 0
+        self.prefill_take = 0
+
     def is_finished(self) -> bool:
         return len(self.output_token_ids) >= self.output_len
 
@@ -52,6 +57,11 @@ class Request:
 
     def is_prefill_stage(self) -> bool:
         return not self.output_token_ids
+
+    def is_prompt_resident(self) -> bool:
+        """The whole prompt has been forwarded: the request decodes from here on. (`is_prefill_stage()` stays "no token
+        generated yet", which is also true between the chunks of a chunked prefill.)"""
+        return self.num_prefilled >= self.prompt_len or bool(self.output_token_ids)
 
     def num_tokens(self) -> int:
         """Tokens whose KV must be resident: the prompt plus everything generated so far."""

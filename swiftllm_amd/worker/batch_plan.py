@@ -6,7 +6,7 @@ indices, the seq_block_size heuristic) and post_layer.py:24-29 (last-token indic
 """
 import dataclasses
 import itertools
-from typing import List, Sequence
+from typing import List, Optional, Sequence
 
 import numpy as np
 
@@ -64,6 +64,10 @@ class BatchPlan:
     # sequences of the caller's batch; batch_size - num_real_seqs trailing rows are inert padding (length 0) that rounds a
     # pure-decode batch up to its hipGraph bucket (worker/model.py: _decode_batch_bucket). -1: not set = batch_size
     num_real_seqs: int = -1
+    # chunked prefill: tokens of each prefill sequence already resident in the KV pool (int32 [Bp]); None = every prompt
+    # starts at position 0 (no segment is packed then: the layout is what it always was)
+    prefill_ctx_lens: Optional[np.ndarray] = None
+    max_prefill_total_len: int = 0      # max over prefill sequences of context + new tokens
 
     @property
     def real_seqs(self) -> int:
@@ -82,6 +86,9 @@ class BatchPlan:
             n = getattr(self, name).size
             out.append((name, off, n))
             off += (n + 3) // 4 * 4
+        if self.prefill_ctx_lens is not None:       # appended: every offset above is the one of a plan without contexts
+            out.append(("prefill_ctx_lens", off, self.prefill_ctx_lens.size))
+            off += (self.prefill_ctx_lens.size + 3) // 4 * 4
         return out, off
 
     def pack_into(self, buf: np.ndarray) -> int:
@@ -93,9 +100,13 @@ class BatchPlan:
 
 def plan_batch(input_ids_list: Sequence[Sequence[int]], seq_ids_list: Sequence[int],
                decoding_seq_lens_list: Sequence[int], num_kv_heads: int,
-               num_slots: int = 256) -> BatchPlan:
+               num_slots: int = 256, prefill_ctx_lens: Optional[Sequence[int]] = None) -> BatchPlan:
     """Prefill sequences come first in all three lists (reference model.py:268-270); a decoding
-    sequence contributes exactly one token and its length INCLUDES that token."""
+    sequence contributes exactly one token and its length INCLUDES that token.
+
+    `prefill_ctx_lens` (chunked prefill; one entry per prefill sequence): tokens of the sequence that are already in
+    the KV pool. Its input ids are then the NEXT chunk of its prompt: positions ctx + 0..n-1, sequence length ctx + n
+    (the block-allocation target and the rotary-table check). None: every prompt starts at 0, the plan of always."""
     batch_size = len(input_ids_list)
     num_decoding = len(decoding_seq_lens_list)
     num_prefill = batch_size - num_decoding
@@ -116,13 +127,24 @@ def plan_batch(input_ids_list: Sequence[Sequence[int]], seq_ids_list: Sequence[i
         # 0..len-1 for every prefill sequence: global arange minus each token's sequence start
         pos[:num_prefill_tokens] = (np.arange(num_prefill_tokens, dtype=np.int32)
                                     - np.repeat(starts_with_end[:-1], pl))
+    ctx = None
+    if prefill_ctx_lens is not None:
+        ctx = np.asarray(prefill_ctx_lens, dtype=np.int32).reshape(-1)
+        if ctx.size != num_prefill:
+            raise ValueError("prefill_ctx_lens needs one entry per prefill sequence")
+        if ctx.size and int(ctx.min()) < 0:
+            raise ValueError("prefill_ctx_lens must be >= 0")
+        if num_prefill_tokens:
+            pos[:num_prefill_tokens] += np.repeat(ctx, pl)
     pos[num_prefill_tokens:] = dl - 1
     last = np.concatenate((starts_with_end[1:] - 1,
                            np.arange(num_prefill_tokens, num_tokens, dtype=np.int32))).astype(np.int32)
     sbs = select_seq_block_size(decoding_seq_lens_list, num_kv_heads, num_slots)
     max_dec = max(decoding_seq_lens_list) if num_decoding else 0
-    seq_lengths_list = prefill_lens + list(decoding_seq_lens_list)
+    total_lens = prefill_lens if ctx is None else [int(c) + n for c, n in zip(ctx, prefill_lens)]
+    seq_lengths_list = total_lens + list(decoding_seq_lens_list)
     return BatchPlan(
+        prefill_ctx_lens=ctx, max_prefill_total_len=max(total_lens) if total_lens else 0,
         batch_size=batch_size, num_tokens=num_tokens, num_prefill_seqs=num_prefill,
         num_prefill_tokens=num_prefill_tokens,
         max_prefill_len=max(prefill_lens) if prefill_lens else 0,

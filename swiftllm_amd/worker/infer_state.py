@@ -1,7 +1,7 @@
 """LlamaInferState — the per-forward metadata bundle handed to every operator.
 
 Field-compatible with the reference's swiftllm/worker/infer_state.py:4-29 (same names and meaning:
-this is the kernel-argument contract), plus four optional fields this implementation uses to keep
+this is the kernel-argument contract), plus a few optional fields this implementation uses to keep
 the hot path free of extra launches.
 """
 import dataclasses
@@ -48,3 +48,8 @@ class LlamaInferState:
     # A sampled step (some row not greedy): the per-row parameters and `pos` (= the plan's seq_lengths view, the index
     # the sampled token takes) as kernels/sampling.SampleArgs. None: every row is greedy (argmax).
     sampling: Optional[object] = None
+    # Chunked prefill: tokens of each prefill sequence already resident in the pool (int32 [num_prefill_seqs]); its new
+    # tokens take logical positions [ctx, ctx + len) and attend to the pool (kernels/prefill_attn.prefill_attention_paged).
+    # None: every prompt starts at position 0 and attends to its fresh projections — the reference's prefill.
+    prefill_ctx_lens: Optional[torch.Tensor] = None
+    max_prefill_total_len: int = 0      # max over prefill sequences of ctx + len (only read when prefill_ctx_lens is set)

@@ -9,7 +9,7 @@ from .linear import linear
 from .rmsnorm import rmsnorm_inplace, fused_add_rmsnorm_inplace
 from .rotary_emb import rotary_embedding_inplace
 from .kvcache_mgmt import store_kvcache
-from .prefill_attn import prefill_attention
+from .prefill_attn import prefill_attention, prefill_attention_paged
 from .paged_attn import paged_attention
 from .silu_and_mul import silu_and_mul_inplace
 from .block_mgmt import (
@@ -21,7 +21,7 @@ from .block_swapping import swap_blocks
 
 __all__ = [
     "linear", "rmsnorm_inplace", "fused_add_rmsnorm_inplace", "rotary_embedding_inplace",
-    "store_kvcache", "prefill_attention", "paged_attention", "silu_and_mul_inplace",
+    "store_kvcache", "prefill_attention", "prefill_attention_paged", "paged_attention", "silu_and_mul_inplace",
     "set_block_table_and_num_seq_alloc_blocks", "unset_block_table_and_num_seq_alloc_blocks",
     "gather_allocated_blocks_and_unset", "swap_blocks",
 ]

@@ -50,7 +50,7 @@ from ..kernels.rotary_emb import (rotary_embedding_inplace, rotary_embedding_and
                                   rotary_embedding_and_store_kvcache_decode_from_splitk,
                                   rotary_embedding_and_store_kvcache_prefill)
 from ..kernels.kvcache_mgmt import store_kvcache
-from ..kernels.prefill_attn import prefill_attention
+from ..kernels.prefill_attn import prefill_attention, prefill_attention_paged
 from ..kernels.paged_attn import paged_attention, paged_attention_from_qkv_splitk
 from ..kernels.silu_and_mul import silu_and_mul_inplace
 
@@ -276,7 +276,7 @@ class LlamaTransformerLayer:
             assert not st.ignore_kvcache
             stored = torch.cuda.Event()
             stored.record()
-            prefill_attention(q, k, v, o, cfg, ecfg, st)
+            self._prefill_attention(q, k, v, o, k_cache, v_cache, block_table, st)
             side = self.decoding_piggyback_stream
             with torch.cuda.stream(side):
                 side.wait_event(stored)
@@ -285,12 +285,22 @@ class LlamaTransformerLayer:
                 decoded.record()
             torch.cuda.current_stream().wait_event(decoded)
         elif st.num_prefill_seqs > 0:
-            prefill_attention(q, k, v, o, cfg, ecfg, st)
+            self._prefill_attention(q, k, v, o, k_cache, v_cache, block_table, st)
         elif st.num_decoding_seqs > 0:
             assert not st.ignore_kvcache
             paged_attention(q, k_cache, v_cache, block_table, cfg, ecfg, st, self.layer_id, o)
         q = k = v = None
         return self._forward_after_attention(input_embds, residual_buf, fast, st)
+
+    def _prefill_attention(self, q, k, v, o, k_cache, v_cache, block_table, st):
+        """Whole prompts attend to their fresh projections; prompt chunks behind a resident context (chunked prefill:
+        st.prefill_ctx_lens) attend to the pool, which the store above has just extended by the chunk."""
+        if getattr(st, "prefill_ctx_lens", None) is not None:
+            assert not st.ignore_kvcache
+            prefill_attention_paged(q, k_cache, v_cache, block_table, o, self.model_config, self.engine_config, st,
+                                    self.layer_id)
+        else:
+            prefill_attention(q, k, v, o, self.model_config, self.engine_config, st)
 
     def _forward_after_attention(self, input_embds, residual_buf, fast: bool, st):
         cfg, w = self.model_config, self.weight

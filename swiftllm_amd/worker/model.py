@@ -394,7 +394,8 @@ class LlamaModel:
             ignore_kvcache=ignore_kvcache,
             position_indices=dev["position_indices"], last_token_indices=dev["last_token_indices"],
             paged_attn_scratch=self._scratch if nsb > 1 else None,
-            sampling=device_args(self._sample_dev, dev["seq_lengths"]) if sampled else None)
+            sampling=device_args(self._sample_dev, dev["seq_lengths"]) if sampled else None,
+            prefill_ctx_lens=dev.get("prefill_ctx_lens"), max_prefill_total_len=plan.max_prefill_total_len)
 
     @torch.inference_mode()
     def _forward(self, input_ids: torch.Tensor, infer_state: LlamaInferState) -> torch.Tensor:
@@ -626,15 +627,24 @@ class LlamaModel:
     @torch.inference_mode()
     def forward(self, input_ids_list: List[List[int]], seq_ids_list: List[int],
                 decoding_seq_lens_list: List[int], ignore_kvcache: bool = False,
-                sampling_params: Optional[List[Optional[SamplingParams]]] = None) -> List[int]:
+                sampling_params: Optional[List[Optional[SamplingParams]]] = None,
+                prefill_ctx_lens: Optional[List[int]] = None) -> List[int]:
         """One iteration: prefill sequences first, then decoding sequences (one token each, their
         lengths in `decoding_seq_lens_list` INCLUDE that token). Returns the next token of every
         sequence: greedy (the reference, model.py:252-359), or — for the entries of `sampling_params`
         (aligned with `input_ids_list`) that are not greedy — a seeded draw at the position the token
-        takes (a None seed draws a fresh one for this call). All-greedy steps launch what they always did."""
+        takes (a None seed draws a fresh one for this call). All-greedy steps launch what they always did.
+
+        `prefill_ctx_lens` (chunked prefill; one entry per prefill sequence): tokens of that sequence already resident
+        in the KV pool from earlier calls. Its `input_ids` are then the next chunk of its prompt: the chunk is stored
+        behind the context and attends to the pool (csrc/prefill_attn_paged.hip). The token returned for it follows the
+        chunk's last token — the caller ignores it for every chunk but the last; a sampled draw is keyed by position, so
+        the final chunk draws what a whole-prompt prefill draws from the same logits. None or all zeros: today's path."""
         if len(input_ids_list) == 0:
             return []   # the reference's idle engine calls forward([], [], []) in a loop
         _require_hip_device()
+        prefill_ctx_lens = self._check_prefill_ctx(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache,
+                                                   prefill_ctx_lens)
         sampling = None
         if sampling_params is not None:
             if len(sampling_params) != len(input_ids_list):
@@ -642,14 +652,45 @@ class LlamaModel:
             if not all(is_greedy(p) for p in sampling_params):
                 sampling = [None if is_greedy(p) else p.with_seed() for p in sampling_params]
         try:
-            return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling)
+            return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
+                                      prefill_ctx_lens)
         except _decode_engine.DecodeEngineError as exc:
             # bounded hand-off timed out inside the persistent one-sequence step: its KV writes are re-done below with the
             # same values by the multi-launch HIP path, which serves one-sequence steps from here on
             self._engine_failed(int(str(exc)))
-            return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling)
+            return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
+                                      prefill_ctx_lens)
 
-    def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None):
+    def _check_prefill_ctx(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, ctx):
+        """Host-side refusals of a chunked-prefill call, before anything is launched or allocated. Returns the contexts
+        as a list, or None when there are none (None / all zeros: the whole-prompt path, bit for bit)."""
+        if ctx is None:
+            return None
+        ctx = [int(c) for c in ctx]
+        num_prefill = len(input_ids_list) - len(decoding_seq_lens_list)
+        if len(ctx) != num_prefill:
+            raise ValueError(f"prefill_ctx_lens needs one entry per prefill sequence ({num_prefill}), got {len(ctx)}")
+        if any(c < 0 for c in ctx):
+            raise ValueError("prefill_ctx_lens must be >= 0")
+        if not any(ctx):
+            return None
+        if ignore_kvcache:
+            raise ValueError("prefill_ctx_lens with ignore_kvcache=True: a context lives in the KV cache")
+        if self.gpu_block_manager is None:
+            raise RuntimeError("prefill_ctx_lens before init_kvcache_and_swap: there is no KV pool to hold a context")
+        bs = self.engine_config.block_size
+        rope_rows = self._cos_cached.shape[0]
+        for c, sid, ids in zip(ctx, seq_ids_list, input_ids_list):
+            have = self.gpu_block_manager.host.num_allocated(sid) * bs
+            if c > have:
+                raise ValueError(f"sequence {sid}: a context of {c} tokens, but its allocated KV blocks hold {have}")
+            if c + len(ids) > rope_rows:
+                raise RuntimeError(f"sequence {sid}: context {c} + {len(ids)} new tokens exceeds the rotary table "
+                                   f"({rope_rows} positions)")
+        return ctx
+
+    def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
+                      prefill_ctx_lens=None):
         prof = self._host_prof
         t0 = time.perf_counter() if prof is not None else 0.0
         sampled = sampling is not None
@@ -678,7 +719,7 @@ class LlamaModel:
             plan = self._plan_decode(seq_ids_list, list(decoding_seq_lens_list), input_ids_list, True)
         else:
             plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
-                              self.model_config.num_kv_heads, self._num_slots)
+                              self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
             plan.num_real_seqs = num_real
         longest = max(plan.seq_lengths_list)
         if longest > self._cos_cached.shape[0]:
