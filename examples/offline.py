@@ -25,12 +25,13 @@ def main():
     ap.add_argument("--dtype", default="float16", choices=["float16", "bfloat16"])
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--use-dummy", action="store_true")
+    ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8_e4m3"])
     args = ap.parse_args()
 
     cfg = swiftllm.EngineConfig(model_path=args.model_path, use_dummy=args.use_dummy, block_size=16,
                                 gpu_mem_utilization=0.9, num_cpu_blocks=0, max_seqs_in_block_table=128,
                                 max_blocks_per_seq=2048, max_batch_size=16, max_tokens_in_batch=2048 * 16,
-                                dtype=args.dtype, use_hip_graph=True)
+                                dtype=args.dtype, use_hip_graph=True, kv_cache_dtype=args.kv_cache_dtype)
     t0 = time.perf_counter()
     model = swiftllm.LlamaModel(cfg)
     model.load_weights()

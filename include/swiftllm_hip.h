@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define SWL_ABI_VERSION 1
+#define SWL_ABI_VERSION 2
 
 #define SWL_F16 0
 #define SWL_BF16 1
@@ -232,6 +232,60 @@ int swl_prefill_attn_paged(void *o, const void *q, const void *k_cache, const vo
                            int32_t num_layers, int32_t block_size, int32_t cur_layer, int32_t max_blocks_per_seq,
                            float softmax_scale, int64_t q_tok_stride, int64_t o_tok_stride, int32_t dtype,
                            swl_stream_t stream);
+
+/* ---- FP8 (OCP e4m3fn) KV cache (an addition, no reference counterpart; opt-in: EngineConfig.kv_cache_dtype) -------
+ * Storage contract (csrc/fp8_kv.h):
+ *   pools    [num_blocks, L, KVH, 16, D], ONE byte per element (torch.float8_e4m3fn); a (block, layer, kv-head) tile is
+ *            16 D bytes (2 KiB at D = 128); the host swap pools have the same layout.
+ *   scales   kv_scales fp32 [2, L, KVH] on the device: k_scale[layer, kvh] rows first, then v_scale (default: ones);
+ *            inv_scales, same shape, holds fp32(1 / scale) computed on the host.
+ *   store    stored = RNE_e4m3(clamp(fp32(x) * inv, -448, +448)); the clamp is explicit. Bit-exact host twin:
+ *            x.float().mul(inv).clamp(-448, 448).to(torch.float8_e4m3fn) (saturating, ties to even, e4m3 subnormals).
+ *   read     e4m3 -> the activation dtype is exact; k_scale is folded into the exp2 factor scale * log2(e) * k_scale,
+ *            v_scale multiplies the normalised output in fp32 before its one rounding. q, p and the accumulators are
+ *            what the 16-bit kernels use; the error bounds are theirs, on the stored values (code * scale).
+ *   NaN      codes 0x7f / 0xff are NaN; slots at or beyond a sequence's length may hold anything and are never allowed to
+ *            reach a product as anything but zeros.
+ * `dtype` is the dtype of the 16-bit side (k / v / q / o). Unlike their 16-bit twins these entries report a head_dim
+ * they are not built for as SWL_ERR_BAD_ARG. Everything is validated before any launch.
+ *
+ * swl_store_kv_prefill_at_fp8: swl_store_kv_prefill_at, quantising; ctx_lens == NULL means every context is 0 (whole
+ * prompts). swl_store_kv_decode_fp8: swl_store_kv_decode, quantising. head_dim % 16 == 0 (16-byte stores). */
+int swl_store_kv_prefill_at_fp8(void *k_cache, void *v_cache, const void *k, const void *v, const float *inv_scales,
+                                const int32_t *block_table, const int32_t *seq_ids, const int32_t *start_locs,
+                                const int32_t *seq_lens, const int32_t *ctx_lens, int32_t num_prefill_seqs,
+                                int32_t max_prefill_len, int32_t cur_layer, int32_t num_layers, int32_t num_kv_heads,
+                                int32_t block_size, int32_t head_dim, int32_t max_blocks_per_seq, int64_t k_tok_stride,
+                                int64_t v_tok_stride, int32_t dtype, swl_stream_t stream);
+int swl_store_kv_decode_fp8(void *k_cache, void *v_cache, const void *k, const void *v, const float *inv_scales,
+                            const int32_t *block_table, const int32_t *seq_ids, const int32_t *seq_lens,
+                            int32_t num_decoding_seqs, int32_t cur_layer, int32_t num_layers, int32_t num_kv_heads,
+                            int32_t block_size, int32_t head_dim, int32_t max_blocks_per_seq, int64_t k_tok_stride,
+                            int64_t v_tok_stride, int32_t dtype, swl_stream_t stream);
+/* swl_paged_attn_phase1 / swl_paged_attn_decode over the FP8 pools: same grid, split-K contract, partial format and
+ * scratch (swl_paged_attn_scratch_bytes); phase 2 is swl_paged_attn_phase2. One matrix-core path for G in {1, 2, 4, 8},
+ * D in {32, 64, 128}. */
+int swl_paged_attn_phase1_fp8(void *o_direct, const void *q, const void *k_cache, const void *v_cache,
+                              const float *kv_scales, const int32_t *block_table, const int32_t *seq_ids,
+                              const int32_t *seq_lens, float *mid_o, float *mid_lse, float softmax_scale,
+                              int32_t num_decoding_seqs, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim,
+                              int32_t num_layers, int32_t block_size, int32_t cur_layer, int32_t max_blocks_per_seq,
+                              int32_t seq_block_size, int32_t num_seq_blocks, int64_t q_tok_stride, int64_t o_tok_stride,
+                              int32_t dtype, swl_stream_t stream);
+int swl_paged_attn_decode_fp8(void *o, const void *q, const void *k_cache, const void *v_cache, const float *kv_scales,
+                              const int32_t *block_table, const int32_t *seq_ids, const int32_t *seq_lens, void *scratch,
+                              float softmax_scale, int32_t num_decoding_seqs, int32_t num_q_heads, int32_t num_kv_heads,
+                              int32_t head_dim, int32_t num_layers, int32_t block_size, int32_t cur_layer,
+                              int32_t max_blocks_per_seq, int32_t seq_block_size, int32_t num_seq_blocks,
+                              int64_t q_tok_stride, int64_t o_tok_stride, int32_t dtype, swl_stream_t stream);
+/* swl_prefill_attn_paged over the FP8 pools (the chunk's own keys are read back quantised). */
+int swl_prefill_attn_paged_fp8(void *o, const void *q, const void *k_cache, const void *v_cache, const float *kv_scales,
+                               const int32_t *block_table, const int32_t *seq_ids, const int32_t *cu_seqlens,
+                               const int32_t *ctx_lens, int32_t num_prefill_seqs, int32_t max_new_len,
+                               int32_t max_total_len, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim,
+                               int32_t num_layers, int32_t block_size, int32_t cur_layer, int32_t max_blocks_per_seq,
+                               float softmax_scale, int64_t q_tok_stride, int64_t o_tok_stride, int32_t dtype,
+                               swl_stream_t stream);
 
 /* ---- Block-table maintenance ------------------------------------------------------------------
  * reference: block_mgmt.py:5-46 (set), :49-80 (unset), :83-127 (gather + unset)

@@ -20,7 +20,7 @@ _LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", _LI
 
 SWL_F16 = 0
 SWL_BF16 = 1
-ABI_VERSION = 1
+ABI_VERSION = 2
 
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
@@ -57,6 +57,17 @@ SIGNATURES = {
                                 _I64, _I64, _I32, _P],
     "swl_prefill_attn_paged": [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,
                                _I32, _F32, _I64, _I64, _I32, _P],
+    # FP8 (e4m3fn) KV cache: the pool-side pointers are bytes, the scale tables fp32 [2, L, KVH]
+    "swl_store_kv_prefill_at_fp8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32,
+                                    _I32, _I32, _I64, _I64, _I32, _P],
+    "swl_store_kv_decode_fp8": [_P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32,
+                                _I64, _I64, _I32, _P],
+    "swl_paged_attn_phase1_fp8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F32, _I32, _I32, _I32, _I32,
+                                  _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I64, _I32, _P],
+    "swl_paged_attn_decode_fp8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F32, _I32, _I32, _I32, _I32, _I32,
+                                  _I32, _I32, _I32, _I32, _I32, _I64, _I64, _I32, _P],
+    "swl_prefill_attn_paged_fp8": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,
+                                   _I32, _I32, _F32, _I64, _I64, _I32, _P],
     "swl_block_table_set": [_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P],
     "swl_block_table_unset": [_P, _P, _P, _P, _I32, _I32, _P],
     "swl_block_table_gather": [_P, _P, _P, _P, _P, _P, _I32, _I32, _P],

@@ -22,6 +22,9 @@ SOURCES = [
     "paged_attn.hip",
     "prefill_attn.hip",
     "prefill_attn_paged.hip",
+    "kvcache_fp8.hip",
+    "paged_attn_fp8.hip",
+    "prefill_attn_paged_fp8.hip",
     "block_table.hip",
     "swap_blocks.hip",
     "gemm_skinny.hip",
@@ -32,7 +35,7 @@ SOURCES = [
     "sampling.hip",
     "decode_engine.hip",
 ]
-HEADERS = ["swl_common.h", "attend_block.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
+HEADERS = ["swl_common.h", "attend_block.h", "fp8_kv.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
 LIB = os.path.join(HERE, "libswiftllm_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 ARCH = "gfx950"

@@ -1,0 +1,456 @@
+// paged_attn_fp8.hip — flash-decoding phase 1 over the FP8 (e4m3fn) KV pool (gfx950). Storage contract: fp8_kv.h.
+//
+// The kernel of paged_attn.hip (paged_attn_phase1_kernel, matrix-core form) with half the bytes behind it: same grid
+// (seq-block, kv-head, sequence), one workgroup serving all G query heads of its kv-head, the same split-K contract, the
+// same partial format (mid_o = acc / sum, mid_lse = log2(sum) + max in the scaled base-2 domain), direct output with one
+// split — so swl_paged_attn_phase2 and swl_paged_attn_scratch_bytes serve both. Algorithmic bytes per call:
+// sum_i len_i * 2 * KVH * D * 1 + q/o + partials.
+//   * a 16-token x D tile of one (block, layer, kv-head) is 16 D BYTES, contiguous (2 KiB at D = 128); a lane's 16-byte
+//     non-temporal load carries 16 elements: two 1 KiB instructions per tile at D = 128 (the 16-bit kernel: four), one at
+//     D = 64, half a wave's worth at D = 32 (lanes 32..63 re-read the tile and do not stage it);
+//   * the raw codes wait in the register ring (kPa8Depth blocks per wave, K + V = 16 VGPRs each at D = 128; see
+//     SWL_PA8_DEPTH below for the depth); conversion to the activation dtype
+//     is exact (v_cvt_scalef32_pk_{f16,bf16}_fp8, scale 1) and sits between the ring and the wave-private LDS stage;
+//   * from the stage on it is attend_block_mfma: S = K.Q^T on 16x16x32 MFMA, one (m, l) pair per lane, P as hi + lo
+//     16-bit halves, O^T += V^T.P^T through ds_read_b64_tr_b16, mfma_results_ready before VALU reads the scores. ONE path
+//     for every G: at G = 1 the columns 1..15 of Q^T are zero;
+//   * k_scale[layer, kv-head] is uniform per workgroup: it is folded into c = scale * log2(e) * k_scale, the factor of
+//     every exp2 argument (scores stay un-scaled dot products of q with the stored codes' values); v_scale multiplies the
+//     normalised output / partial in fp32, before the one rounding;
+//   * the masked-garbage rule: 0x7f / 0xff are NaN and a slot past the sequence's length may hold them. A block that
+//     crosses the length has the codes of its rows >= len replaced by 0x00 (= +0) in registers before conversion, K and V
+//     alike; blocks wholly past it are never loaded. p = 0 then meets v = 0, never NaN.
+#include "fp8_kv.h"
+
+// Ring depth (16-token blocks resident per wave, one of them being attended). 2: at D = 128 the 8-wave kernel builds to
+// 181 VGPRs; the same source at depth 3 / 4 needs 256 + 320 / 596 spilled registers under the 2-waves-per-SIMD budget
+// (hipcc of ROCm 7.2, -Rpass-analysis=kernel-resource-usage), so deeper rings are an experiment build
+// (python -m swiftllm_amd.csrc.build --tag d3 -D SWL_PA8_DEPTH=3), not the product.
+#ifndef SWL_PA8_DEPTH
+#define SWL_PA8_DEPTH 2
+#endif
+
+namespace swl {
+
+constexpr int kBlk8 = 16;          // tokens per KV block
+constexpr int kPa8Depth = SWL_PA8_DEPTH;
+
+struct PagedAttnFp8Params {
+    void *o_direct;
+    const void *q;
+    const uint8_t *k_cache;
+    const uint8_t *v_cache;
+    const float *kv_scales;     // [2][L][KVH]
+    float *mid_o;
+    float *mid_lse;
+    float scale_log2e;
+    int H, KVH, L, layer, max_blocks_per_seq, seq_block_size, num_seq_blocks;
+    int64_t q_tok_stride, o_tok_stride;
+};
+
+typedef short pa8_short4_t __attribute__((ext_vector_type(4)));
+template <typename T>
+struct Pa8Vec4 {
+    typedef T type __attribute__((ext_vector_type(4)));
+};
+
+__device__ __forceinline__ float4_t pa8_mfma16x32(vec8_t<f16> a, vec8_t<f16> b, float4_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ float4_t pa8_mfma16x32(vec8_t<bf16> a, vec8_t<bf16> b, float4_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ float4_t pa8_mfma16x16(pa8_short4_t a, typename Pa8Vec4<f16>::type b, float4_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(typename Pa8Vec4<f16>::type, a), b, c, 0, 0, 0);
+}
+__device__ __forceinline__ float4_t pa8_mfma16x16(pa8_short4_t a, typename Pa8Vec4<bf16>::type b, float4_t c) {
+    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(pa8_short4_t, b), c, 0, 0, 0);
+}
+template <typename T>
+__device__ __forceinline__ pa8_short4_t pa8_lds_tr16_b64(const T *p) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((pa8_short4_t __attribute__((address_space(3))) *)(p));
+}
+__device__ __forceinline__ float pa8_rows_allreduce_max(float v) {
+    const auto r1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = fmaxf(__uint_as_float(r1[0]), __uint_as_float(r1[1]));
+    const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return fmaxf(__uint_as_float(r2[0]), __uint_as_float(r2[1]));
+}
+__device__ __forceinline__ float pa8_rows_allreduce_sum(float v) {
+    const auto r1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    v = __uint_as_float(r1[0]) + __uint_as_float(r1[1]);
+    const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+    return __uint_as_float(r2[0]) + __uint_as_float(r2[1]);
+}
+
+template <int D>
+struct Pa8Tile {
+    static constexpr int LPT = D / 16;                          // lanes per token row (16 codes each)
+    static constexpr int TPI = 64 / LPT < kBlk8 ? 64 / LPT : kBlk8;   // token rows per load instruction
+    static constexpr int NI = kBlk8 / TPI;                      // load instructions per 16-token block
+    static constexpr bool ALL = LPT * kBlk8 >= 64;              // every lane owns a chunk of the tile (D >= 64)
+    static constexpr int KRS = D + 8;    // K row pitch in the stage (elements of T), as MfmaTile of paged_attn.hip
+    static constexpr int VRS = D + 16;   // V row pitch
+    static constexpr int ELEMS = 16 * VRS;
+    static constexpr int QS = D / 32;    // QK^T MFMAs per block
+    static constexpr int OS = D / 16;    // PV MFMA pairs per block
+};
+
+// One 16-token block of one wave: codes -> stage -> attend_block_mfma's arithmetic (paged_attn.hip), unchanged.
+template <typename T, int D>
+__device__ __forceinline__ void attend_block_fp8(const vec8_t<T> (&qb)[Pa8Tile<D>::QS], const u32x4_t (&Kraw)[Pa8Tile<D>::NI],
+                                                 const u32x4_t (&Vraw)[Pa8Tile<D>::NI], float &m, float &l,
+                                                 float4_t (&acc)[Pa8Tile<D>::OS], T *stage, float c, int tok0, int row,
+                                                 int chunk, int lane, int len, bool partial) {
+    using Tile = Pa8Tile<D>;
+    constexpr int NI = Tile::NI;
+    const int q = lane >> 4, i16 = lane & 15;
+    u32x4_t Kc[NI], Vc[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        Kc[i] = Kraw[i];
+        Vc[i] = Vraw[i];
+    }
+    if (partial) {   // rows at or beyond the length: +0 instead of whatever the slot holds (NaN codes included)
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+            if (tok0 + i * Tile::TPI + row >= len) {
+                Kc[i] = u32x4_t{0u, 0u, 0u, 0u};
+                Vc[i] = u32x4_t{0u, 0u, 0u, 0u};
+            }
+    }
+    // the codes are converted HERE, one block at a time: tied to this point so that no pass widens a whole ring slot (or
+    // several) into 16-bit registers ahead of its turn
+#pragma unroll
+    for (int i = 0; i < NI; ++i) asm volatile("" : "+v"(Kc[i]));
+    const bool stager = Tile::ALL || row < kBlk8;
+    if (stager) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            vec8_t<T> lo, hi;
+            fp8x16_to_t<T>(Kc[i], lo, hi);
+            T *dst = stage + (i * Tile::TPI + row) * Tile::KRS + chunk * 16;
+            *reinterpret_cast<vec8_t<T> *>(dst) = lo;
+            *reinterpret_cast<vec8_t<T> *>(dst + 8) = hi;
+        }
+    }
+    float4_t s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < Tile::QS; ++j) {
+        const vec8_t<T> kf = *reinterpret_cast<const vec8_t<T> *>(stage + i16 * Tile::KRS + 32 * j + 8 * q);
+        s = pa8_mfma16x32(kf, qb[j], s);
+    }
+    mfma_results_ready<4>(s); // the scores are read by VALU next, behind a branch (swl_common.h)
+    // V goes into the same tile once the K fragments are out (same wave: LDS executes in order)
+#pragma unroll
+    for (int i = 0; i < NI; ++i) asm volatile("" : "+v"(Vc[i]));
+    if (stager) {
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            vec8_t<T> lo, hi;
+            fp8x16_to_t<T>(Vc[i], lo, hi);
+            T *dst = stage + (i * Tile::TPI + row) * Tile::VRS + chunk * 16;
+            *reinterpret_cast<vec8_t<T> *>(dst) = lo;
+            *reinterpret_cast<vec8_t<T> *>(dst + 8) = hi;
+        }
+    }
+    // s[r] = score of token tok0 + 4q + r for head i16
+    if (partial) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (tok0 + 4 * q + r >= len) s[r] = kNegBig;
+    }
+    float mb = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
+    mb = pa8_rows_allreduce_max(mb);
+    const float m_new = fmaxf(m, mb);
+    const float alpha = fast_exp2((m - m_new) * c); // difference first (see attend_block.h)
+    const float mc = m_new * c;
+    float pf[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pf[r] = fast_exp2(fmaf(s[r], c, -mc));
+    if (partial) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (tok0 + 4 * q + r >= len) pf[r] = 0.f;
+    }
+    l = fmaf(l, alpha, (pf[0] + pf[1]) + (pf[2] + pf[3]));
+    m = m_new;
+    typename Pa8Vec4<T>::type ph, pl;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        ph[r] = to_t<T>(pf[r]);
+        pl[r] = to_t<T>(pf[r] - to_f(ph[r]));
+    }
+    if (!__all(alpha == 1.0f)) {
+#pragma unroll
+        for (int mm = 0; mm < Tile::OS; ++mm) acc[mm] *= alpha;
+    }
+#pragma unroll
+    for (int mm = 0; mm < Tile::OS; ++mm) {
+        const pa8_short4_t vf = pa8_lds_tr16_b64(stage + (4 * q + (i16 >> 2)) * Tile::VRS + 16 * mm + 4 * (i16 & 3));
+        acc[mm] = pa8_mfma16x16(vf, ph, acc[mm]);
+        acc[mm] = pa8_mfma16x16(vf, pl, acc[mm]);
+    }
+}
+
+// NW = waves per workgroup (4 for short sequence blocks, 8 for long ones: launch_fp8_phase1). The block table, the
+// lengths and the sequence ids are __restrict__ kernel arguments so their reads stay scalar loads (paged_attn.hip).
+template <typename T, int D, int G, int NW>
+__global__ __launch_bounds__(NW * 64) void paged_attn_fp8_phase1_kernel(PagedAttnFp8Params p,
+                                                                        const int *__restrict__ block_table,
+                                                                        const int *__restrict__ seq_lens_r,
+                                                                        const int *__restrict__ seq_ids_r) {
+    using Tile = Pa8Tile<D>;
+    constexpr int NI = Tile::NI;
+    constexpr int NT = NW * 64;
+    constexpr int ND = kPa8Depth;
+    __shared__ float sm_ml[NW][G][2];
+    __shared__ float sm_acc[NW][G][D];
+    __shared__ __attribute__((aligned(16))) T sm_stage[NW][Tile::ELEMS];
+
+    const int split = blockIdx.x;
+    const int kvh = blockIdx.y;
+    const int seq = blockIdx.z;
+    const int len = seq_lens_r[seq];
+    const int tok_begin = split * p.seq_block_size;
+    if (tok_begin >= len) return; // uniform for the workgroup, before any barrier
+    const int tok_end = min(len, tok_begin + p.seq_block_size);
+    const int blk_end = (tok_end + kBlk8 - 1) / kBlk8;
+    const int seq_id = seq_ids_r[seq];
+    const int *__restrict__ bt = block_table + static_cast<int64_t>(seq_id) * p.max_blocks_per_seq;
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int chunk = lane % Tile::LPT;
+    const int row = lane / Tile::LPT;
+    const float k_scale = p.kv_scales[static_cast<int64_t>(p.layer) * p.KVH + kvh];
+    const float v_scale = p.kv_scales[(static_cast<int64_t>(p.L) + p.layer) * p.KVH + kvh];
+    const float c = p.scale_log2e * k_scale;
+
+    const int64_t tile_bytes = static_cast<int64_t>(kBlk8) * D;
+    const int64_t layer_head = static_cast<int64_t>(p.layer) * p.KVH + kvh;
+    const int64_t blk_pitch = static_cast<int64_t>(p.L) * p.KVH;
+    // D = 32: a tile is 512 bytes, lanes 32..63 read it a second time (in bounds) and never stage it
+    const int lane_off = (Tile::ALL ? lane : (lane & 31)) * 16;
+
+    vec8_t<T> qb[Tile::QS];               // Q^T B fragments, lane (q, h) -> Q[head h][32 j + 8 q ..], zero for h >= G
+    const int mq = lane >> 4, mh = lane & 15;
+    {
+        const T *qp = static_cast<const T *>(p.q) + seq * p.q_tok_stride +
+                      (static_cast<int64_t>(kvh) * G + min(mh, G - 1)) * D + 8 * mq;
+#pragma unroll
+        for (int j = 0; j < Tile::QS; ++j) {
+            qb[j] = load8(qp + 32 * j);
+            if (mh >= G) qb[j] = vec8_t<T>{};
+        }
+    }
+
+    float m = kNegBig, l = 0.f;
+    float4_t acc4[Tile::OS];              // O^T[d = 16 mm + 4 q + r][head h]
+#pragma unroll
+    for (int mm = 0; mm < Tile::OS; ++mm) acc4[mm] = float4_t{0.f, 0.f, 0.f, 0.f};
+
+    u32x4_t Kr[ND][NI], Vr[ND][NI];
+    auto load_phys = [&](int64_t phys, u32x4_t(&Kd)[NI], u32x4_t(&Vd)[NI]) {
+        const int64_t base = (phys * blk_pitch + layer_head) * tile_bytes + lane_off;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            Kd[i] = load16b_nt(p.k_cache + base + i * 1024);
+            Vd[i] = load16b_nt(p.v_cache + base + i * 1024);
+        }
+    };
+    auto load_block = [&](int b, u32x4_t(&Kd)[NI], u32x4_t(&Vd)[NI]) {
+        load_phys(bt[b], Kd, Vd); // scalar load: b is wave-uniform
+    };
+    auto attend = [&](int b, u32x4_t(&Kd)[NI], u32x4_t(&Vd)[NI]) {
+        const int tok0 = b * kBlk8;
+        attend_block_fp8<T, D>(qb, Kd, Vd, m, l, acc4, &sm_stage[wave][0], c, tok0, row, chunk, lane, len,
+                               tok0 + kBlk8 > len);
+    };
+
+    int b = tok_begin / kBlk8 + wave;
+    // the first ND blocks of this wave go into slots 0..ND-1
+#pragma unroll
+    for (int d = 0; d < ND; ++d)
+        if (b + d * NW < blk_end) load_block(b + d * NW, Kr[d], Vr[d]);
+
+    // steady state: every refill is unconditional, so the waits between slots are exact counted vmcnt waits; slot d
+    // attends block b + d*NW and is refilled with block b + (d+ND)*NW (the loop of paged_attn.hip, its fences included)
+    if (b + (2 * ND - 1) * NW < blk_end) {
+        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): the pipeline fill, hands the loop an exact state
+        do {
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                const int64_t phys_next = bt[b + (d + ND) * NW];
+                __builtin_amdgcn_sched_barrier(0);
+                attend(b + d * NW, Kr[d], Vr[d]);
+                __builtin_amdgcn_sched_barrier(0);
+                load_phys(phys_next, Kr[d], Vr[d]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            b += ND * NW;
+        } while (b + (2 * ND - 1) * NW < blk_end);
+    }
+    // drain: at most 2*ND-1 blocks left, the first ND of them already in their slots
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        if (b + d * NW < blk_end) {
+            attend(b + d * NW, Kr[d], Vr[d]);
+            __builtin_amdgcn_sched_barrier(0);
+            if (b + (d + ND) * NW < blk_end) load_block(b + (d + ND) * NW, Kr[d], Vr[d]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < ND - 1; ++d)
+        if (b + (d + ND) * NW < blk_end) {
+            attend(b + (d + ND) * NW, Kr[d], Vr[d]);
+            __builtin_amdgcn_sched_barrier(0);   // one block's converted fragments live at a time
+        }
+
+    // O^T of the last block is stored by DS instructions below (swl_common.h)
+#pragma unroll
+    for (int mm = 0; mm < Tile::OS; ++mm) mfma_results_tie(acc4[mm]);
+    mfma_results_ready<4>(acc4[Tile::OS - 1]);
+    // the four lanes (q = 0..3) of a head share m and each hold the row sum of their own tokens; O^T is complete
+    const float lt = pa8_rows_allreduce_sum(l);
+    if (mh < G) {
+        if (mq == 0) {
+            sm_ml[wave][mh][0] = m;
+            sm_ml[wave][mh][1] = lt;
+        }
+#pragma unroll
+        for (int mm = 0; mm < Tile::OS; ++mm)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) sm_acc[wave][mh][16 * mm + 4 * mq + r] = acc4[mm][r];
+    }
+    __syncthreads();
+
+    // ---- merge the NW waves and write the partial (or the final output when there is one split) -
+    const int nsb = p.num_seq_blocks;
+    for (int oidx = threadIdx.x; oidx < G * D; oidx += NT) {
+        const int g = oidx / D;
+        const int d = oidx % D;
+        float M = sm_ml[0][g][0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) M = fmaxf(M, sm_ml[w][g][0]);
+        float Lsum = 0.f, A = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float wgt = fast_exp2((sm_ml[w][g][0] - M) * c);
+            Lsum = fmaf(sm_ml[w][g][1], wgt, Lsum);
+            A = fmaf(sm_acc[w][g][d], wgt, A);
+        }
+        const float out = (A / Lsum) * v_scale;
+        const int head = kvh * G + g;
+        if (nsb == 1) {
+            static_cast<T *>(p.o_direct)[seq * p.o_tok_stride + static_cast<int64_t>(head) * D + d] = to_t<T>(out);
+        } else {
+            const int64_t part = (static_cast<int64_t>(seq) * p.H + head) * nsb + split;
+            p.mid_o[part * D + d] = out;
+            if (d == 0) p.mid_lse[part] = fast_log2(Lsum) + M * c;
+        }
+    }
+}
+
+template <typename T, int D, int G>
+static int launch_fp8_phase1(const PagedAttnFp8Params &p, const int *bt, const int *lens, const int *ids, int Bd,
+                             hipStream_t stream) {
+    const dim3 grid(p.num_seq_blocks, p.KVH, Bd);
+    // >= 32 KV blocks per sequence block: 8-wave workgroups (>= 4 blocks per wave); else 4 waves (paged_attn.hip)
+    if (p.seq_block_size >= 32 * kBlk8)
+        hipLaunchKernelGGL((paged_attn_fp8_phase1_kernel<T, D, G, 8>), grid, dim3(512), 0, stream, p, bt, lens, ids);
+    else
+        hipLaunchKernelGGL((paged_attn_fp8_phase1_kernel<T, D, G, 4>), grid, dim3(256), 0, stream, p, bt, lens, ids);
+    return check_launch();
+}
+
+template <typename T, int D>
+static int dispatch_fp8_g(const PagedAttnFp8Params &p, const int *bt, const int *lens, const int *ids, int Bd, int G,
+                          hipStream_t stream) {
+    switch (G) {
+    case 1: return launch_fp8_phase1<T, D, 1>(p, bt, lens, ids, Bd, stream);
+    case 2: return launch_fp8_phase1<T, D, 2>(p, bt, lens, ids, Bd, stream);
+    case 4: return launch_fp8_phase1<T, D, 4>(p, bt, lens, ids, Bd, stream);
+    case 8: return launch_fp8_phase1<T, D, 8>(p, bt, lens, ids, Bd, stream);
+    default: return SWL_ERR_UNSUPPORTED;
+    }
+}
+
+} // namespace swl
+
+extern "C" int swl_paged_attn_phase1_fp8(void *o_direct, const void *q, const void *k_cache, const void *v_cache,
+                                         const float *kv_scales, const int32_t *block_table, const int32_t *seq_ids,
+                                         const int32_t *seq_lens, float *mid_o, float *mid_lse, float softmax_scale,
+                                         int32_t num_decoding_seqs, int32_t num_q_heads, int32_t num_kv_heads,
+                                         int32_t head_dim, int32_t num_layers, int32_t block_size, int32_t cur_layer,
+                                         int32_t max_blocks_per_seq, int32_t seq_block_size, int32_t num_seq_blocks,
+                                         int64_t q_tok_stride, int64_t o_tok_stride, int32_t dtype, swl_stream_t stream) {
+    if (num_decoding_seqs < 0) return SWL_ERR_BAD_ARG;
+    if (num_decoding_seqs == 0 || num_seq_blocks == 0) return SWL_OK;
+    if (!q || !k_cache || !v_cache || !kv_scales || !block_table || !seq_ids || !seq_lens) return SWL_ERR_BAD_ARG;
+    if (num_seq_blocks < 0 || num_q_heads <= 0 || num_kv_heads <= 0 || num_q_heads % num_kv_heads != 0 ||
+        num_layers <= 0 || cur_layer < 0 || cur_layer >= num_layers || max_blocks_per_seq <= 0)
+        return SWL_ERR_BAD_ARG;
+    if (!(head_dim == 32 || head_dim == 64 || head_dim == 128)) return SWL_ERR_BAD_ARG;
+    if (!(dtype == SWL_F16 || dtype == SWL_BF16)) return SWL_ERR_BAD_ARG;
+    if (block_size != swl::kBlk8) return SWL_ERR_UNSUPPORTED;
+    if (seq_block_size <= 0 || seq_block_size % block_size != 0) return SWL_ERR_BAD_ARG;
+    if (num_seq_blocks == 1 ? !o_direct : (!mid_o || !mid_lse)) return SWL_ERR_BAD_ARG;
+    if (!swl::aligned16(q) || !swl::aligned16(k_cache) || !swl::aligned16(v_cache) || (q_tok_stride & 7))
+        return SWL_ERR_BAD_ARG;
+    if (num_decoding_seqs > 65535 || num_kv_heads > 65535) return SWL_ERR_UNSUPPORTED;
+    swl::PagedAttnFp8Params p{};
+    p.o_direct = o_direct;
+    p.q = q;
+    p.k_cache = static_cast<const uint8_t *>(k_cache);
+    p.v_cache = static_cast<const uint8_t *>(v_cache);
+    p.kv_scales = kv_scales;
+    p.mid_o = mid_o;
+    p.mid_lse = mid_lse;
+    p.scale_log2e = softmax_scale * 1.44269504088896340736f;
+    p.H = num_q_heads;
+    p.KVH = num_kv_heads;
+    p.L = num_layers;
+    p.layer = cur_layer;
+    p.max_blocks_per_seq = max_blocks_per_seq;
+    p.seq_block_size = seq_block_size;
+    p.num_seq_blocks = num_seq_blocks;
+    p.q_tok_stride = q_tok_stride;
+    p.o_tok_stride = o_tok_stride;
+    const int G = num_q_heads / num_kv_heads;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    SWL_DISPATCH_DTYPE(dtype, T, {
+        switch (head_dim) {
+        case 32: return swl::dispatch_fp8_g<T, 32>(p, block_table, seq_lens, seq_ids, num_decoding_seqs, G, s);
+        case 64: return swl::dispatch_fp8_g<T, 64>(p, block_table, seq_lens, seq_ids, num_decoding_seqs, G, s);
+        default: return swl::dispatch_fp8_g<T, 128>(p, block_table, seq_lens, seq_ids, num_decoding_seqs, G, s);
+        }
+    });
+}
+
+extern "C" int swl_paged_attn_decode_fp8(void *o, const void *q, const void *k_cache, const void *v_cache,
+                                         const float *kv_scales, const int32_t *block_table, const int32_t *seq_ids,
+                                         const int32_t *seq_lens, void *scratch, float softmax_scale,
+                                         int32_t num_decoding_seqs, int32_t num_q_heads, int32_t num_kv_heads,
+                                         int32_t head_dim, int32_t num_layers, int32_t block_size, int32_t cur_layer,
+                                         int32_t max_blocks_per_seq, int32_t seq_block_size, int32_t num_seq_blocks,
+                                         int64_t q_tok_stride, int64_t o_tok_stride, int32_t dtype, swl_stream_t stream) {
+    if (num_decoding_seqs < 0) return SWL_ERR_BAD_ARG;
+    if (num_decoding_seqs == 0 || num_seq_blocks == 0) return SWL_OK;
+    if (!o) return SWL_ERR_BAD_ARG;
+    float *mid_o = nullptr, *mid_lse = nullptr;
+    if (num_seq_blocks > 1) {
+        if (!scratch || !swl::aligned16(scratch)) return SWL_ERR_BAD_ARG;
+        if (num_q_heads <= 0 || head_dim <= 0) return SWL_ERR_BAD_ARG;
+        mid_o = static_cast<float *>(scratch);
+        mid_lse = mid_o + static_cast<size_t>(num_decoding_seqs) * num_q_heads * num_seq_blocks * head_dim;
+    }
+    const int rc = swl_paged_attn_phase1_fp8(o, q, k_cache, v_cache, kv_scales, block_table, seq_ids, seq_lens, mid_o,
+                                             mid_lse, softmax_scale, num_decoding_seqs, num_q_heads, num_kv_heads,
+                                             head_dim, num_layers, block_size, cur_layer, max_blocks_per_seq,
+                                             seq_block_size, num_seq_blocks, q_tok_stride, o_tok_stride, dtype, stream);
+    if (rc != SWL_OK || num_seq_blocks == 1) return rc;
+    return swl_paged_attn_phase2(o, mid_o, mid_lse, seq_lens, num_decoding_seqs, num_q_heads, head_dim, seq_block_size,
+                                 num_seq_blocks, o_tok_stride, dtype, stream);
+}

@@ -59,6 +59,12 @@ class EngineConfig:
     # running decodes ride along with every chunk step when the scheduler piggybacks, and a prompt longer than
     # max_tokens_in_batch becomes servable. 0 (default): off — a prompt is one forward, as in the reference.
     max_prefill_chunk: int = 0
+    # Element type of the paged KV pools (GPU and host swap). "auto": the activation dtype — nothing changes. "fp8_e4m3":
+    # OCP e4m3fn, one byte per element with one fp32 k_scale / v_scale per (layer, kv-head) (LlamaModel.set_kv_scales;
+    # default 1): the pool holds twice the tokens and decode attention streams half the bytes (csrc/paged_attn_fp8.hip).
+    # The layer then runs qkv projection -> rotary -> quantising store -> FP8 paged attention: the slab-fed attention
+    # prologue and the paths that hang on it are 16-bit only.
+    kv_cache_dtype: str = "auto"
 
     # Internal switches (all on): set through `tuning`, read by the layer code as plain attributes.
     TUNING_DEFAULTS = dict(
@@ -97,6 +103,7 @@ class EngineConfig:
     # Tokens per KV block the HIP kernels are built for (csrc/paged_attn.hip kBlk, kvcache.hip): one 16-token block
     # of a 128-wide head is 4 KiB = one wave-wide 16 B/lane load x 4.
     SUPPORTED_BLOCK_SIZE = 16
+    KV_CACHE_DTYPES = ("auto", "fp8_e4m3")
 
     def __post_init__(self):
         # The reference takes block_size as a Triton constexpr (paged_attn.py:27) and its CLI default is 16
@@ -110,11 +117,16 @@ class EngineConfig:
             raise ValueError(f"dtype must be 'float16' or 'bfloat16', got {self.dtype!r}")
         if int(self.max_prefill_chunk) < 0:
             raise ValueError(f"max_prefill_chunk must be >= 0 (0 = off), got {self.max_prefill_chunk}")
+        if self.kv_cache_dtype not in self.KV_CACHE_DTYPES:
+            raise ValueError(f"kv_cache_dtype must be one of {list(self.KV_CACHE_DTYPES)}, got {self.kv_cache_dtype!r}")
         unknown = set(self.tuning or ()) - set(self.TUNING_DEFAULTS)
         if unknown:
             raise ValueError(f"unknown tuning switches {sorted(unknown)}; known: {sorted(self.TUNING_DEFAULTS)}")
         for name, default in self.TUNING_DEFAULTS.items():
             setattr(self, name, bool((self.tuning or {}).get(name, default)))
+        if self.kv_cache_dtype == "fp8_e4m3" and self.decode_engine:
+            raise ValueError("kv_cache_dtype='fp8_e4m3' cannot be combined with tuning={'decode_engine': True}: the "
+                             "persistent one-sequence decode step reads and writes 16-bit KV pools only")
 
     @staticmethod
     def add_cli_args(parser: argparse.ArgumentParser):
@@ -143,5 +155,7 @@ class EngineConfig:
                        help="(default) replay captured hipGraphs for pure-decode steps")
         g.add_argument("--no-hip-graph", dest="use_hip_graph", action="store_false")
         g.add_argument("--no-skinny-gemm", dest="use_skinny_gemm", action="store_false")
+        g.add_argument("--kv-cache-dtype", type=str, default="auto", choices=list(EngineConfig.KV_CACHE_DTYPES),
+                       help="Element type of the KV pools: auto = the activation dtype, fp8_e4m3 = 1 byte per element")
         g.add_argument("--max-prefill-chunk", type=int, default=0,
                        help="Chunked prefill: prompt tokens per forward, at most (0 = off: a prompt is one forward)")

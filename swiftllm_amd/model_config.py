@@ -31,7 +31,8 @@ class LlamaModelConfig:
         self.rope_scaling = 1.0 if scaling is None else scaling
 
     def get_kvslot_size(self, dtype: torch.dtype = torch.float16) -> int:
-        """Bytes of KV cache one token occupies (K and V, all layers)."""
+        """Bytes of KV cache one token occupies (K and V, all layers); `dtype` is the POOL's element type (1 byte for
+        torch.float8_e4m3fn)."""
         return 2 * self.num_layers * self.num_kv_heads * self.head_dim * dtype.itemsize
 
     @staticmethod

@@ -116,7 +116,12 @@ def main():
     ap.add_argument("--num-replicas", type=int, default=8)
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8000)
+    # checked here, before eight replicas load their weights, and handed on to every one of them
+    ap.add_argument("--kv-cache-dtype", default=None, choices=["auto", "fp8_e4m3"],
+                    help="element type of every replica's KV pools (api_server --kv-cache-dtype)")
     args, passthrough = ap.parse_known_args()
+    if args.kv_cache_dtype is not None:
+        passthrough = list(passthrough) + ["--kv-cache-dtype", args.kv_cache_dtype]
     procs = spawn_replicas(args.num_replicas, args.port, passthrough)
     router = ReplicaRouter([f"http://127.0.0.1:{args.port + 1 + i}" for i in range(args.num_replicas)])
     try:

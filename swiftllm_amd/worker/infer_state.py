@@ -53,3 +53,7 @@ class LlamaInferState:
     # None: every prompt starts at position 0 and attends to its fresh projections — the reference's prefill.
     prefill_ctx_lens: Optional[torch.Tensor] = None
     max_prefill_total_len: int = 0      # max over prefill sequences of ctx + len (only read when prefill_ctx_lens is set)
+    # FP8 KV pools (EngineConfig.kv_cache_dtype = "fp8_e4m3"): fp32 [2, L, KVH] k/v scales and their host-computed
+    # reciprocals (what the quantising stores multiply by). None with 16-bit pools.
+    kv_scales: Optional[torch.Tensor] = None
+    kv_inv_scales: Optional[torch.Tensor] = None

@@ -22,7 +22,14 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
         return
     assert k_cache.is_contiguous() and v_cache.is_contiguous() and block_table.is_contiguous()
     assert infer_state.seq_block_size % engine_config.block_size == 0
-    assert q.dtype == k_cache.dtype == v_cache.dtype == o.dtype
+    fp8 = k_cache.dtype == torch.float8_e4m3fn
+    if fp8:
+        scales = infer_state.kv_scales
+        assert q.dtype == o.dtype and v_cache.dtype == torch.float8_e4m3fn
+        assert scales is not None and scales.dtype == torch.float32 and scales.is_contiguous()
+        assert scales.shape == (2, model_config.num_layers, model_config.num_kv_heads)
+    else:
+        assert q.dtype == k_cache.dtype == v_cache.dtype == o.dtype
     if o.dim() == 2:
         o = o.view(o.shape[0], model_config.num_q_heads, model_config.head_dim)
     nsb = infer_state.num_seq_blocks
@@ -32,6 +39,15 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
         scratch = getattr(infer_state, "paged_attn_scratch", None)
         if scratch is None or scratch.numel() * scratch.element_size() < need:
             scratch = torch.empty(need // 4, dtype=torch.float32, device=q.device)
+    if fp8:     # csrc/paged_attn_fp8.hip: phase 1 over the 1-byte pools, the same phase 2 and scratch
+        _hip.call("swl_paged_attn_decode_fp8", _hip.ptr(o), _hip.ptr(q), _hip.ptr(k_cache), _hip.ptr(v_cache),
+                  _hip.ptr(scales), _hip.ptr(block_table), _hip.ptr(infer_state.seq_ids[infer_state.num_prefill_seqs:]),
+                  _hip.ptr(infer_state.decoding_seq_lens), _hip.ptr(scratch), infer_state.softmax_scale,
+                  nd, model_config.num_q_heads, model_config.num_kv_heads, model_config.head_dim,
+                  model_config.num_layers, engine_config.block_size, cur_layer, block_table.shape[1],
+                  infer_state.seq_block_size, nsb, token_stride(q, "q"), token_stride(o, "o"),
+                  _hip.dtype_code(q.dtype), _hip.stream())
+        return
     _hip.call("swl_paged_attn_decode", _hip.ptr(o), _hip.ptr(q), _hip.ptr(k_cache),
               _hip.ptr(v_cache), _hip.ptr(block_table),
               _hip.ptr(infer_state.seq_ids[infer_state.num_prefill_seqs:]),

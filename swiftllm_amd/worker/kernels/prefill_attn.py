@@ -43,9 +43,21 @@ def prefill_attention_paged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
     assert cu.dtype == torch.int32 and cu.is_contiguous() and cu.numel() == st.num_prefill_seqs + 1
     assert ctx is not None and ctx.dtype == torch.int32 and ctx.is_contiguous() and ctx.numel() == st.num_prefill_seqs
     assert k_cache.is_contiguous() and v_cache.is_contiguous() and block_table.is_contiguous()
-    assert q.dtype == o.dtype == k_cache.dtype == v_cache.dtype
     if o.dim() == 2:
         o = o.view(o.shape[0], model_config.num_q_heads, model_config.head_dim)
+    if k_cache.dtype == torch.float8_e4m3fn:    # csrc/prefill_attn_paged_fp8.hip: the chunk's own keys come back quantised
+        scales = st.kv_scales
+        assert q.dtype == o.dtype and v_cache.dtype == torch.float8_e4m3fn
+        assert scales is not None and scales.dtype == torch.float32 and scales.is_contiguous()
+        assert scales.shape == (2, model_config.num_layers, model_config.num_kv_heads)
+        _hip.call("swl_prefill_attn_paged_fp8", _hip.ptr(o), _hip.ptr(q), _hip.ptr(k_cache), _hip.ptr(v_cache),
+                  _hip.ptr(scales), _hip.ptr(block_table), _hip.ptr(st.seq_ids), _hip.ptr(cu), _hip.ptr(ctx),
+                  st.num_prefill_seqs, st.max_prefill_len, st.max_prefill_total_len, model_config.num_q_heads,
+                  model_config.num_kv_heads, model_config.head_dim, model_config.num_layers, engine_config.block_size,
+                  cur_layer, block_table.shape[1], st.softmax_scale, token_stride(q, "q"), token_stride(o, "o"),
+                  _hip.dtype_code(q.dtype), _hip.stream())
+        return
+    assert q.dtype == o.dtype == k_cache.dtype == v_cache.dtype
     _hip.call("swl_prefill_attn_paged", _hip.ptr(o), _hip.ptr(q), _hip.ptr(k_cache), _hip.ptr(v_cache),
               _hip.ptr(block_table), _hip.ptr(st.seq_ids), _hip.ptr(cu), _hip.ptr(ctx), st.num_prefill_seqs,
               st.max_prefill_len, st.max_prefill_total_len, model_config.num_q_heads, model_config.num_kv_heads,

@@ -71,6 +71,9 @@ class LlamaTransformerLayer:
         self.decoding_piggyback_stream = decoding_piggyback_stream
         self.layer_id = layer_id
         self.skinny = bool(getattr(engine_config, "use_skinny_gemm", False))
+        # FP8 KV pools: qkv projection -> rotary -> quantising store -> FP8 attention; every fused rotary + store form and
+        # the slab-fed attention prologue (with the deferred / exact norm on the fly and the tiny path that hang on it) are off
+        self.kv_fp8 = getattr(engine_config, "kv_cache_dtype", "auto") == "fp8_e4m3"
         self._qkv_splits = None     # k-splits the skinny GEMM picks for the fused qkv projection (cached)
         self._qkv_even = None       # ... and whether they are even splits of whole 128-column tiles (the exact norm on the fly)
         self._tiny_ok = None        # can this layer run the tiny-batch (<= TINY_POLICY_M sequences) path (cached)
@@ -116,6 +119,8 @@ class LlamaTransformerLayer:
     def _slab_fed_attention_applies(self, st) -> bool:
         """Pure-decode batch on the path `fused qkv slabs -> (rotary + KV store + paged attention)` in one launch."""
         cfg, ecfg, w = self.model_config, self.engine_config, self.weight
+        if self.kv_fp8:     # the slab-fed prologue stores and attends 16-bit pools only
+            return False
         return (self.skinny and st.num_prefill_seqs == 0 and 0 < st.num_decoding_seqs <= 256 and not st.ignore_kvcache
                 and st.position_indices is not None and getattr(ecfg, "fuse_rope_kvstore", False)
                 and getattr(ecfg, "fuse_splitk_consumers", True) and w.qkv_proj is not None
@@ -231,7 +236,7 @@ class LlamaTransformerLayer:
 
         pure_decode = st.num_prefill_seqs == 0 and st.num_decoding_seqs > 0
         fused_rope_store = (pure_decode and not st.ignore_kvcache and st.position_indices is not None
-                            and getattr(ecfg, "fuse_rope_kvstore", False))
+                            and getattr(ecfg, "fuse_rope_kvstore", False) and not self.kv_fp8)
         fast = self.skinny and pure_decode and getattr(ecfg, "fuse_splitk_consumers", True)
         qkv = None
         if (fast and fused_rope_store and w.qkv_proj is not None and getattr(ecfg, "fuse_rope_into_attention", True)
@@ -259,7 +264,7 @@ class LlamaTransformerLayer:
                 rotary_embedding_and_store_kvcache_decode(q, k, v, k_cache, v_cache, block_table, cfg,
                                                           ecfg, st, self.layer_id)
             elif (st.num_prefill_seqs > 0 and not st.ignore_kvcache and st.position_indices is not None
-                  and getattr(ecfg, "fuse_rope_kvstore", False)):
+                  and getattr(ecfg, "fuse_rope_kvstore", False) and not self.kv_fp8):
                 # prompt tokens: rotary + KV store in one pass over k (r05); riding decodes: their fused launch
                 rotary_embedding_and_store_kvcache_prefill(q, k, v, k_cache, v_cache, block_table, cfg, ecfg, st,
                                                            self.layer_id)

@@ -76,6 +76,11 @@ class LlamaModel:
         self.model_config = LlamaModelConfig.load_from_model_path(engine_config.model_path)
         self.dtype = _DTYPES[getattr(engine_config, "dtype", "float16")]
         self.device = torch.device("cuda")
+        # element type of the KV pools: the activation dtype, or e4m3fn (EngineConfig.kv_cache_dtype = "fp8_e4m3")
+        self.kv_fp8 = getattr(engine_config, "kv_cache_dtype", "auto") == "fp8_e4m3"
+        self.kv_dtype = torch.float8_e4m3fn if self.kv_fp8 else self.dtype
+        # FP8 pools: fp32 [2, L, KVH] k/v scales (default 1) and, next to them, their reciprocals computed on the host
+        self.kv_scales = self.kv_inv_scales = None
 
         self.weight = None
         self._cos_cached = self._sin_cached = None
@@ -137,6 +142,10 @@ class LlamaModel:
         ]
         self.post_layer = LlamaPostLayer(self.model_config, self.weight)
         self.post_layer.skinny = bool(getattr(self.engine_config, "use_skinny_gemm", False))
+        if self.kv_fp8 and self.kv_scales is None:
+            cfg = self.model_config
+            self.kv_scales = torch.ones((2, cfg.num_layers, cfg.num_kv_heads), dtype=torch.float32, device=self.device)
+            self.kv_inv_scales = torch.ones_like(self.kv_scales)
         # (allocated before profile_num_blocks measures: the largest replay bucket's rows)
         ecfg = self.engine_config
         self._ensure_sampling_rows(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
@@ -221,7 +230,7 @@ class LlamaModel:
             raise RuntimeError(
                 f"Peak memory {peak_memory / GB:.2f} GB exceeds usable memory {usable / GB:.2f} GB "
                 f"({total_memory / GB:.2f} GB * {ecfg.gpu_mem_utilization})")
-        block_bytes = ecfg.block_size * self.model_config.get_kvslot_size(self.dtype)
+        block_bytes = ecfg.block_size * self.model_config.get_kvslot_size(self.kv_dtype)
         # the two block tables (GPU + CPU manager) are allocated after this point: budget them
         table_bytes = 2 * ecfg.max_seqs_in_block_table * ecfg.max_blocks_per_seq * 4
         # ... and so is the private memory pool of the decode hipGraphs (captured on first use, AFTER the KV pool took
@@ -232,9 +241,16 @@ class LlamaModel:
             graph_bytes = self._measure_decode_graph_bytes()
             free_memory, _ = torch.cuda.mem_get_info()      # (the measurement may have grown the regular pool as well)
             peak_memory = max(peak_memory, total_memory - free_memory)
-        num_blocks = math.floor((usable - peak_memory - table_bytes - graph_bytes) / block_bytes)
+        num_blocks = self.blocks_that_fit(usable - peak_memory - table_bytes - graph_bytes, block_bytes)
         torch.cuda.empty_cache()
-        return max(num_blocks, 0)
+        return num_blocks
+
+    @staticmethod
+    def blocks_that_fit(pool_bytes: float, block_bytes: int) -> int:
+        """KV blocks a budget of `pool_bytes` holds; `block_bytes` = block_size * get_kvslot_size(pool dtype), so an FP8
+        pool gets the count a 16-bit pool would get with half the block bytes. The block tables and the hipGraph reserve
+        were taken off the budget before: they do not shrink with the pool's element size."""
+        return max(math.floor(pool_bytes / block_bytes), 0)
 
     def _measure_decode_graph_bytes(self) -> int:
         """What the private memory pool of the decode hipGraphs will hold: MEASURED (r03-r04 used a formula) as
@@ -251,8 +267,8 @@ class LlamaModel:
         saved = (self.k_cache, self.v_cache, self.gpu_block_manager, self.cpu_block_manager, ecfg.use_hip_graph)
         try:
             shape = (b, cfg.num_layers, cfg.num_kv_heads, ecfg.block_size, cfg.head_dim)
-            self.k_cache = torch.zeros(shape, dtype=self.dtype, device=self.device)
-            self.v_cache = torch.zeros(shape, dtype=self.dtype, device=self.device)
+            self.k_cache = torch.zeros(shape, dtype=self.kv_dtype, device=self.device)
+            self.v_cache = torch.zeros(shape, dtype=self.kv_dtype, device=self.device)
             self.gpu_block_manager = BlockManager("GPU", b, ecfg.max_seqs_in_block_table, ecfg.max_blocks_per_seq,
                                                   ecfg.block_size, self.device)
             ecfg.use_hip_graph = False
@@ -290,16 +306,16 @@ class LlamaModel:
         self.num_blocks = num_blocks
         shape = (num_blocks, cfg.num_layers, cfg.num_kv_heads, ecfg.block_size, cfg.head_dim)
         # zeros, not empty: stale NaNs in never-written slots would poison 0 * NaN products
-        self.k_cache = torch.zeros(shape, dtype=self.dtype, device=self.device)
-        self.v_cache = torch.zeros(shape, dtype=self.dtype, device=self.device)
+        self.k_cache = torch.zeros(shape, dtype=self.kv_dtype, device=self.device)
+        self.v_cache = torch.zeros(shape, dtype=self.kv_dtype, device=self.device)
         swap_shape = (ecfg.num_cpu_blocks,) + shape[1:]
         pin = getattr(ecfg, "pin_swap_memory", True) and ecfg.num_cpu_blocks > 0
         try:
-            self.k_swap = torch.zeros(swap_shape, dtype=self.dtype, device="cpu", pin_memory=pin)
-            self.v_swap = torch.zeros(swap_shape, dtype=self.dtype, device="cpu", pin_memory=pin)
+            self.k_swap = torch.zeros(swap_shape, dtype=self.kv_dtype, device="cpu", pin_memory=pin)
+            self.v_swap = torch.zeros(swap_shape, dtype=self.kv_dtype, device="cpu", pin_memory=pin)
         except RuntimeError:    # host cannot pin that much: pageable pools, as the reference has
-            self.k_swap = torch.zeros(swap_shape, dtype=self.dtype, device="cpu")
-            self.v_swap = torch.zeros(swap_shape, dtype=self.dtype, device="cpu")
+            self.k_swap = torch.zeros(swap_shape, dtype=self.kv_dtype, device="cpu")
+            self.v_swap = torch.zeros(swap_shape, dtype=self.kv_dtype, device="cpu")
         self.gpu_block_manager = BlockManager("GPU", num_blocks, ecfg.max_seqs_in_block_table,
                                               ecfg.max_blocks_per_seq, ecfg.block_size, self.device)
         self.cpu_block_manager = BlockManager("CPU", ecfg.num_cpu_blocks,
@@ -307,6 +323,33 @@ class LlamaModel:
                                               ecfg.block_size, self.device)
         self._drop_decode_graphs()
         self._lookahead = None
+
+    @torch.inference_mode()
+    def set_kv_scales(self, k_scale: torch.Tensor, v_scale: torch.Tensor):
+        """FP8 KV pools: one fp32 scale per (layer, kv-head) for K and for V, tensors of shape [L, KVH] (positive, finite).
+        A stored code means code * scale, so the scales may only change while no sequence holds blocks: raises otherwise.
+        The reciprocals the quantising stores multiply by are fp32(1 / scale), computed here on the host. The tensors are
+        updated in place (captured decode graphs read them by address)."""
+        if not self.kv_fp8:
+            raise RuntimeError("set_kv_scales needs kv_cache_dtype='fp8_e4m3' (16-bit KV pools have no scales)")
+        if self.kv_scales is None:
+            raise RuntimeError("set_kv_scales before load_weights")
+        cfg = self.model_config
+        want = (cfg.num_layers, cfg.num_kv_heads)
+        ks = torch.as_tensor(k_scale, dtype=torch.float32, device="cpu")
+        vs = torch.as_tensor(v_scale, dtype=torch.float32, device="cpu")
+        if tuple(ks.shape) != want or tuple(vs.shape) != want:
+            raise ValueError(f"k_scale and v_scale must have shape {want}, got {tuple(ks.shape)} and {tuple(vs.shape)}")
+        both = torch.stack([ks, vs])
+        if not bool((torch.isfinite(both) & (both > 0)).all()):
+            raise ValueError("KV scales must be positive and finite")
+        for mgr in (self.gpu_block_manager, self.cpu_block_manager):
+            if mgr is not None and mgr.host.num_free_blocks < mgr.host.num_blocks:
+                raise RuntimeError("set_kv_scales while sequences hold KV blocks: their stored codes were quantised with "
+                                   "the old scales (free or finish them first)")
+        self._lookahead = None
+        self.kv_scales.copy_(both)
+        self.kv_inv_scales.copy_(1.0 / both)        # fp32 division on the host, one rounding
 
     def _init_to_get_rotary(self):
         """cos/sin tables [positions, head_dim/2] in the model dtype. Formulas (including the
@@ -395,7 +438,8 @@ class LlamaModel:
             position_indices=dev["position_indices"], last_token_indices=dev["last_token_indices"],
             paged_attn_scratch=self._scratch if nsb > 1 else None,
             sampling=device_args(self._sample_dev, dev["seq_lengths"]) if sampled else None,
-            prefill_ctx_lens=dev.get("prefill_ctx_lens"), max_prefill_total_len=plan.max_prefill_total_len)
+            prefill_ctx_lens=dev.get("prefill_ctx_lens"), max_prefill_total_len=plan.max_prefill_total_len,
+            kv_scales=self.kv_scales, kv_inv_scales=self.kv_inv_scales)
 
     @torch.inference_mode()
     def _forward(self, input_ids: torch.Tensor, infer_state: LlamaInferState) -> torch.Tensor:
