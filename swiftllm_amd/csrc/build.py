@@ -24,7 +24,6 @@ SOURCES = [
     "prefill_attn_paged.hip",
     "kvcache_fp8.hip",
     "paged_attn_fp8.hip",
-    "prefill_attn_paged_fp8.hip",
     "block_table.hip",
     "swap_blocks.hip",
     "gemm_skinny.hip",
@@ -35,7 +34,7 @@ SOURCES = [
     "sampling.hip",
     "decode_engine.hip",
 ]
-HEADERS = ["swl_common.h", "attend_block.h", "fp8_kv.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
+HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "fp8_kv.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
 LIB = os.path.join(HERE, "libswiftllm_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 ARCH = "gfx950"

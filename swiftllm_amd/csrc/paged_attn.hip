@@ -27,8 +27,7 @@
 // paged_attn.py:72-73; ours is closer to the exact value). Partials use the reference's format:
 // mid_o = acc/sum (normalised), mid_lse = log2(sum) + max in the scaled base-2 domain
 // (paged_attn.py:106-108), so phase 1 can be compared with the reference's phase 1 directly.
-#include "swl_common.h"
-#include "attend_block.h"
+#include "attn_mfma.h"
 
 namespace swl {
 
@@ -76,55 +75,6 @@ struct PagedAttnParams {
 // (the VALU version: 8 G). P is fed as hi + lo 16-bit halves (two MFMAs): the product keeps fp32-level accuracy
 // instead of the storage dtype's, so the numerics stay those of the VALU version (and of the reference's fp32 p,
 // paged_attn.py:74-79) at 16 more MFMA issues per block.
-typedef short short4_t __attribute__((ext_vector_type(4)));
-template <typename T>
-struct Vec4 {
-    typedef T type __attribute__((ext_vector_type(4)));
-};
-
-__device__ __forceinline__ float4_t mfma16x32(vec8_t<f16> a, vec8_t<f16> b, float4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float4_t mfma16x32(vec8_t<bf16> a, vec8_t<bf16> b, float4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float4_t mfma16x16(short4_t a, typename Vec4<f16>::type b, float4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(typename Vec4<f16>::type, a), b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float4_t mfma16x16(short4_t a, typename Vec4<bf16>::type b, float4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(short4_t, b), c, 0, 0, 0);
-}
-// LDS transpose read (gfx950): the 16 lanes of a group each give the address of 4 consecutive 16-bit elements (lanes
-// 4r..4r+3 = the four quarters of row r); lane i receives column i of that 4 x 16 block: {row0[i], .., row3[i]}.
-template <typename T>
-__device__ __forceinline__ short4_t lds_tr16_b64(const T *p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3))) *)(p));
-}
-
-// All-reduce over the four 16-lane rows of a wave (lanes l, l^16, l^32, l^48), VALU only:
-// v_permlane16_swap(a, a) -> {rows 0,0,2,2 | rows 1,1,3,3}, v_permlane32_swap(b, b) -> {lo, lo | hi, hi}.
-__device__ __forceinline__ float rows_allreduce_max(float v) {
-    const auto r1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(r1[0]), __uint_as_float(r1[1]));
-    const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r2[0]), __uint_as_float(r2[1]));
-}
-__device__ __forceinline__ float rows_allreduce_sum(float v) {
-    const auto r1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r1[0]) + __uint_as_float(r1[1]);
-    const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r2[0]) + __uint_as_float(r2[1]);
-}
-
-template <typename T, int D>
-struct MfmaTile {
-    static constexpr int KRS = D + 8;    // K row pitch (elements): 16 rows -> 16 distinct 16-byte slots for ds_read_b128
-    static constexpr int VRS = D + 16;   // V row pitch: 8 rows x 32 B tile the 64 banks exactly for the b64 transpose read
-    static constexpr int ELEMS = 16 * VRS;
-    static constexpr int QS = D / 32;    // QK^T MFMAs per block
-    static constexpr int OS = D / 16;    // PV MFMA pairs per block
-};
-
 template <typename T, int D, int G>
 __device__ __forceinline__ void attend_block_mfma(const vec8_t<T> (&qb)[MfmaTile<T, D>::QS],
                                                   const vec8_t<T> (&Kv)[DecodeTile<T, D, G>::NI],
@@ -187,7 +137,7 @@ __device__ __forceinline__ void attend_block_mfma(const vec8_t<T> (&qb)[MfmaTile
     }
 #pragma unroll
     for (int mm = 0; mm < MT::OS; ++mm) {
-        const short4_t vf = lds_tr16_b64(stage + (4 * q + (i16 >> 2)) * MT::VRS + 16 * mm + 4 * (i16 & 3));
+        const short4_t vf = lds_tr_read(stage + (4 * q + (i16 >> 2)) * MT::VRS + 16 * mm + 4 * (i16 & 3));
         acc[mm] = mfma16x16(vf, ph, acc[mm]);
         acc[mm] = mfma16x16(vf, pl, acc[mm]);
     }
@@ -220,7 +170,6 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_phase1_kernel(PagedAttnPar
                                                                     const int *__restrict__ seq_ids_r) {
     using Tile = DecodeTile<T, D, G>;
     constexpr int LPT = Tile::LPT, TPI = Tile::TPI, NI = Tile::NI;
-    constexpr int NT = NW * 64;
     __shared__ float sm_ml[NW][G][2];
     __shared__ float sm_acc[NW][G][D];
     __shared__ __attribute__((aligned(16))) T sm_q[QKV ? G * D : 8];
@@ -558,32 +507,7 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_phase1_kernel(PagedAttnPar
     } // !MF
     __syncthreads();
 
-    // ---- merge the NW waves and write the partial (or the final output when there is one split) -
-    const int nsb = p.num_seq_blocks;
-    for (int oidx = threadIdx.x; oidx < G * D; oidx += NT) {
-        const int g = oidx / D;
-        const int d = oidx % D;
-        float M = sm_ml[0][g][0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) M = fmaxf(M, sm_ml[w][g][0]);
-        float Lsum = 0.f, A = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const float wgt = fast_exp2((sm_ml[w][g][0] - M) * c);
-            Lsum = fmaf(sm_ml[w][g][1], wgt, Lsum);
-            A = fmaf(sm_acc[w][g][d], wgt, A);
-        }
-        const float out = A / Lsum;
-        const int head = kvh * G + g;
-        if (nsb == 1) {
-            static_cast<T *>(p.o_direct)[seq * p.o_tok_stride + static_cast<int64_t>(head) * D + d] =
-                to_t<T>(out);
-        } else {
-            const int64_t part = (static_cast<int64_t>(seq) * p.H + head) * nsb + split;
-            p.mid_o[part * D + d] = out;
-            if (d == 0) p.mid_lse[part] = fast_log2(Lsum) + M * c;
-        }
-    }
+    merge_waves_write<T, D, G, NW, false>(p, sm_ml, sm_acc, c, 1.0f, kvh, seq, split);
 }
 
 // grid (H, Bd), one wave per (sequence, q-head): LSE-weighted merge of the partials (reference paged_attn.py:

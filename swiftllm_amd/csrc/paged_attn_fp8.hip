@@ -20,6 +20,7 @@
 //   * the masked-garbage rule: 0x7f / 0xff are NaN and a slot past the sequence's length may hold them. A block that
 //     crosses the length has the codes of its rows >= len replaced by 0x00 (= +0) in registers before conversion, K and V
 //     alike; blocks wholly past it are never loaded. p = 0 then meets v = 0, never NaN.
+#include "attn_mfma.h"
 #include "fp8_kv.h"
 
 // Ring depth (16-token blocks resident per wave, one of them being attended). 2: at D = 128 the 8-wave kernel builds to
@@ -32,7 +33,6 @@
 
 namespace swl {
 
-constexpr int kBlk8 = 16;          // tokens per KV block
 constexpr int kPa8Depth = SWL_PA8_DEPTH;
 
 struct PagedAttnFp8Params {
@@ -48,61 +48,28 @@ struct PagedAttnFp8Params {
     int64_t q_tok_stride, o_tok_stride;
 };
 
-typedef short pa8_short4_t __attribute__((ext_vector_type(4)));
-template <typename T>
-struct Pa8Vec4 {
-    typedef T type __attribute__((ext_vector_type(4)));
-};
-
-__device__ __forceinline__ float4_t pa8_mfma16x32(vec8_t<f16> a, vec8_t<f16> b, float4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float4_t pa8_mfma16x32(vec8_t<bf16> a, vec8_t<bf16> b, float4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float4_t pa8_mfma16x16(pa8_short4_t a, typename Pa8Vec4<f16>::type b, float4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(typename Pa8Vec4<f16>::type, a), b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float4_t pa8_mfma16x16(pa8_short4_t a, typename Pa8Vec4<bf16>::type b, float4_t c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, __builtin_bit_cast(pa8_short4_t, b), c, 0, 0, 0);
-}
-template <typename T>
-__device__ __forceinline__ pa8_short4_t pa8_lds_tr16_b64(const T *p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((pa8_short4_t __attribute__((address_space(3))) *)(p));
-}
-__device__ __forceinline__ float pa8_rows_allreduce_max(float v) {
-    const auto r1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(r1[0]), __uint_as_float(r1[1]));
-    const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(r2[0]), __uint_as_float(r2[1]));
-}
-__device__ __forceinline__ float pa8_rows_allreduce_sum(float v) {
-    const auto r1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(r1[0]) + __uint_as_float(r1[1]);
-    const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(r2[0]) + __uint_as_float(r2[1]);
-}
-
+// How a wave's 16-byte lanes cover the 16-token x D-byte tile of one (block, layer, kv-head); the stage's pitches are
+// MfmaTile's (attn_mfma.h).
 template <int D>
-struct Pa8Tile {
+struct Fp8DecodeTile {
     static constexpr int LPT = D / 16;                          // lanes per token row (16 codes each)
-    static constexpr int TPI = 64 / LPT < kBlk8 ? 64 / LPT : kBlk8;   // token rows per load instruction
-    static constexpr int NI = kBlk8 / TPI;                      // load instructions per 16-token block
-    static constexpr bool ALL = LPT * kBlk8 >= 64;              // every lane owns a chunk of the tile (D >= 64)
-    static constexpr int KRS = D + 8;    // K row pitch in the stage (elements of T), as MfmaTile of paged_attn.hip
-    static constexpr int VRS = D + 16;   // V row pitch
-    static constexpr int ELEMS = 16 * VRS;
-    static constexpr int QS = D / 32;    // QK^T MFMAs per block
-    static constexpr int OS = D / 16;    // PV MFMA pairs per block
+    static constexpr int TPI = 64 / LPT < kBlk ? 64 / LPT : kBlk;   // token rows per load instruction
+    static constexpr int NI = kBlk / TPI;                       // load instructions per 16-token block
+    static constexpr bool ALL = LPT * kBlk >= 64;               // every lane owns a chunk of the tile (D >= 64)
 };
 
-// One 16-token block of one wave: codes -> stage -> attend_block_mfma's arithmetic (paged_attn.hip), unchanged.
+// One 16-token block of one wave: codes -> stage -> attend_block_mfma's arithmetic (paged_attn.hip), unchanged. From the
+// scores on, the text is that function's on purpose: as a shared __forceinline__ helper it compiled to another register
+// allocation in this kernel (one SGPR at D = 128, two VGPRs at D = 32; hipcc of ROCm 7.2) with the fp32 adds commuted,
+// and the rings of both kernels are sized against the 256-VGPR budget.
 template <typename T, int D>
-__device__ __forceinline__ void attend_block_fp8(const vec8_t<T> (&qb)[Pa8Tile<D>::QS], const u32x4_t (&Kraw)[Pa8Tile<D>::NI],
-                                                 const u32x4_t (&Vraw)[Pa8Tile<D>::NI], float &m, float &l,
-                                                 float4_t (&acc)[Pa8Tile<D>::OS], T *stage, float c, int tok0, int row,
-                                                 int chunk, int lane, int len, bool partial) {
-    using Tile = Pa8Tile<D>;
+__device__ __forceinline__ void attend_block_fp8(const vec8_t<T> (&qb)[MfmaTile<T, D>::QS],
+                                                 const u32x4_t (&Kraw)[Fp8DecodeTile<D>::NI],
+                                                 const u32x4_t (&Vraw)[Fp8DecodeTile<D>::NI], float &m, float &l,
+                                                 float4_t (&acc)[MfmaTile<T, D>::OS], T *stage, float c, int tok0,
+                                                 int row, int chunk, int lane, int len, bool partial) {
+    using Tile = Fp8DecodeTile<D>;
+    using MT = MfmaTile<T, D>;
     constexpr int NI = Tile::NI;
     const int q = lane >> 4, i16 = lane & 15;
     u32x4_t Kc[NI], Vc[NI];
@@ -123,22 +90,22 @@ __device__ __forceinline__ void attend_block_fp8(const vec8_t<T> (&qb)[Pa8Tile<D
     // several) into 16-bit registers ahead of its turn
 #pragma unroll
     for (int i = 0; i < NI; ++i) asm volatile("" : "+v"(Kc[i]));
-    const bool stager = Tile::ALL || row < kBlk8;
+    const bool stager = Tile::ALL || row < kBlk;
     if (stager) {
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             vec8_t<T> lo, hi;
             fp8x16_to_t<T>(Kc[i], lo, hi);
-            T *dst = stage + (i * Tile::TPI + row) * Tile::KRS + chunk * 16;
+            T *dst = stage + (i * Tile::TPI + row) * MT::KRS + chunk * 16;
             *reinterpret_cast<vec8_t<T> *>(dst) = lo;
             *reinterpret_cast<vec8_t<T> *>(dst + 8) = hi;
         }
     }
     float4_t s = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int j = 0; j < Tile::QS; ++j) {
-        const vec8_t<T> kf = *reinterpret_cast<const vec8_t<T> *>(stage + i16 * Tile::KRS + 32 * j + 8 * q);
-        s = pa8_mfma16x32(kf, qb[j], s);
+    for (int j = 0; j < MT::QS; ++j) {
+        const vec8_t<T> kf = *reinterpret_cast<const vec8_t<T> *>(stage + i16 * MT::KRS + 32 * j + 8 * q);
+        s = mfma16x32(kf, qb[j], s);
     }
     mfma_results_ready<4>(s); // the scores are read by VALU next, behind a branch (swl_common.h)
     // V goes into the same tile once the K fragments are out (same wave: LDS executes in order)
@@ -149,7 +116,7 @@ __device__ __forceinline__ void attend_block_fp8(const vec8_t<T> (&qb)[Pa8Tile<D
         for (int i = 0; i < NI; ++i) {
             vec8_t<T> lo, hi;
             fp8x16_to_t<T>(Vc[i], lo, hi);
-            T *dst = stage + (i * Tile::TPI + row) * Tile::VRS + chunk * 16;
+            T *dst = stage + (i * Tile::TPI + row) * MT::VRS + chunk * 16;
             *reinterpret_cast<vec8_t<T> *>(dst) = lo;
             *reinterpret_cast<vec8_t<T> *>(dst + 8) = hi;
         }
@@ -161,7 +128,7 @@ __device__ __forceinline__ void attend_block_fp8(const vec8_t<T> (&qb)[Pa8Tile<D
             if (tok0 + 4 * q + r >= len) s[r] = kNegBig;
     }
     float mb = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
-    mb = pa8_rows_allreduce_max(mb);
+    mb = rows_allreduce_max(mb);
     const float m_new = fmaxf(m, mb);
     const float alpha = fast_exp2((m - m_new) * c); // difference first (see attend_block.h)
     const float mc = m_new * c;
@@ -175,7 +142,7 @@ __device__ __forceinline__ void attend_block_fp8(const vec8_t<T> (&qb)[Pa8Tile<D
     }
     l = fmaf(l, alpha, (pf[0] + pf[1]) + (pf[2] + pf[3]));
     m = m_new;
-    typename Pa8Vec4<T>::type ph, pl;
+    typename Vec4<T>::type ph, pl;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         ph[r] = to_t<T>(pf[r]);
@@ -183,13 +150,13 @@ __device__ __forceinline__ void attend_block_fp8(const vec8_t<T> (&qb)[Pa8Tile<D
     }
     if (!__all(alpha == 1.0f)) {
 #pragma unroll
-        for (int mm = 0; mm < Tile::OS; ++mm) acc[mm] *= alpha;
+        for (int mm = 0; mm < MT::OS; ++mm) acc[mm] *= alpha;
     }
 #pragma unroll
-    for (int mm = 0; mm < Tile::OS; ++mm) {
-        const pa8_short4_t vf = pa8_lds_tr16_b64(stage + (4 * q + (i16 >> 2)) * Tile::VRS + 16 * mm + 4 * (i16 & 3));
-        acc[mm] = pa8_mfma16x16(vf, ph, acc[mm]);
-        acc[mm] = pa8_mfma16x16(vf, pl, acc[mm]);
+    for (int mm = 0; mm < MT::OS; ++mm) {
+        const short4_t vf = lds_tr_read(stage + (4 * q + (i16 >> 2)) * MT::VRS + 16 * mm + 4 * (i16 & 3));
+        acc[mm] = mfma16x16(vf, ph, acc[mm]);
+        acc[mm] = mfma16x16(vf, pl, acc[mm]);
     }
 }
 
@@ -200,13 +167,13 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_fp8_phase1_kernel(PagedAtt
                                                                         const int *__restrict__ block_table,
                                                                         const int *__restrict__ seq_lens_r,
                                                                         const int *__restrict__ seq_ids_r) {
-    using Tile = Pa8Tile<D>;
+    using Tile = Fp8DecodeTile<D>;
+    using MT = MfmaTile<T, D>;
     constexpr int NI = Tile::NI;
-    constexpr int NT = NW * 64;
     constexpr int ND = kPa8Depth;
     __shared__ float sm_ml[NW][G][2];
     __shared__ float sm_acc[NW][G][D];
-    __shared__ __attribute__((aligned(16))) T sm_stage[NW][Tile::ELEMS];
+    __shared__ __attribute__((aligned(16))) T sm_stage[NW][MT::ELEMS];
 
     const int split = blockIdx.x;
     const int kvh = blockIdx.y;
@@ -215,7 +182,7 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_fp8_phase1_kernel(PagedAtt
     const int tok_begin = split * p.seq_block_size;
     if (tok_begin >= len) return; // uniform for the workgroup, before any barrier
     const int tok_end = min(len, tok_begin + p.seq_block_size);
-    const int blk_end = (tok_end + kBlk8 - 1) / kBlk8;
+    const int blk_end = (tok_end + kBlk - 1) / kBlk;
     const int seq_id = seq_ids_r[seq];
     const int *__restrict__ bt = block_table + static_cast<int64_t>(seq_id) * p.max_blocks_per_seq;
 
@@ -227,28 +194,28 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_fp8_phase1_kernel(PagedAtt
     const float v_scale = p.kv_scales[(static_cast<int64_t>(p.L) + p.layer) * p.KVH + kvh];
     const float c = p.scale_log2e * k_scale;
 
-    const int64_t tile_bytes = static_cast<int64_t>(kBlk8) * D;
+    const int64_t tile_bytes = static_cast<int64_t>(kBlk) * D;
     const int64_t layer_head = static_cast<int64_t>(p.layer) * p.KVH + kvh;
     const int64_t blk_pitch = static_cast<int64_t>(p.L) * p.KVH;
     // D = 32: a tile is 512 bytes, lanes 32..63 read it a second time (in bounds) and never stage it
     const int lane_off = (Tile::ALL ? lane : (lane & 31)) * 16;
 
-    vec8_t<T> qb[Tile::QS];               // Q^T B fragments, lane (q, h) -> Q[head h][32 j + 8 q ..], zero for h >= G
+    vec8_t<T> qb[MT::QS];               // Q^T B fragments, lane (q, h) -> Q[head h][32 j + 8 q ..], zero for h >= G
     const int mq = lane >> 4, mh = lane & 15;
     {
         const T *qp = static_cast<const T *>(p.q) + seq * p.q_tok_stride +
                       (static_cast<int64_t>(kvh) * G + min(mh, G - 1)) * D + 8 * mq;
 #pragma unroll
-        for (int j = 0; j < Tile::QS; ++j) {
+        for (int j = 0; j < MT::QS; ++j) {
             qb[j] = load8(qp + 32 * j);
             if (mh >= G) qb[j] = vec8_t<T>{};
         }
     }
 
     float m = kNegBig, l = 0.f;
-    float4_t acc4[Tile::OS];              // O^T[d = 16 mm + 4 q + r][head h]
+    float4_t acc4[MT::OS];              // O^T[d = 16 mm + 4 q + r][head h]
 #pragma unroll
-    for (int mm = 0; mm < Tile::OS; ++mm) acc4[mm] = float4_t{0.f, 0.f, 0.f, 0.f};
+    for (int mm = 0; mm < MT::OS; ++mm) acc4[mm] = float4_t{0.f, 0.f, 0.f, 0.f};
 
     u32x4_t Kr[ND][NI], Vr[ND][NI];
     auto load_phys = [&](int64_t phys, u32x4_t(&Kd)[NI], u32x4_t(&Vd)[NI]) {
@@ -263,12 +230,12 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_fp8_phase1_kernel(PagedAtt
         load_phys(bt[b], Kd, Vd); // scalar load: b is wave-uniform
     };
     auto attend = [&](int b, u32x4_t(&Kd)[NI], u32x4_t(&Vd)[NI]) {
-        const int tok0 = b * kBlk8;
+        const int tok0 = b * kBlk;
         attend_block_fp8<T, D>(qb, Kd, Vd, m, l, acc4, &sm_stage[wave][0], c, tok0, row, chunk, lane, len,
-                               tok0 + kBlk8 > len);
+                               tok0 + kBlk > len);
     };
 
-    int b = tok_begin / kBlk8 + wave;
+    int b = tok_begin / kBlk + wave;
     // the first ND blocks of this wave go into slots 0..ND-1
 #pragma unroll
     for (int d = 0; d < ND; ++d)
@@ -310,47 +277,22 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_fp8_phase1_kernel(PagedAtt
 
     // O^T of the last block is stored by DS instructions below (swl_common.h)
 #pragma unroll
-    for (int mm = 0; mm < Tile::OS; ++mm) mfma_results_tie(acc4[mm]);
-    mfma_results_ready<4>(acc4[Tile::OS - 1]);
+    for (int mm = 0; mm < MT::OS; ++mm) mfma_results_tie(acc4[mm]);
+    mfma_results_ready<4>(acc4[MT::OS - 1]);
     // the four lanes (q = 0..3) of a head share m and each hold the row sum of their own tokens; O^T is complete
-    const float lt = pa8_rows_allreduce_sum(l);
+    const float lt = rows_allreduce_sum(l);
     if (mh < G) {
         if (mq == 0) {
             sm_ml[wave][mh][0] = m;
             sm_ml[wave][mh][1] = lt;
         }
 #pragma unroll
-        for (int mm = 0; mm < Tile::OS; ++mm)
+        for (int mm = 0; mm < MT::OS; ++mm)
 #pragma unroll
             for (int r = 0; r < 4; ++r) sm_acc[wave][mh][16 * mm + 4 * mq + r] = acc4[mm][r];
     }
     __syncthreads();
-
-    // ---- merge the NW waves and write the partial (or the final output when there is one split) -
-    const int nsb = p.num_seq_blocks;
-    for (int oidx = threadIdx.x; oidx < G * D; oidx += NT) {
-        const int g = oidx / D;
-        const int d = oidx % D;
-        float M = sm_ml[0][g][0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) M = fmaxf(M, sm_ml[w][g][0]);
-        float Lsum = 0.f, A = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const float wgt = fast_exp2((sm_ml[w][g][0] - M) * c);
-            Lsum = fmaf(sm_ml[w][g][1], wgt, Lsum);
-            A = fmaf(sm_acc[w][g][d], wgt, A);
-        }
-        const float out = (A / Lsum) * v_scale;
-        const int head = kvh * G + g;
-        if (nsb == 1) {
-            static_cast<T *>(p.o_direct)[seq * p.o_tok_stride + static_cast<int64_t>(head) * D + d] = to_t<T>(out);
-        } else {
-            const int64_t part = (static_cast<int64_t>(seq) * p.H + head) * nsb + split;
-            p.mid_o[part * D + d] = out;
-            if (d == 0) p.mid_lse[part] = fast_log2(Lsum) + M * c;
-        }
-    }
+    merge_waves_write<T, D, G, NW, true>(p, sm_ml, sm_acc, c, v_scale, kvh, seq, split);
 }
 
 template <typename T, int D, int G>
@@ -358,7 +300,7 @@ static int launch_fp8_phase1(const PagedAttnFp8Params &p, const int *bt, const i
                              hipStream_t stream) {
     const dim3 grid(p.num_seq_blocks, p.KVH, Bd);
     // >= 32 KV blocks per sequence block: 8-wave workgroups (>= 4 blocks per wave); else 4 waves (paged_attn.hip)
-    if (p.seq_block_size >= 32 * kBlk8)
+    if (p.seq_block_size >= 32 * kBlk)
         hipLaunchKernelGGL((paged_attn_fp8_phase1_kernel<T, D, G, 8>), grid, dim3(512), 0, stream, p, bt, lens, ids);
     else
         hipLaunchKernelGGL((paged_attn_fp8_phase1_kernel<T, D, G, 4>), grid, dim3(256), 0, stream, p, bt, lens, ids);
@@ -394,7 +336,7 @@ extern "C" int swl_paged_attn_phase1_fp8(void *o_direct, const void *q, const vo
         return SWL_ERR_BAD_ARG;
     if (!(head_dim == 32 || head_dim == 64 || head_dim == 128)) return SWL_ERR_BAD_ARG;
     if (!(dtype == SWL_F16 || dtype == SWL_BF16)) return SWL_ERR_BAD_ARG;
-    if (block_size != swl::kBlk8) return SWL_ERR_UNSUPPORTED;
+    if (block_size != swl::kBlk) return SWL_ERR_UNSUPPORTED;
     if (seq_block_size <= 0 || seq_block_size % block_size != 0) return SWL_ERR_BAD_ARG;
     if (num_seq_blocks == 1 ? !o_direct : (!mid_o || !mid_lse)) return SWL_ERR_BAD_ARG;
     if (!swl::aligned16(q) || !swl::aligned16(k_cache) || !swl::aligned16(v_cache) || (q_tok_stride & 7))

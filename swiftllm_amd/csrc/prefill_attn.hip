@@ -27,27 +27,9 @@
 // the PV product, fp32 accumulators, one rounding at the store (prefill_attn.py:62-71,100).
 #include <stdlib.h>
 
-#include "swl_common.h"
+#include "attn_mfma.h"
 
 namespace swl {
-
-typedef short short4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float16_t mfma32(vec8_t<f16> a, vec8_t<f16> b, float16_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float16_t mfma32(vec8_t<bf16> a, vec8_t<bf16> b, float16_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// LDS transpose read: the 16 lanes of a group each supply the address of 4 consecutive 16-bit
-// elements (one quarter of a 16-element row; lanes 4r..4r+3 = row r); lane i receives column i of
-// the resulting 4x16 block, i.e. {row0[i], row1[i], row2[i], row3[i]}.
-template <typename T>
-__device__ __forceinline__ short4_t lds_tr_read(const T *p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (short4_t __attribute__((address_space(3))) *)(p));
-}
 
 struct PrefillParams {
     void *o;
@@ -61,7 +43,6 @@ struct PrefillParams {
     int64_t q_tok_stride, k_tok_stride, v_tok_stride, o_tok_stride;
 };
 
-constexpr float kLazyMax = 4.0f; // see the softmax step of the kernels (p <= 16)
 constexpr int kBQ = 128; // q rows per workgroup
 constexpr int kBK = 64;  // keys per LDS tile
 

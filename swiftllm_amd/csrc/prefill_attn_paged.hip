@@ -28,24 +28,28 @@
 // exactly 0, but 0 * NaN in the PV product is NaN. Keys >= c + n are therefore never read: their K and V rows are
 // staged as zeros (block-table indices past the sequence's last block are clamped and unused). Keys inside [0, c + n)
 // above a row's diagonal are real, finite rows the store has just written; their scores are replaced by the finite
-// stand-in for -inf before the softmax, so p = 0 times a finite v.
-#include "swl_common.h"
+// stand-in for -inf before the softmax, so p = 0 times a finite v. In an FP8 pool the codes 0x7f / 0xff are NaN and a slot
+// past the length may hold them: the rule is the same, the zero rows are staged as code 0x00 = +0.
+//
+// The two pool formats. prefill_attn_paged_kernel<T, D, FP8> is ONE kernel: grid, tiles, fragment order, masking, lazy
+// maximum and epilogue do not know how the pool is stored. FP8 = false reads pools of T. FP8 = true reads 1-byte e4m3fn
+// pools (storage contract: fp8_kv.h) and computes on the STORED values, since the conversion to T is exact. What the
+// format decides is the staging and two factors:
+//   * a lane's 16 bytes per pass are 8 elements or 16 codes, so a pass covers 256 / (D / 8) tile rows (16 / 32 / 64 at
+//     D = 128 / 64 / 32) or 256 / (D / 16), at most the tile (32 / 64 / 64; at D = 32 threads 128..255 stage nothing).
+//     Only the 16-row pass of 16-bit pools at D = 128 has a workgroup-uniform block id; an FP8 pass may span two blocks;
+//   * FP8: the conversion (v_cvt_scalef32_pk_*_fp8, scale 1) sits between the staging registers and the two 16-byte LDS
+//     writes per lane;
+//   * FP8: k_scale[layer, kv-head] is folded into the exp2 factor c = scale * log2(e) * k_scale, v_scale into the final
+//     normalisation before the one rounding. 16-bit pools carry no such multiplies.
+// With FP8 pools the chunk's own keys are read back QUANTISED: a chunked prompt is not bit-equal to a whole-prompt prefill
+// (which attends to its fresh 16-bit projections).
+#include <type_traits>
+
+#include "attn_mfma.h"
+#include "fp8_kv.h"
 
 namespace swl {
-
-typedef short short4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float16_t pg_mfma32(vec8_t<f16> a, vec8_t<f16> b, float16_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float16_t pg_mfma32(vec8_t<bf16> a, vec8_t<bf16> b, float16_t c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-// LDS transpose read (see prefill_attn.hip): lane i of a 16-lane group receives column i of a 4 x 16 block.
-template <typename T>
-__device__ __forceinline__ short4_t pg_lds_tr_read(const T *p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4_t __attribute__((address_space(3))) *)(p));
-}
 
 struct PagedPrefillParams {
     void *o;
@@ -60,22 +64,25 @@ struct PagedPrefillParams {
     int num_layers, cur_layer, max_blocks_per_seq;
     float scale_log2e;
     int64_t q_tok_stride, o_tok_stride;
+    const float *kv_scales;     // FP8 pools: [2][L][KVH]; not read for 16-bit pools
 };
 
-constexpr float kPgLazyMax = 4.0f; // = kLazyMax of prefill_attn.hip (p <= 16)
 constexpr int kPgBQ = 128;         // chunk rows per workgroup
 constexpr int kPgBK = 64;          // keys per LDS tile = four pool blocks
-constexpr int kPgBlk = 16;         // tokens per pool block
 
-template <typename T, int D>
+template <typename T, int D, bool FP8>
 __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefillParams p) {
     constexpr int KRS = D + 8;   // K row pitch (elements): 16 consecutive rows hit 16 distinct 16-B slots
     constexpr int VRS = D + 32;  // V row pitch: 4 rows x two 16-col halves tile the 64 banks exactly
     constexpr int KSTEPS = D / 16;
     constexpr int DT = D / 32;
-    constexpr int CPR = D / 8;           // 16-byte chunks per row
-    constexpr int RPP = 256 / CPR;       // rows staged per pass (16 / 32 / 64 at D = 128 / 64 / 32)
-    constexpr int NPASS = kPgBK / RPP;   // passes per tile
+    constexpr int CPR = D / 8;           // 16-byte chunks per row of T (epilogue)
+    using Pool = std::conditional_t<FP8, uint8_t, T>;        // pool element
+    using Raw = std::conditional_t<FP8, u32x4_t, vec8_t<T>>; // a lane's 16 bytes of a pool row
+    constexpr int EPC = 16 / sizeof(Pool);   // pool elements per 16-byte chunk
+    constexpr int SCPR = D / EPC;            // 16-byte chunks per pool row (staging)
+    constexpr int RPP = 256 / SCPR < kPgBK ? 256 / SCPR : kPgBK;   // rows staged per pass (see the header)
+    constexpr int NPASS = kPgBK / RPP;       // passes per tile
     __shared__ __attribute__((aligned(16))) T smem[kPgBK * KRS + kPgBK * VRS];   // K tile, V tile; the O tiles of the epilogue
     T *const Ks = smem;
     T *const Vs = smem + kPgBK * KRS;
@@ -101,7 +108,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
     if (q0 >= len) return;
     const int ctx = p.ctx_lens[seq];
     const int total = ctx + len;                        // keys resident once the chunk is stored
-    const int last_blk = (total - 1) / kPgBlk;          // last logical block of the sequence (len >= 1 here)
+    const int last_blk = (total - 1) / kBlk;            // last logical block of the sequence (len >= 1 here)
     const int *bt = p.block_table + static_cast<int64_t>(p.seq_ids[seq]) * p.max_blocks_per_seq;
 
     const int tid = threadIdx.x;
@@ -113,11 +120,15 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
     const int qrow = q0w + l32;     // this lane's chunk row
     const int qpos = ctx + qrow;    // ... and its absolute position: it sees keys <= qpos
     const int qpos0w = ctx + q0w;
-    const float c = p.scale_log2e;
+    float c = p.scale_log2e, v_scale = 1.0f;
+    if constexpr (FP8) {
+        c *= p.kv_scales[static_cast<int64_t>(p.cur_layer) * p.KVH + kvh];
+        v_scale = p.kv_scales[(static_cast<int64_t>(p.num_layers) + p.cur_layer) * p.KVH + kvh];
+    }
 
     const T *qg = static_cast<const T *>(p.q);
-    const T *kc = static_cast<const T *>(p.k_cache);
-    const T *vc = static_cast<const T *>(p.v_cache);
+    const Pool *kc = static_cast<const Pool *>(p.k_cache);
+    const Pool *vc = static_cast<const Pool *>(p.v_cache);
 
     // ---- Q^T B-fragments: lane holds Q[qrow][kk*16 + hf*8 .. +8] ---------------------------------
     vec8_t<T> qf[KSTEPS];
@@ -140,18 +151,21 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
     float l_run = 0.f;
 
     // ---- staging: thread -> (tile row srow + pass*RPP, chunk sc); tile row r = block r / 16 of the tile, slot r % 16 ----
-    const int srow = tid / CPR;
-    const int sc = tid % CPR;
-    vec8_t<T> kst[NPASS], vst[NPASS];
+    const int srow = tid / SCPR;
+    const int sc = tid % SCPR;
+    // FP8, D = 32: a pass is the whole tile and threads 128.. have no row. (At D >= 64 every FP8 thread stages as well; the
+    // test stays a run-time one there, as it has been since the FP8 kernel was written: its register allocation is kept.)
+    const bool stager = !FP8 || srow < RPP;
+    Raw kst[NPASS], vst[NPASS];
     int bid[NPASS];                                      // pool block of each pass, for the tile fetch_tile takes next
-    // element offset of (block 0, this layer, this kv-head, slot 0) and the pitch of one pool block
-    const int64_t blk_pitch = static_cast<int64_t>(p.num_layers) * p.KVH * kPgBlk * D;
-    const int64_t slab0 = (static_cast<int64_t>(p.cur_layer) * p.KVH + kvh) * kPgBlk * D;
+    // offset of (block 0, this layer, this kv-head, slot 0) and the pitch of one pool block, in pool elements
+    const int64_t blk_pitch = static_cast<int64_t>(p.num_layers) * p.KVH * kBlk * D;
+    const int64_t slab0 = (static_cast<int64_t>(p.cur_layer) * p.KVH + kvh) * kBlk * D;
     auto load_ids = [&](int tile) {
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
-            // (D = 128: RPP = 16, the block of a pass is the same for the whole workgroup — a scalar load)
-            const int b = 4 * tile + (RPP == 16 ? ps : (srow + ps * RPP) >> 4);
+            // (RPP = 16: the block of a pass is the same for the whole workgroup — a scalar load)
+            const int b = 4 * tile + (RPP == 16 ? ps : ((stager ? srow : 0) + ps * RPP) >> 4);
             bid[ps] = bt[min(b, last_blk)];              // indices past the sequence's blocks: clamped, their rows unused
         }
     };
@@ -161,22 +175,33 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
             const int r = srow + ps * RPP;
-            const int64_t off = static_cast<int64_t>(bid[ps]) * blk_pitch + slab0 + (r & 15) * D + sc * 8;
-            vec8_t<T> kt = vec8_t<T>{}, vt = vec8_t<T>{};
-            if (whole || key0 + r < total) {             // keys >= c + n are never read: zeros (see the header)
-                kt = load8(kc + off);
-                vt = load8(vc + off);
+            const int64_t off = static_cast<int64_t>(bid[ps]) * blk_pitch + slab0 + (r & 15) * D + sc * EPC;
+            Raw kt = Raw{}, vt = Raw{};
+            if (stager && (whole || key0 + r < total)) { // keys >= c + n are never read: zeros (see the header)
+                kt = *reinterpret_cast<const Raw *>(kc + off);
+                vt = *reinterpret_cast<const Raw *>(vc + off);
             }
             kst[ps] = kt;
             vst[ps] = vt;
         }
     };
+    auto to_lds = [&](T *dst, const Raw &raw) {
+        if constexpr (FP8) {
+            vec8_t<T> lo, hi;
+            fp8x16_to_t<T>(raw, lo, hi);
+            *reinterpret_cast<vec8_t<T> *>(dst) = lo;
+            *reinterpret_cast<vec8_t<T> *>(dst + 8) = hi;
+        } else {
+            *reinterpret_cast<vec8_t<T> *>(dst) = raw;
+        }
+    };
     auto commit_tile = [&]() {
+        if (!stager) return;
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
             const int r = srow + ps * RPP;
-            *reinterpret_cast<vec8_t<T> *>(&Ks[r * KRS + sc * 8]) = kst[ps];
-            *reinterpret_cast<vec8_t<T> *>(&Vs[r * VRS + sc * 8]) = vst[ps];
+            to_lds(&Ks[r * KRS + sc * EPC], kst[ps]);
+            to_lds(&Vs[r * VRS + sc * EPC], vst[ps]);
         }
     };
 
@@ -213,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
             for (int kk = 0; kk < KSTEPS; ++kk) {
                 const vec8_t<T> kf =
                     *reinterpret_cast<const vec8_t<T> *>(&Ks[k_frag_off + t * 32 * KRS + kk * 16]);
-                st[t] = pg_mfma32(kf, qf[kk], st[t]);
+                st[t] = mfma32(kf, qf[kk], st[t]);
             }
         }
         __builtin_amdgcn_s_setprio(0);
@@ -241,7 +266,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         // lazy running maximum, decided per ROW (prefill_attn.hip): a row's arithmetic depends on its own scores only
         const float m_cand = fmaxf(m_run, mx * c);
-        const float m_new = m_cand - m_run > kPgLazyMax ? m_cand : m_run;
+        const float m_new = m_cand - m_run > kLazyMax ? m_cand : m_run;
         const float alpha = fast_exp2(m_run - m_new);
         m_run = m_new;
         float psum = 0.f;
@@ -273,12 +298,12 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
 #pragma unroll
                 for (int dt = 0; dt < DT; ++dt) {
                     const T *vp = &Vs[v_frag_off + (t * 32 + 16 * ks) * VRS + dt * 32];
-                    const short4_t lo = pg_lds_tr_read(vp);
-                    const short4_t hi = pg_lds_tr_read(vp + 8 * VRS);
+                    const short4_t lo = lds_tr_read(vp);
+                    const short4_t hi = lds_tr_read(vp + 8 * VRS);
                     typedef short short8_t __attribute__((ext_vector_type(8)));
                     const short8_t both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                     const vec8_t<T> vf = __builtin_bit_cast(vec8_t<T>, both);
-                    ot[dt] = pg_mfma32(vf, pb, ot[dt]);
+                    ot[dt] = mfma32(vf, pb, ot[dt]);
                 }
             }
         __builtin_amdgcn_s_setprio(0);
@@ -289,7 +314,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
     for (int dt = 0; dt < DT; ++dt) mfma_results_tie(ot[dt]);
     mfma_results_ready<8>(ot[DT - 1]);
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
+    const float inv = 1.0f / l_tot;                  // (FP8: then v_scale, in fp32, before the one rounding)
     constexpr int ORS = D + 8;                       // O row pitch in LDS (elements)
     static_assert(4 * 32 * ORS <= kPgBK * KRS + kPgBK * VRS, "the four waves' O tiles must fit the K/V tiles' LDS");
     __syncthreads();                                 // every wave is done with the last K/V tile
@@ -301,7 +326,13 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
             typedef T vec4 __attribute__((ext_vector_type(4)));
             vec4 ov;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = to_t<T>(ot[dt][4 * r4 + e] * inv);
+            for (int e = 0; e < 4; ++e) {
+                // (float16, 16-bit pools: product and rounding become one v_fma_mixlo/hi_f16, the exact product rounded
+                // once; the FP8 form rounds it to fp32 first: 1 ulp apart on rare ties — DESIGN.md section 3)
+                float x = ot[dt][4 * r4 + e] * inv;
+                if constexpr (FP8) x *= v_scale;
+                ov[e] = to_t<T>(x);
+            }
             *reinterpret_cast<vec4 *>(ow + l32 * ORS + dt * 32 + 8 * r4 + 4 * hf) = ov;
         }
     // (wave-private tile: LDS operations of one wave complete in order, no barrier needed)
@@ -318,22 +349,27 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
 
 } // namespace swl
 
-extern "C" int swl_prefill_attn_paged(void *o, const void *q, const void *k_cache, const void *v_cache,
-                                      const int32_t *block_table, const int32_t *seq_ids, const int32_t *cu_seqlens,
-                                      const int32_t *ctx_lens, int32_t num_prefill_seqs, int32_t max_new_len,
-                                      int32_t max_total_len, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim,
-                                      int32_t num_layers, int32_t block_size, int32_t cur_layer,
-                                      int32_t max_blocks_per_seq, float softmax_scale, int64_t q_tok_stride,
-                                      int64_t o_tok_stride, int32_t dtype, swl_stream_t stream) {
+// Argument checks and launch of both entries. They differ in what a bad head_dim returns (bad_head_dim), in the scales
+// pointer, and FP8 rejects an unknown dtype before the block size is looked at.
+template <bool FP8>
+static int launch_prefill_attn_paged(void *o, const void *q, const void *k_cache, const void *v_cache, const float *kv_scales,
+                                     const int32_t *block_table, const int32_t *seq_ids, const int32_t *cu_seqlens,
+                                     const int32_t *ctx_lens, int32_t num_prefill_seqs, int32_t max_new_len,
+                                     int32_t max_total_len, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim,
+                                     int32_t num_layers, int32_t block_size, int32_t cur_layer, int32_t max_blocks_per_seq,
+                                     float softmax_scale, int64_t q_tok_stride, int64_t o_tok_stride, int32_t dtype,
+                                     swl_stream_t stream, int bad_head_dim) {
     if (num_prefill_seqs < 0 || max_new_len < 0 || max_total_len < 0) return SWL_ERR_BAD_ARG;
     if (num_prefill_seqs == 0 || max_new_len == 0) return SWL_OK;
-    if (!o || !q || !k_cache || !v_cache || !block_table || !seq_ids || !cu_seqlens || !ctx_lens) return SWL_ERR_BAD_ARG;
+    if (!o || !q || !k_cache || !v_cache || (FP8 && !kv_scales) || !block_table || !seq_ids || !cu_seqlens || !ctx_lens)
+        return SWL_ERR_BAD_ARG;
     if (num_q_heads <= 0 || num_kv_heads <= 0 || num_q_heads % num_kv_heads != 0) return SWL_ERR_BAD_ARG;
     if (num_layers <= 0 || cur_layer < 0 || cur_layer >= num_layers || max_blocks_per_seq <= 0 || block_size <= 0)
         return SWL_ERR_BAD_ARG;
     if (max_total_len < max_new_len) return SWL_ERR_BAD_ARG;
-    if (!(head_dim == 32 || head_dim == 64 || head_dim == 128)) return SWL_ERR_UNSUPPORTED;
-    if (block_size != swl::kPgBlk) return SWL_ERR_UNSUPPORTED;
+    if (!(head_dim == 32 || head_dim == 64 || head_dim == 128)) return bad_head_dim;
+    if (FP8 && !(dtype == SWL_F16 || dtype == SWL_BF16)) return SWL_ERR_BAD_ARG;
+    if (block_size != swl::kBlk) return SWL_ERR_UNSUPPORTED;
     // the longest sequence must fit a block-table row (the kernel reads ceil(total / 16) entries of it)
     if ((static_cast<int64_t>(max_total_len) + block_size - 1) / block_size > max_blocks_per_seq) return SWL_ERR_BAD_ARG;
     if ((q_tok_stride & 7) || (o_tok_stride & 7) || q_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim ||
@@ -360,6 +396,7 @@ extern "C" int swl_prefill_attn_paged(void *o, const void *q, const void *k_cach
     p.scale_log2e = softmax_scale * 1.44269504088896340736f;
     p.q_tok_stride = q_tok_stride;
     p.o_tok_stride = o_tok_stride;
+    p.kv_scales = kv_scales;
     const int64_t units = static_cast<int64_t>(num_prefill_seqs) * num_kv_heads;
     const int64_t units_padded = (units + 7) / 8 * 8;
     const int G = num_q_heads / num_kv_heads;
@@ -369,11 +406,37 @@ extern "C" int swl_prefill_attn_paged(void *o, const void *q, const void *k_cach
     hipStream_t s = static_cast<hipStream_t>(stream);
     SWL_DISPATCH_DTYPE(dtype, T, {
         if (head_dim == 128)
-            hipLaunchKernelGGL((swl::prefill_attn_paged_kernel<T, 128>), grid, dim3(256), 0, s, p);
+            hipLaunchKernelGGL((swl::prefill_attn_paged_kernel<T, 128, FP8>), grid, dim3(256), 0, s, p);
         else if (head_dim == 64)
-            hipLaunchKernelGGL((swl::prefill_attn_paged_kernel<T, 64>), grid, dim3(256), 0, s, p);
+            hipLaunchKernelGGL((swl::prefill_attn_paged_kernel<T, 64, FP8>), grid, dim3(256), 0, s, p);
         else
-            hipLaunchKernelGGL((swl::prefill_attn_paged_kernel<T, 32>), grid, dim3(256), 0, s, p);
+            hipLaunchKernelGGL((swl::prefill_attn_paged_kernel<T, 32, FP8>), grid, dim3(256), 0, s, p);
     });
     return swl::check_launch();
+}
+
+extern "C" int swl_prefill_attn_paged(void *o, const void *q, const void *k_cache, const void *v_cache,
+                                      const int32_t *block_table, const int32_t *seq_ids, const int32_t *cu_seqlens,
+                                      const int32_t *ctx_lens, int32_t num_prefill_seqs, int32_t max_new_len,
+                                      int32_t max_total_len, int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim,
+                                      int32_t num_layers, int32_t block_size, int32_t cur_layer,
+                                      int32_t max_blocks_per_seq, float softmax_scale, int64_t q_tok_stride,
+                                      int64_t o_tok_stride, int32_t dtype, swl_stream_t stream) {
+    return launch_prefill_attn_paged<false>(o, q, k_cache, v_cache, nullptr, block_table, seq_ids, cu_seqlens, ctx_lens,
+                                            num_prefill_seqs, max_new_len, max_total_len, num_q_heads, num_kv_heads,
+                                            head_dim, num_layers, block_size, cur_layer, max_blocks_per_seq, softmax_scale,
+                                            q_tok_stride, o_tok_stride, dtype, stream, SWL_ERR_UNSUPPORTED);
+}
+
+extern "C" int swl_prefill_attn_paged_fp8(void *o, const void *q, const void *k_cache, const void *v_cache,
+                                          const float *kv_scales, const int32_t *block_table, const int32_t *seq_ids,
+                                          const int32_t *cu_seqlens, const int32_t *ctx_lens, int32_t num_prefill_seqs,
+                                          int32_t max_new_len, int32_t max_total_len, int32_t num_q_heads,
+                                          int32_t num_kv_heads, int32_t head_dim, int32_t num_layers, int32_t block_size,
+                                          int32_t cur_layer, int32_t max_blocks_per_seq, float softmax_scale,
+                                          int64_t q_tok_stride, int64_t o_tok_stride, int32_t dtype, swl_stream_t stream) {
+    return launch_prefill_attn_paged<true>(o, q, k_cache, v_cache, kv_scales, block_table, seq_ids, cu_seqlens, ctx_lens,
+                                           num_prefill_seqs, max_new_len, max_total_len, num_q_heads, num_kv_heads,
+                                           head_dim, num_layers, block_size, cur_layer, max_blocks_per_seq, softmax_scale,
+                                           q_tok_stride, o_tok_stride, dtype, stream, SWL_ERR_BAD_ARG);
 }

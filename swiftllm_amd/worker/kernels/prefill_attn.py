@@ -33,7 +33,7 @@ def prefill_attention_paged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
                             o: torch.Tensor, model_config, engine_config, infer_state, cur_layer: int):
     """Chunked prefill (no reference counterpart): prefill sequence s has `infer_state.prefill_ctx_lens[s]` tokens in
     the pool already and its new tokens' K/V were stored behind them on this stream; row i of its chunk attends to every
-    resident key up to its own position. All K/V is read from the pools (csrc/prefill_attn_paged.hip). q/o are
+    resident key up to its own position. All K/V is read from the pools, 16-bit or FP8 (e4m3): one kernel, csrc/prefill_attn_paged.hip. q/o are
     [tokens, heads, head_dim]; only the first `num_prefill_tokens` rows are touched."""
     _hip.require_gpu_tensor(q, "q")
     st = infer_state
@@ -45,7 +45,7 @@ def prefill_attention_paged(q: torch.Tensor, k_cache: torch.Tensor, v_cache: tor
     assert k_cache.is_contiguous() and v_cache.is_contiguous() and block_table.is_contiguous()
     if o.dim() == 2:
         o = o.view(o.shape[0], model_config.num_q_heads, model_config.head_dim)
-    if k_cache.dtype == torch.float8_e4m3fn:    # csrc/prefill_attn_paged_fp8.hip: the chunk's own keys come back quantised
+    if k_cache.dtype == torch.float8_e4m3fn:    # the FP8 instantiation: the chunk's own keys come back quantised
         scales = st.kv_scales
         assert q.dtype == o.dtype and v_cache.dtype == torch.float8_e4m3fn
         assert scales is not None and scales.dtype == torch.float32 and scales.is_contiguous()

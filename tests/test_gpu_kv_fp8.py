@@ -386,6 +386,70 @@ def test_fp8_paged_attention_is_run_to_run_deterministic(dtype):
     assert all(torch.equal(outs[0], o) for o in outs[1:])
 
 
+# ---- d2 / e2. one pool of e4m3 values, stored as bytes or as 16-bit elements: the same bits --------------------------------
+def _two_pools(shape, dtype, g):
+    """K = randn * 0.5 and V = randn quantised at unit scale, in EVERY slot (slots past a length and unowned blocks hold
+    finite codes too): the byte pools, and 16-bit pools holding exactly the same values."""
+    k8 = R.quantise(torch.randn(shape, generator=g) * 0.5, 1.0)
+    v8 = R.quantise(torch.randn(shape, generator=g), 1.0)
+    return k8, v8, R.dequantise(k8, dtype), R.dequantise(v8, dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("H,KVH,D,sbs,lens", [FP8_PAGED_CASES[i] for i in (0, 3, 4, 5)])
+def test_decode_bits_do_not_depend_on_the_pool_format(dtype, H, KVH, D, sbs, lens):
+    """Matrix-core decode (G >= 2; at G = 1 the 16-bit kernel takes the VALU path) over a pool of e4m3 values at unit
+    scales: swl_paged_attn_decode on the 16-bit copy and swl_paged_attn_decode_fp8 on the bytes give the same bits, and so
+    do the phase-1 partials of the two entry points (first case)."""
+    from swiftllm_amd import _hip
+    E = _ext()
+    g = E.gen(H * 7 + D + sbs + (dtype == torch.bfloat16))
+    L, layer = 2, 1
+    need = [-(-n // 16) for n in lens]
+    nb = sum(need) + 3
+    perm = torch.randperm(nb, generator=g)
+    seq_ids = list(range(1, 1 + len(lens)))
+    bt = torch.full((len(lens) + 2, max(need) + 1), int(perm[-1]), dtype=torch.int32)
+    off = 0
+    for sid, nblk in zip(seq_ids, need):
+        bt[sid, :nblk] = perm[off:off + nblk].to(torch.int32)
+        off += nblk
+    k8, v8, k16, v16 = _two_pools((nb, L, KVH, 16, D), dtype, g)
+    q = (torch.randn(len(lens), H, D, generator=g) * 0.5).to(dtype).cuda()
+    st = E._paged_state(lens, seq_ids, sbs, D, "cuda")
+    st.kv_scales = _scales(L, KVH, unit=True).cuda()
+    mc, ec, btd = NS(num_q_heads=H, num_kv_heads=KVH, head_dim=D, num_layers=L), NS(block_size=16), bt.cuda()
+    pools = {"fp8": (k8.cuda(), v8.cuda()), "16-bit": (k16.cuda(), v16.cuda())}
+    outs = {}
+    for name, (kc, vc) in pools.items():
+        o = torch.full_like(q, float("nan"))
+        E.K().paged_attention(q, kc, vc, btd, mc, ec, st, layer, o)
+        outs[name] = o
+    torch.cuda.synchronize()
+    assert torch.isfinite(outs["fp8"].float()).all()
+    assert torch.equal(outs["fp8"], outs["16-bit"]), "the output depends on the pool format"
+    if (H, KVH, D, sbs) != FP8_PAGED_CASES[0][:4]:
+        return
+    nd, nsb = len(lens), -(-max(lens) // sbs)
+    mids = {}
+    for name, (kc, vc) in pools.items():
+        mid_o = torch.full((nd, H, nsb, D), float("nan"), dtype=torch.float32, device="cuda")
+        mid_lse = torch.full((nd, H, nsb), float("-inf"), dtype=torch.float32, device="cuda")
+        tail = (btd.data_ptr(), st.seq_ids.data_ptr(), st.decoding_seq_lens.data_ptr(), mid_o.data_ptr(), mid_lse.data_ptr(),
+                st.softmax_scale, nd, H, KVH, D, L, 16, layer, bt.shape[1], sbs, nsb, H * D, H * D, _hip.dtype_code(dtype),
+                _hip.stream())
+        if name == "fp8":
+            _hip.call("swl_paged_attn_phase1_fp8", 0, q.data_ptr(), kc.data_ptr(), vc.data_ptr(), st.kv_scales.data_ptr(), *tail)
+        else:
+            _hip.call("swl_paged_attn_phase1", 0, q.data_ptr(), kc.data_ptr(), vc.data_ptr(), *tail)
+        mids[name] = (mid_o, mid_lse)
+    torch.cuda.synchronize()
+    written = torch.isfinite(mids["fp8"][1])
+    assert written.any() and torch.equal(written, torch.isfinite(mids["16-bit"][1]))
+    assert torch.equal(mids["fp8"][1], mids["16-bit"][1]), "mid_lse depends on the pool format"
+    assert torch.equal(mids["fp8"][0][written], mids["16-bit"][0][written]), "mid_o depends on the pool format"
+
+
 # ---- e. chunked prefill -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("H,KVH,D", [(8, 2, 128), (4, 2, 64), (4, 4, 32)])
@@ -442,6 +506,69 @@ def test_fp8_paged_prefill_attention(dtype, H, KVH, D):
             off += n
     print(f"\n[fp8 paged prefill {dtype} {H}/{KVH}/{D}] bound fractions: general {worst[0]:.3f} needle {worst[1]:.3f} "
           f"tie {worst[2]:.3f}")
+
+
+CROSS_FORMAT_CHUNKS = [(0, 1), (0, 130), (5, 130), (64, 64), (200, 17), (37, 0)]     # (context, new tokens) of one launch
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16])
+@pytest.mark.parametrize("H,KVH,D", [(8, 2, 128), (4, 2, 64), (4, 4, 32)])
+def test_chunked_prefill_bits_do_not_depend_on_the_pool_format(dtype, H, KVH, D):
+    """One kernel for both pool formats: over a pool of e4m3 values at unit scales, swl_prefill_attn_paged on the 16-bit
+    copy and swl_prefill_attn_paged_fp8 on the bytes give the same bits. One launch with two q-blocks, a partial last
+    tile, a tile-aligned context, staging passes that span two pool blocks, the non-staging threads of D = 32 and an
+    empty chunk. The inputs are checked first: in fp64 the largest softmax weight is below 0.9 for at least half of the
+    rows that see >= 8 keys, so the comparison is not one between one-hot rows.
+    bfloat16 only. With float16 the two formats differ by 1 ulp in about 2^-15 of the output elements, and did before the
+    kernels were merged (measured on MI355X with these inputs: 1 of 43 776 elements at D = 32, 11 of 350 208 at D = 128,
+    each format repeatable): the 16-bit epilogue's `ot * inv` and its rounding become one v_fma_mixlo_f16 — the exact
+    product rounded once — while the FP8 epilogue rounds `ot * inv` to fp32 for the v_scale multiply first (DESIGN.md
+    section 3). bfloat16 has no such instruction: both formats round to fp32, then once to bfloat16."""
+    C = _chk()
+    from swiftllm_amd.worker.kernels.prefill_attn import prefill_attention_paged
+    g = C.gen(H * 13 + D + (dtype == torch.bfloat16))
+    L, layer = 2, 1
+    ctxs, lens = [c for c, _ in CROSS_FORMAT_CHUNKS], [n for _, n in CROSS_FORMAT_CHUNKS]
+    need = [-(-(c + n) // 16) for c, n in CROSS_FORMAT_CHUNKS]
+    nb = sum(need) + 3
+    perm = torch.randperm(nb, generator=g)
+    rows = len(lens) + 2
+    bt = torch.full((rows, max(need) + 3), int(perm[-1]), dtype=torch.int32)
+    seq_ids, mine, off = [], [], 0
+    for i, nblk in enumerate(need):
+        seq_ids.append(rows - 1 - i)
+        mine.append(perm[off:off + nblk])
+        bt[seq_ids[-1], :nblk] = mine[-1].to(torch.int32)
+        off += nblk
+    k8, v8, k16, v16 = _two_pools((nb, L, KVH, 16, D), dtype, g)
+    q = (torch.randn(sum(lens), H, D, generator=g) * 0.5).to(dtype)
+    # the condition on the inputs, from the fp64 softmax on the stored values
+    peaked = seen = 0
+    off = 0
+    for (c, n), blocks in zip(CROSS_FORMAT_CHUNKS, mine):
+        if n == 0:
+            continue
+        pos = torch.arange(c + n)
+        kd = R.dequantise(k8[blocks[pos // 16], layer, :, pos % 16])                 # [c + n, KVH, D] fp64
+        s = scores64(q[off:off + n], kd, D ** -0.5)                                  # [n, H, c + n]
+        vis = pos[None, :] <= torch.arange(n)[:, None] + c
+        pmax = torch.softmax(s.masked_fill(~vis[:, None, :], float("-inf")), dim=-1).amax(-1)     # [n, H]
+        wide = (vis.sum(-1) >= 8)[:, None].expand_as(pmax)
+        seen += int(wide.sum())
+        peaked += int((pmax[wide] >= 0.9).sum())
+        off += n
+    assert seen > 0 and 2 * peaked <= seen, f"{peaked} of {seen} rows with >= 8 keys are one-hot: the inputs decide nothing"
+    st = C._state(ctxs, lens, D, torch.tensor(seq_ids, dtype=torch.int32))
+    st.kv_scales = _scales(L, KVH, unit=True).cuda()
+    mc, ec, qd, btd = NS(num_q_heads=H, num_kv_heads=KVH, head_dim=D, num_layers=L), NS(block_size=16), q.cuda(), bt.cuda()
+    outs = []
+    for kc, vc in ((k8, v8), (k16, v16)):
+        o = torch.full_like(qd, float("nan"))
+        prefill_attention_paged(qd, kc.cuda(), vc.cuda(), btd, o, mc, ec, st, layer)
+        outs.append(o)
+    torch.cuda.synchronize()
+    assert torch.isfinite(outs[0].float()).all()
+    assert torch.equal(outs[0], outs[1]), "the output depends on the pool format"
 
 
 # ---- f-h. the model -----------------------------------------------------------------------------------------------------------
