@@ -18,6 +18,23 @@
  *     (the reference's idle engine spins on empty forwards: server/engine.py:115-171);
  *   - all offsets into the KV pools are 64-bit (288 GB pools exceed 2^31 elements).
  *
+ * Argument and memory contract (checked before any launch; tests/_contract.py holds one row per entry point)
+ *   - unless an entry says otherwise, every 16-bit tensor operand, KV pool, rope table, packed weight, fp32 slab /
+ *     workspace / scratch pointer is 16-byte aligned (the kernels use 16-byte accesses), and every row or token stride
+ *     is a multiple of 8 elements and at least the row width (H * D, KVH * D, K, n ...). Strides are never negative.
+ *     A violation is SWL_ERR_BAD_ARG. The exceptions, each stated at its entry: GEMM outputs (`out` 8 bytes,
+ *     out_row_stride % 4), `residual` of swl_gemm_rows_add* (2 bytes), `x` of swl_sample (2 bytes, any stride >= n);
+ *   - index arrays (int32 / int64), per-row fp32 parameter arrays and the scale tables need their natural alignment;
+ *     this is not checked, except where an entry says so (mid_o / mid_lse, ssq_out of swl_gemm_rows_add_ssq: 4 bytes);
+ *   - a kernel reads and writes nothing outside its operands: rows [0, M) x the row width of every tensor (the
+ *     padding between rows of a strided operand is neither read into a result nor written), the table rows and pool
+ *     blocks its index arrays name, and the first *_bytes of a scratch buffer as the matching *_bytes function
+ *     reports them. Scratch contents need no initialisation and are undefined afterwards;
+ *   - a *_bytes argument smaller than required is SWL_ERR_BAD_ARG; a count past a documented limit, an unsupported
+ *     head / group / block size is SWL_ERR_UNSUPPORTED where the entry says so, else SWL_ERR_BAD_ARG. Counts that become
+ *     a grid dimension are limited to 65535 (SWL_ERR_UNSUPPORTED beyond): the sequences of the attention entries and of
+ *     the prefill stores, the tokens of swl_splitk_add_scale, the rows of swl_argmax.
+ *
  * KV pool layout (reference model.py:138-148): [num_blocks, num_layers, num_kv_heads, block_size, head_dim],
  * contiguous, one pool for K and one for V.
  */
@@ -175,7 +192,15 @@ int swl_sample(int64_t *out, const void *x, int64_t num_rows, int32_t n, int64_t
  * directly. Scratch: mid_o [Bd, H, num_seq_blocks, D] fp32 followed by mid_lse [Bd, H, num_seq_blocks]
  * fp32 — the same shapes the reference allocates at paged_attn.py:170-180.
  * One workgroup serves ALL G = H/KVH q-heads of a kv-head, so every KV byte is fetched once.
- * seq_block_size % block_size == 0; block_size == 16; D in {32, 64, 128}; G in {1, 2, 4, 8}. */
+ * seq_block_size % block_size == 0; block_size == 16; D in {32, 64, 128}; G in {1, 2, 4, 8} (else SWL_ERR_UNSUPPORTED);
+ * num_decoding_seqs <= 65535.
+ * q, o and the pools are 16-byte aligned, q_tok_stride and o_tok_stride are multiples of 8 elements and >= H * D: a
+ * smaller or negative stride would make the rows of o overlap or land in front of the buffer, so it is
+ * SWL_ERR_BAD_ARG, as is a misaligned o. This holds for EVERY decode-attention entry (swl_paged_attn_decode / _phase1 /
+ * _phase2 / _decode_qkv / _decode_qkv_rs / _decode_qkv_rs_partials and the _fp8 twins); where o may be NULL (phase 1
+ * with num_seq_blocks > 1, _partials) its alignment and stride are only checked when it is given. scratch is 16-byte
+ * aligned and holds swl_paged_attn_scratch_bytes(...) bytes; mid_o / mid_lse passed separately are 4-byte aligned.
+ * The _qkv entries also need qkv_slabs, cos_table and sin_table 16-byte aligned; pos_idx may be NULL (row = len - 1). */
 size_t swl_paged_attn_scratch_bytes(int32_t num_decoding_seqs, int32_t num_q_heads,
                                     int32_t head_dim, int32_t num_seq_blocks);
 
@@ -207,7 +232,8 @@ int swl_paged_attn_phase2(void *o, const float *mid_o, const float *mid_lse,
  * in-repo equivalent prefill_attn.py:9-139 (_fwd_prefill_attention / prefill_attention).
  * q[P, H, D], k/v[P, KVH, D] are the FRESH projections (the paged pool is not read), cu_seqlens is
  * prefill_seq_start_locs_with_end (int32 [Bp+1]); o[P, H, D]. MFMA 32x32x16, fp32 softmax.
- * D in {32, 64, 128}; all four tensors 16-byte aligned with token strides that are multiples of 8 elements. */
+ * D in {32, 64, 128}; all four tensors 16-byte aligned with token strides that are multiples of 8 elements and
+ * >= H * D (q, o) / KVH * D (k, v); H % KVH == 0. */
 int swl_prefill_attn_varlen(void *o, const void *q, const void *k, const void *v,
                             const int32_t *cu_seqlens, int32_t num_prefill_seqs,
                             int32_t max_prefill_len, int32_t num_q_heads, int32_t num_kv_heads,
@@ -338,7 +364,8 @@ int swl_rotary_store_kv_decode(void *q, void *k, const void *v, const void *cos_
  * M <= 32 tokens: a weight-streaming MFMA kernel (every byte of W read once, in full lines). When N/32
  * tiles cannot fill the chip, K is split across workgroups into fp32 partial slabs in `workspace` and
  * reduced in a fixed order by a second kernel. N % 32 == 0, K % 128 == 0; x/out rows may be strided
- * (elements). k_splits: 0 = choose, or a power of two <= 16. Larger M: use the BLAS.
+ * (elements): x 16-byte aligned with x_row_stride % 8 == 0, out 8-byte aligned with out_row_stride % 4 == 0 (the same
+ * for every GEMM entry below that has an `out`). k_splits: 0 = choose, or a power of two <= 16. Larger M: use the BLAS.
  * workspace: >= swl_gemm_skinny_workspace_bytes(M, N, K) bytes (0 = none needed). */
 size_t swl_gemm_skinny_workspace_bytes(int32_t M, int32_t N, int32_t K);
 int swl_gemm_skinny(void *out, const void *x, const void *w, void *workspace, size_t workspace_bytes,
@@ -415,6 +442,7 @@ int swl_gemm_skinny_packed_choose_splits(int32_t N, int32_t K); /* 0 = shape uns
 int swl_gemm_skinny_partial(float *slabs, size_t slabs_bytes, const void *x, const void *w, int32_t M,
                             int32_t N, int32_t K, int64_t x_row_stride, int32_t k_splits,
                             int32_t dtype, swl_stream_t stream);
+/* swl_splitk_reduce: N % 4 == 0, slabs 16-byte aligned, out 8-byte aligned, out_row_stride % 4 == 0 and >= N. */
 int swl_splitk_reduce(void *out, const float *slabs, int32_t k_splits, int32_t M, int32_t N,
                       int64_t out_row_stride, int32_t dtype, swl_stream_t stream);
 /* residual <- round(sum slabs) + residual ; x_out <- rmsnorm(residual) * w   (slabs: [k_splits][T][hidden]) */
@@ -451,7 +479,7 @@ int swl_decode_positions(int32_t *pos_idx, const int32_t *seq_lens, int32_t num_
  *     rstd[m] = 1/sqrt(sum_p row_ssq[p][m] / K + eps). Replaces transformer_layer.py:120-127 for decode batches.
  *   swl_paged_attn_decode_qkv_rs: swl_paged_attn_decode_qkv whose fused-qkv slab sums are scaled the same way before they
  *     are rounded, rotated and stored (transformer_layer.py:46-77 + paged_attn.py:152-222). k_splits in {1, 2, 4}.
- * ssq_parts <= 8 everywhere. */
+ * ssq_parts <= 8 everywhere; another k_splits or more ssq_parts is SWL_ERR_UNSUPPORTED. */
 int swl_splitk_add_scale(void *x_scaled, void *residual, const void *w, const float *slabs, int32_t k_splits,
                          float *ssq_out, int64_t num_tokens, int32_t hidden, int32_t dtype, swl_stream_t stream);
 int swl_gemm_skinny_packed_silu_gate_rs(void *out, const void *x, const void *w_up_gate_packed, const float *row_ssq,

@@ -653,6 +653,7 @@ extern "C" int swl_splitk_reduce(void *out, const float *slabs, int32_t k_splits
     if (M < 0 || N <= 0 || (N & 3) || k_splits <= 0) return SWL_ERR_BAD_ARG;
     if (M == 0) return SWL_OK;
     if (!out || !slabs || out_row_stride < N || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
+    if (!swl::aligned16(slabs) || (reinterpret_cast<uintptr_t>(out) & 7u)) return SWL_ERR_BAD_ARG;   // float4 loads, 8-byte stores
     const int64_t items = static_cast<int64_t>(M) * (N / 4);
     const unsigned grid = static_cast<unsigned>((items + 255) / 256);
     SWL_DISPATCH_DTYPE(dtype, T, {

@@ -659,7 +659,13 @@ extern "C" int swl_paged_attn_phase1(void *o_direct, const void *q, const void *
     if (seq_block_size <= 0 || seq_block_size % block_size != 0) return SWL_ERR_BAD_ARG;
     if (num_seq_blocks == 1 ? !o_direct : (!mid_o || !mid_lse)) return SWL_ERR_BAD_ARG;
     if (!swl::aligned16(q) || !swl::aligned16(k_cache) || !swl::aligned16(v_cache) ||
-        (q_tok_stride & 7))
+        (q_tok_stride & 7) || q_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim)
+        return SWL_ERR_BAD_ARG;
+    // o is only looked at when it is given (it may be NULL when the sequences are split)
+    if (o_direct && (!swl::aligned16(o_direct) || (o_tok_stride & 7) ||
+                     o_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim))
+        return SWL_ERR_BAD_ARG;
+    if (num_seq_blocks > 1 && ((reinterpret_cast<uintptr_t>(mid_o) | reinterpret_cast<uintptr_t>(mid_lse)) & 3u))
         return SWL_ERR_BAD_ARG;
     if (num_decoding_seqs > 65535 || num_kv_heads > 65535) return SWL_ERR_UNSUPPORTED;
     swl::PagedAttnParams p{};
@@ -698,6 +704,10 @@ extern "C" int swl_paged_attn_phase2(void *o, const float *mid_o, const float *m
     if (num_decoding_seqs == 0 || num_seq_blocks == 0) return SWL_OK;
     if (!o || !mid_o || !mid_lse || !seq_lens || num_q_heads <= 0 || seq_block_size <= 0 ||
         num_seq_blocks < 0)
+        return SWL_ERR_BAD_ARG;
+    if (!(head_dim == 32 || head_dim == 64 || head_dim == 128)) return SWL_ERR_UNSUPPORTED;
+    if (!swl::aligned16(o) || (o_tok_stride & 7) || o_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim ||
+        ((reinterpret_cast<uintptr_t>(mid_o) | reinterpret_cast<uintptr_t>(mid_lse)) & 3u))
         return SWL_ERR_BAD_ARG;
     if (num_decoding_seqs > 65535) return SWL_ERR_UNSUPPORTED;
     SWL_DISPATCH_DTYPE(dtype, T, {
@@ -811,6 +821,8 @@ static int paged_attn_decode_qkv_impl(void *o, const float *qkv_slabs, int32_t k
     if (seq_block_size <= 0 || seq_block_size % block_size != 0) return SWL_ERR_BAD_ARG;
     if (!swl::aligned16(qkv_slabs) || !swl::aligned16(k_cache) || !swl::aligned16(v_cache) ||
         !swl::aligned16(cos_table) || !swl::aligned16(sin_table))
+        return SWL_ERR_BAD_ARG;
+    if (o && (!swl::aligned16(o) || (o_tok_stride & 7) || o_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim))
         return SWL_ERR_BAD_ARG;
     if (num_decoding_seqs > 65535 || num_kv_heads > 65535) return SWL_ERR_UNSUPPORTED;
     float *mid_o = nullptr, *mid_lse = nullptr;

@@ -339,7 +339,14 @@ extern "C" int swl_paged_attn_phase1_fp8(void *o_direct, const void *q, const vo
     if (block_size != swl::kBlk) return SWL_ERR_UNSUPPORTED;
     if (seq_block_size <= 0 || seq_block_size % block_size != 0) return SWL_ERR_BAD_ARG;
     if (num_seq_blocks == 1 ? !o_direct : (!mid_o || !mid_lse)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(q) || !swl::aligned16(k_cache) || !swl::aligned16(v_cache) || (q_tok_stride & 7))
+    if (!swl::aligned16(q) || !swl::aligned16(k_cache) || !swl::aligned16(v_cache) || (q_tok_stride & 7) ||
+        q_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim)
+        return SWL_ERR_BAD_ARG;
+    // o is only looked at when it is given (it may be NULL when the sequences are split)
+    if (o_direct && (!swl::aligned16(o_direct) || (o_tok_stride & 7) ||
+                     o_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim))
+        return SWL_ERR_BAD_ARG;
+    if (num_seq_blocks > 1 && ((reinterpret_cast<uintptr_t>(mid_o) | reinterpret_cast<uintptr_t>(mid_lse)) & 3u))
         return SWL_ERR_BAD_ARG;
     if (num_decoding_seqs > 65535 || num_kv_heads > 65535) return SWL_ERR_UNSUPPORTED;
     swl::PagedAttnFp8Params p{};

@@ -606,6 +606,9 @@ extern "C" int swl_prefill_attn_varlen(void *o, const void *q, const void *k, co
     if (!(head_dim == 32 || head_dim == 64 || head_dim == 128)) return SWL_ERR_UNSUPPORTED;
     if ((q_tok_stride & 7) || (k_tok_stride & 7) || (v_tok_stride & 7) || (o_tok_stride & 7))
         return SWL_ERR_BAD_ARG;
+    const int64_t q_row = static_cast<int64_t>(num_q_heads) * head_dim, kv_row = static_cast<int64_t>(num_kv_heads) * head_dim;
+    if (q_tok_stride < q_row || o_tok_stride < q_row || k_tok_stride < kv_row || v_tok_stride < kv_row)
+        return SWL_ERR_BAD_ARG;
     if (!swl::aligned16(q) || !swl::aligned16(k) || !swl::aligned16(v) || !swl::aligned16(o))    // (o: 16-byte row stores)
         return SWL_ERR_BAD_ARG;
     swl::PrefillParams p;
