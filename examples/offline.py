@@ -2,7 +2,7 @@
 examples/offline.py against this implementation: build the model, size the KV pool from free HBM,
 prefill a few prompts in one batch, then decode greedily step by step.
 
-    python examples/offline.py --model-path /path/to/llama [--dtype bfloat16] [--steps 20]
+    python examples/offline.py --model-path /path/to/llama [--dtype bfloat16] [--steps 20] [--speculative-ngram 3]
 
 With a HuggingFace tokenizer in the model directory the prompts are text; otherwise (e.g. the random-init
 checkpoints written by oracle/synth.py) random token ids are used and ids are printed.
@@ -26,12 +26,15 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--use-dummy", action="store_true")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8_e4m3"])
+    ap.add_argument("--speculative-ngram", type=int, default=0,
+                    help="prompt-lookup speculative decoding: n-gram drafts per sequence per step (0 = off)")
     args = ap.parse_args()
 
     cfg = swiftllm.EngineConfig(model_path=args.model_path, use_dummy=args.use_dummy, block_size=16,
                                 gpu_mem_utilization=0.9, num_cpu_blocks=0, max_seqs_in_block_table=128,
                                 max_blocks_per_seq=2048, max_batch_size=16, max_tokens_in_batch=2048 * 16,
-                                dtype=args.dtype, use_hip_graph=True, kv_cache_dtype=args.kv_cache_dtype)
+                                dtype=args.dtype, use_hip_graph=True, kv_cache_dtype=args.kv_cache_dtype,
+                                speculative_ngram=args.speculative_ngram)
     t0 = time.perf_counter()
     model = swiftllm.LlamaModel(cfg)
     model.load_weights()
@@ -51,6 +54,8 @@ def main():
         input_ids = [[rng.randrange(vocab) for _ in range(n)] for n in (9, 5, 22, 6)]
 
     seq_ids = list(range(len(input_ids)))
+    if args.speculative_ngram > 0:
+        return generate_speculative(model, input_ids, seq_ids, args, tokenizer)
     outputs = [model.forward(input_ids, seq_ids, [])]
     lens = [len(x) for x in input_ids]
     t0 = time.perf_counter()
@@ -62,6 +67,40 @@ def main():
     for i in seq_ids:
         toks = [step[i] for step in outputs]
         print(f"[{i}]", tokenizer.decode(toks, skip_special_tokens=True) if tokenizer else toks)
+    model.free_seqs_resources(seq_ids)
+
+
+def generate_speculative(model, input_ids, seq_ids, args, tokenizer):
+    """The same greedy streams with prompt-lookup drafts: a step feeds every sequence's last token and up to k tokens that
+    followed the most recent earlier occurrence of its last n-gram, and keeps what the model confirms (+ one token)."""
+    from swiftllm_amd.server.speculative import NgramProposer, accept
+    k = min(args.speculative_ngram, model.max_draft_tokens)
+    want = args.steps + 1
+    outs = [[t] for t in model.forward(input_ids, seq_ids, [])]
+    props = [NgramProposer(p) for p in input_ids]
+    forwards = proposed = accepted = 0
+    t0 = time.perf_counter()
+    while any(len(o) < want for o in outs):
+        live = [i for i in seq_ids if len(outs[i]) < want]
+        drafts = []
+        for i in live:
+            props[i].sync(input_ids[i], outs[i])
+            drafts.append(props[i].propose(min(k, want - len(outs[i]) - 1)))
+        ctx = [len(input_ids[i]) + len(outs[i]) - 1 for i in live]
+        if any(drafts):
+            targets = model.forward_verify([[outs[i][-1]] + d for i, d in zip(live, drafts)], live, ctx)
+        else:
+            targets = [[t] for t in model.forward([[outs[i][-1]] for i in live], live, [c + 1 for c in ctx])]
+        forwards += 1
+        for i, d, tgt in zip(live, drafts, targets):
+            a = accept(d, tgt)
+            proposed, accepted = proposed + len(d), accepted + a
+            outs[i].extend(tgt[:a + 1])
+    dt = time.perf_counter() - t0
+    print(f"{args.steps} tokens x {len(seq_ids)} sequences in {forwards} forwards ({dt / forwards * 1e3:.2f} ms each); "
+          f"drafts accepted {accepted} / {proposed} (k = {k})")
+    for i in seq_ids:
+        print(f"[{i}]", tokenizer.decode(outs[i], skip_special_tokens=True) if tokenizer else outs[i])
     model.free_seqs_resources(seq_ids)
 
 

@@ -259,6 +259,28 @@ int swl_prefill_attn_paged(void *o, const void *q, const void *k_cache, const vo
                            float softmax_scale, int64_t q_tok_stride, int64_t o_tok_stride, int32_t dtype,
                            swl_stream_t stream);
 
+/* ---- Paged attention of a speculative-decoding verify step (an addition, no reference counterpart) ----------------
+ * swl_prefill_attn_paged's semantics on the decode kernel's arithmetic: sequence s has c = ctx_lens[s] resident tokens
+ * and n = cu_seqlens[s+1] - cu_seqlens[s] new rows (its last accepted token and its drafts), 0 <= n <= 16 / G with
+ * G = H / KVH; row i attends pool keys j <= c + i. The (token, head) pairs of a kv-head ride as the 16 columns of the
+ * decode kernel's MFMA tiles, so up to 16 / G tokens cost the KV bytes of one. row_lens[r] = position + 1 of row r
+ * (int32 [num_rows]): phase 2 is swl_paged_attn_phase2 with every row as a "sequence". scratch holds
+ * swl_paged_attn_scratch_bytes(num_rows, H, D, num_seq_blocks) bytes, 16-byte aligned (unused when num_seq_blocks == 1:
+ * o is written directly). seq_block_size a multiple of 16 with seq_block_size * num_seq_blocks >= max_total_len.
+ * Slots >= c + n, foreign blocks and other layers are never read into the result (they may hold NaN / Inf).
+ * 16-bit pools only; D in {32, 64, 128}, G in {1, 2, 4, 8}, block_size == 16, max_new_len <= 16 / G, <= 65535 sequences
+ * and rows (else SWL_ERR_UNSUPPORTED). An empty batch returns SWL_OK.
+ * swl_paged_attn_verify_max_tokens: 16 / G for G in {1, 2, 4, 8}, else 0 (host only). */
+int swl_paged_attn_verify_max_tokens(int32_t num_q_heads, int32_t num_kv_heads);
+int swl_paged_attn_verify(void *o, const void *q, const void *k_cache, const void *v_cache,
+                          const int32_t *block_table, const int32_t *seq_ids, const int32_t *cu_seqlens,
+                          const int32_t *ctx_lens, const int32_t *row_lens, void *scratch, float softmax_scale,
+                          int32_t num_seqs, int32_t num_rows, int32_t max_new_len, int32_t max_total_len,
+                          int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, int32_t num_layers,
+                          int32_t block_size, int32_t cur_layer, int32_t max_blocks_per_seq, int32_t seq_block_size,
+                          int32_t num_seq_blocks, int64_t q_tok_stride, int64_t o_tok_stride, int32_t dtype,
+                          swl_stream_t stream);
+
 /* ---- FP8 (OCP e4m3fn) KV cache (an addition, no reference counterpart; opt-in: EngineConfig.kv_cache_dtype) -------
  * Storage contract (csrc/fp8_kv.h):
  *   pools    [num_blocks, L, KVH, 16, D], ONE byte per element (torch.float8_e4m3fn); a (block, layer, kv-head) tile is

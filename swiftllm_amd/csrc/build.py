@@ -20,6 +20,7 @@ SOURCES = [
     "kvcache.hip",
     "silu_mul.hip",
     "paged_attn.hip",
+    "paged_attn_verify.hip",
     "prefill_attn.hip",
     "prefill_attn_paged.hip",
     "kvcache_fp8.hip",

@@ -65,6 +65,14 @@ class EngineConfig:
     # The layer then runs qkv projection -> rotary -> quantising store -> FP8 paged attention: the slab-fed attention
     # prologue and the paths that hang on it are 16-bit only.
     kv_cache_dtype: str = "auto"
+    # Prompt-lookup speculative decoding (server/speculative.py): drafts per sequence per step, taken from the request's
+    # own prompt + output by n-gram match and verified in ONE forward (LlamaModel.forward_verify; attention:
+    # csrc/paged_attn_verify.hip). 0 (default): off — every step launches what it always did. The effective value is capped
+    # by the model (16 / (q heads per kv head) - 1 drafts: 3 at Llama-3-8B). Greedy requests, pure-decode steps, 16-bit pools.
+    speculative_ngram: int = 0
+    # ... and only for decode batches of at most this many requests: with 3 drafts, 8 x 4 = 32 rows keep every projection
+    # of the verify forward inside the weight-streaming GEMMs' range (kernels/linear.py: <= 32 tokens).
+    speculative_max_batch: int = 8
 
     # Internal switches (all on): set through `tuning`, read by the layer code as plain attributes.
     TUNING_DEFAULTS = dict(
@@ -119,6 +127,10 @@ class EngineConfig:
             raise ValueError(f"max_prefill_chunk must be >= 0 (0 = off), got {self.max_prefill_chunk}")
         if self.kv_cache_dtype not in self.KV_CACHE_DTYPES:
             raise ValueError(f"kv_cache_dtype must be one of {list(self.KV_CACHE_DTYPES)}, got {self.kv_cache_dtype!r}")
+        if int(self.speculative_ngram) < 0:
+            raise ValueError(f"speculative_ngram must be >= 0 (0 = off), got {self.speculative_ngram}")
+        if int(self.speculative_max_batch) < 0:
+            raise ValueError(f"speculative_max_batch must be >= 0, got {self.speculative_max_batch}")
         unknown = set(self.tuning or ()) - set(self.TUNING_DEFAULTS)
         if unknown:
             raise ValueError(f"unknown tuning switches {sorted(unknown)}; known: {sorted(self.TUNING_DEFAULTS)}")
@@ -127,6 +139,12 @@ class EngineConfig:
         if self.kv_cache_dtype == "fp8_e4m3" and self.decode_engine:
             raise ValueError("kv_cache_dtype='fp8_e4m3' cannot be combined with tuning={'decode_engine': True}: the "
                              "persistent one-sequence decode step reads and writes 16-bit KV pools only")
+        if int(self.speculative_ngram) > 0 and self.kv_cache_dtype == "fp8_e4m3":
+            raise ValueError("speculative_ngram > 0 cannot be combined with kv_cache_dtype='fp8_e4m3': the verify "
+                             "attention kernel reads 16-bit KV pools only")
+        if int(self.speculative_ngram) > 0 and self.decode_engine:
+            raise ValueError("speculative_ngram > 0 cannot be combined with tuning={'decode_engine': True}: a verify step "
+                             "is a multi-row forward the persistent one-sequence decode step does not run")
 
     @staticmethod
     def add_cli_args(parser: argparse.ArgumentParser):
@@ -157,5 +175,9 @@ class EngineConfig:
         g.add_argument("--no-skinny-gemm", dest="use_skinny_gemm", action="store_false")
         g.add_argument("--kv-cache-dtype", type=str, default="auto", choices=list(EngineConfig.KV_CACHE_DTYPES),
                        help="Element type of the KV pools: auto = the activation dtype, fp8_e4m3 = 1 byte per element")
+        g.add_argument("--speculative-ngram", type=int, default=0,
+                       help="Prompt-lookup speculative decoding: n-gram drafts per sequence per step (0 = off)")
+        g.add_argument("--speculative-max-batch", type=int, default=8,
+                       help="Speculate only in decode steps of at most this many requests")
         g.add_argument("--max-prefill-chunk", type=int, default=0,
                        help="Chunked prefill: prompt tokens per forward, at most (0 = off: a prompt is one forward)")

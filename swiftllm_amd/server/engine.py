@@ -26,6 +26,7 @@ from swiftllm_amd.model_config import LlamaModelConfig
 from swiftllm_amd.utils import GB
 
 from .scheduler import Scheduler
+from .speculative import NgramProposer, accept
 from .structs import RawRequest, Request, StepOutput
 from .tokenization import TokenizationEngine
 
@@ -45,6 +46,10 @@ class Engine:
         self.untokenized_raw_requests: List[Tuple[Request, RawRequest]] = []
         self.num_forwards = 0
         self.num_swapped_out = self.num_swapped_in = 0     # sequences moved to / from the host swap pool so far
+        # prompt-lookup speculative decoding (EngineConfig.speculative_ngram): effective drafts per sequence per step (set by
+        # initialize: capped by the model), verify steps run, drafts proposed and drafts accepted so far
+        self.speculative_k = 0
+        self.num_verify_steps = self.num_draft_tokens = self.num_accepted_tokens = 0
         # asyncio thread -> model thread: lists of servable requests (the scheduler is touched by the model thread only)
         self._inbox: "queue.SimpleQueue[List[Request]]" = queue.SimpleQueue()
         # model thread only: (request, token, finished) of the last step, not fanned out yet
@@ -82,6 +87,11 @@ class Engine:
         if rope is not None:     # a request that would outgrow the rotary table is refused up front (HTTP 400),
             self.scheduler.max_seq_len = int(rope.shape[0])     # not left to raise inside forward mid-flight
         self.tokenization_engine = TokenizationEngine(self.engine_config)
+        want_k = int(getattr(self.engine_config, "speculative_ngram", 0) or 0)
+        if want_k > 0:
+            self.speculative_k = max(0, min(want_k, int(getattr(self.model, "max_draft_tokens", 0) or 0)))
+            print(f"[Engine] Prompt-lookup speculative decoding: {self.speculative_k} drafts per sequence per step "
+                  f"(asked for {want_k}), decode batches of <= {self.engine_config.speculative_max_batch} greedy requests")
         if hasattr(self.model, "after_launch_hook"):
             self.model.after_launch_hook = self._post_undelivered
         self.initialized = True
@@ -201,7 +211,10 @@ class Engine:
         if swap_in:
             self.model.swap_in_seqs([r.request_id for r in swap_in])
             self.num_swapped_in += len(swap_in)
-        if batch:
+        drafts = self._propose_drafts(batch) if batch and self.speculative_k > 0 else None
+        if drafts is not None:
+            self._verify_step(batch, drafts)
+        elif batch:
             # prefill sequences first (the scheduler orders them so), their whole prompt; decoding ones
             # bring their last token and their length INCLUDING it
             # (chunked prefill: a prefill sequence brings the next `prefill_take` tokens of its prompt and the number of
@@ -242,6 +255,90 @@ class Engine:
             self._undelivered = outputs
             self.scheduler.on_batch_finish(batch)
         return True
+
+    # ---- prompt-lookup speculative decoding ------------------------------------------------------------------------
+    def _propose_drafts(self, batch: List[Request]) -> Optional[List[List[int]]]:
+        """Drafts for every request of the batch (aligned with it), or None when this step is a plain forward: a prompt
+        (chunk) in the batch, more than speculative_max_batch requests, a sampled request, or no draft at all. Drafts are
+        clipped so that the accepted tokens never pass output_len, positions never pass the rotary table or the block
+        table row, the step's rows never pass max_tokens_in_batch, and the blocks the drafts need beyond the plain step's
+        are free in the allocator right now — drafts are dropped, never swapped for."""
+        ecfg = self.engine_config
+        if (len(batch) > int(getattr(ecfg, "speculative_max_batch", 0)) or not hasattr(self.model, "forward_verify")
+                or any(not r.is_prompt_resident() or r.sampling_params is not None for r in batch)):
+            return None
+        bs = ecfg.block_size
+        limit = self.scheduler.max_seq_len
+        rows_left = ecfg.max_tokens_in_batch - len(batch)
+        mgr = getattr(self.model, "gpu_block_manager", None)
+        held = {}
+        for r in batch:
+            if mgr is not None:
+                held[id(r)] = mgr.host.num_allocated(r.request_id)
+            else:
+                held[id(r)] = -(-max(r.num_tokens() - 1, r.kv_reserved_tokens) // bs)
+        if mgr is not None:
+            free = mgr.num_free_blocks
+        else:
+            free = self.scheduler.num_gpu_blocks - sum(held.values())
+        # what the plain step takes: every request stores one token
+        spare = free - sum(max(0, -(-r.num_tokens() // bs) - held[id(r)]) for r in batch)
+        out, any_draft = [], False
+        for r in batch:
+            n = r.num_tokens()
+            k = min(self.speculative_k, r.output_len - len(r.output_token_ids) - 1, rows_left,
+                    ecfg.max_blocks_per_seq * bs - n)
+            if limit is not None:
+                k = min(k, limit - n)
+            d: List[int] = []
+            if k > 0:
+                prop = r.ngram_proposer
+                if prop is None:
+                    prop = r.ngram_proposer = NgramProposer()
+                prop.sync(r.prompt_token_ids, r.output_token_ids)
+                d = prop.propose(k)
+            if d:
+                base = max(held[id(r)], -(-n // bs))
+                extra = -(-(n + len(d)) // bs) - base
+                if extra > max(spare, 0):       # keep the drafts that fit the blocks the request has (or will take anyway)
+                    d = d[:max(0, (base + max(spare, 0)) * bs - n)]
+                    extra = max(0, -(-(n + len(d)) // bs) - base)
+                spare -= max(extra, 0)
+                rows_left -= len(d)
+                any_draft = any_draft or bool(d)
+            out.append(d)
+        return out if any_draft else None
+
+    def _verify_step(self, batch: List[Request], drafts: List[List[int]]):
+        """One verify forward for a pure-decode batch: every request brings its last token and its drafts (requests
+        without a draft ride with one row), keeps the accepted prefix plus the token after it, and every token is
+        delivered in order as its own StepOutput."""
+        input_ids = [[r.output_token_ids[-1]] + d for r, d in zip(batch, drafts)]
+        seq_ids = [r.request_id for r in batch]
+        ctx_lens = [r.num_tokens() - 1 for r in batch]
+        try:
+            targets = self.model.forward_verify(input_ids, seq_ids, ctx_lens)
+        finally:
+            self._post_undelivered()
+        self.num_forwards += 1
+        self.num_verify_steps += 1
+        outputs, finished = [], []
+        for req, d, tgt, ctx in zip(batch, drafts, targets, ctx_lens):
+            a = accept(d, tgt)
+            self.num_draft_tokens += len(d)
+            self.num_accepted_tokens += a
+            req.kv_reserved_tokens = max(req.kv_reserved_tokens, ctx + 1 + len(d))
+            for tok in tgt[:a + 1]:
+                if req.is_finished():
+                    break
+                req.output_token_ids.append(tok)
+                outputs.append((req, tok, req.is_finished()))
+            if req.is_finished():
+                finished.append(req.request_id)
+        if finished:
+            self.model.free_seqs_resources(finished)
+        self._undelivered = outputs
+        self.scheduler.on_batch_finish(batch)
 
     def _model_loop(self, failed: "asyncio.Future"):
         # Garbage collection around the latency-critical section (EngineConfig tuning `pause_gc_while_serving`): a

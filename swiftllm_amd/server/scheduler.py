@@ -59,12 +59,14 @@ class Scheduler:
 
     # ---- budgets -------------------------------------------------------------------------------------
     def _blocks(self, req: Request, extra_tokens: int = 0) -> int:
-        return cdiv(req.num_tokens() + extra_tokens, self.engine_config.block_size)
+        # (kv_reserved_tokens: what a speculative verify step allocated for drafts, accepted or not; 0 with the option off)
+        return cdiv(max(req.num_tokens() + extra_tokens, req.kv_reserved_tokens), self.engine_config.block_size)
 
     def _running_blocks(self) -> int:
         # (once per decode iteration over the whole running set: spelled out, no per-request method calls)
         bs = self.engine_config.block_size
-        return sum((r.prompt_len + len(r.output_token_ids) + bs - 1) // bs for r in self.running_q)
+        return sum((max(r.prompt_len + len(r.output_token_ids), r.kv_reserved_tokens) + bs - 1) // bs
+                   for r in self.running_q)
 
     # ---- events --------------------------------------------------------------------------------------
     def why_unservable(self, req: Request) -> Optional[str]:

@@ -48,6 +48,13 @@ class Request:
         # gave this request in the step being built (0: not a prompt chunk / the whole rest of the prompt)
         self.num_prefilled = 0
         self.prefill_take = 0
+        # speculative decoding: high-water mark of the tokens this request holds KV blocks for. A verify step stores its
+        # drafts' K/V too; the blocks rejected drafts claimed stay with the request, and the scheduler counts them
+        # (max(num_tokens, kv_reserved_tokens)). 0 = never verified: the arithmetic of always.
+        self.kv_reserved_tokens = 0
+        # ... and its prompt-lookup index (server/speculative.py: NgramProposer), built by the engine the first time the
+        # request is a candidate for a verify step; None = never was
+        self.ngram_proposer = None
 
     def is_finished(self) -> bool:
         return len(self.output_token_ids) >= self.output_len

@@ -68,6 +68,9 @@ class BatchPlan:
     # starts at position 0 (no segment is packed then: the layout is what it always was)
     prefill_ctx_lens: Optional[np.ndarray] = None
     max_prefill_total_len: int = 0      # max over prefill sequences of context + new tokens
+    # speculative-decoding verify step (worker/model.py: forward_verify): position + 1 of every row (int32 [T]) — the key
+    # count the flash-decoding merge of that row covers. None = not a verify step: no segment is packed
+    verify_row_lens: Optional[np.ndarray] = None
 
     @property
     def real_seqs(self) -> int:
@@ -89,6 +92,9 @@ class BatchPlan:
         if self.prefill_ctx_lens is not None:       # appended: every offset above is the one of a plan without contexts
             out.append(("prefill_ctx_lens", off, self.prefill_ctx_lens.size))
             off += (self.prefill_ctx_lens.size + 3) // 4 * 4
+        if self.verify_row_lens is not None:
+            out.append(("verify_row_lens", off, self.verify_row_lens.size))
+            off += (self.verify_row_lens.size + 3) // 4 * 4
         return out, off
 
     def pack_into(self, buf: np.ndarray) -> int:
@@ -154,3 +160,17 @@ def plan_batch(input_ids_list: Sequence[Sequence[int]], seq_ids_list: Sequence[i
         seq_lengths=np.asarray(seq_lengths_list, dtype=np.int32), prefill_seq_lens=pl,
         prefill_start_locs_with_end=starts_with_end, decoding_seq_lens=dl, position_indices=pos,
         last_token_indices=last)
+
+
+def plan_verify(input_ids_list: Sequence[Sequence[int]], seq_ids_list: Sequence[int], ctx_lens: Sequence[int],
+                num_kv_heads: int, num_slots: int = 256) -> BatchPlan:
+    """Plan of a speculative-decoding verify step: the chunked-prefill plan of the same arguments (every sequence brings
+    its last accepted token and its drafts behind `ctx_lens` resident tokens) with three differences — every row is a
+    "last token" (the model returns the token after each of them), the flash-decoding split is chosen over the total
+    lengths (the rows attend with the decode kernel's geometry), and `verify_row_lens` is packed."""
+    plan = plan_batch(input_ids_list, seq_ids_list, [], num_kv_heads, num_slots, prefill_ctx_lens=ctx_lens)
+    plan.last_token_indices = np.arange(plan.num_tokens, dtype=np.int32)
+    plan.verify_row_lens = (plan.position_indices + 1).astype(np.int32)
+    plan.seq_block_size = select_seq_block_size(plan.seq_lengths_list, num_kv_heads, num_slots)
+    plan.num_seq_blocks = -(-plan.max_prefill_total_len // plan.seq_block_size)
+    return plan

@@ -40,6 +40,10 @@ class BlockAllocatorHost:
         self.is_free = np.ones(num_blocks, dtype=bool)
         self.seq_blocks = {}        # seq_id -> list[int] of block ids, in logical order
         self._lowest_maybe_free = 0  # every index below this is known to be in use
+        # speculative decoding: sequences that took a verify step (LlamaModel.forward_verify adds them) may own a block
+        # more than their length needs — the one their rejected drafts claimed — until they are released. For every other
+        # sequence that stays a logic error
+        self.surplus_ok = set()
 
     def num_allocated(self, seq_id: int) -> int:
         blocks = self.seq_blocks.get(seq_id)
@@ -55,6 +59,9 @@ class BlockAllocatorHost:
                 raise RuntimeError(f"sequence id {sid} outside the block table (0..{self.max_seqs - 1})")
             target = -(-int(tlen) // bs)
             have = self.num_allocated(sid)
+            if have > target and sid in self.surplus_ok:
+                needed[i] = 0
+                continue
             if have > target:
                 raise AssertionError(
                     f"(On {self.device_name}) Logic error: sequence {sid} already owns {have} blocks, "
@@ -101,6 +108,7 @@ class BlockAllocatorHost:
         freed: List[int] = []
         for sid in seq_ids:
             blocks = self.seq_blocks.pop(sid, None)
+            self.surplus_ok.discard(sid)
             if blocks:
                 freed.extend(blocks)
         if freed:

@@ -57,3 +57,8 @@ class LlamaInferState:
     # reciprocals (what the quantising stores multiply by). None with 16-bit pools.
     kv_scales: Optional[torch.Tensor] = None
     kv_inv_scales: Optional[torch.Tensor] = None
+    # Speculative-decoding verify step (LlamaModel.forward_verify): the "prefill" sequences bring their last accepted token
+    # and drafts, attention is kernels/paged_attn.paged_attention_verify with seq_block_size / num_seq_blocks taken over
+    # the total lengths, and verify_row_lens (int32 [num_tokens]) is position + 1 of every row.
+    verify: bool = False
+    verify_row_lens: Optional[torch.Tensor] = None

@@ -110,3 +110,48 @@ def paged_attention_from_qkv_splitk(partials, k_cache: torch.Tensor, v_cache: to
               infer_state.softmax_scale, nd, h, kvh, d, model_config.num_layers, engine_config.block_size,
               cur_layer, block_table.shape[1], infer_state.seq_block_size, nsb, token_stride(o, "o"),
               _hip.dtype_code(o.dtype), _hip.stream())
+
+
+def verify_max_tokens(model_config) -> int:
+    """Tokens per sequence one verify step takes (its last accepted token + drafts): 16 / G for G = H / KVH in
+    {1, 2, 4, 8}, else 0 (host arithmetic of the library, no device)."""
+    return int(_hip.load().swl_paged_attn_verify_max_tokens(model_config.num_q_heads, model_config.num_kv_heads))
+
+
+def paged_attention_verify(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
+                           o: torch.Tensor, model_config, engine_config, infer_state, cur_layer: int):
+    """Attention of a speculative-decoding verify step (no reference counterpart; csrc/paged_attn_verify.hip): sequence s
+    has `infer_state.prefill_ctx_lens[s]` tokens resident and brings 1..16/G new rows whose K/V were stored behind them on
+    this stream; row i attends pool keys up to its own position. Flash-decoding geometry: `infer_state.seq_block_size /
+    num_seq_blocks` over the total lengths, `infer_state.verify_row_lens` (position + 1 of every row) for phase 2.
+    q/o are [rows, heads, head_dim]. 16-bit pools only."""
+    _hip.require_gpu_tensor(q, "q")
+    st = infer_state
+    if st.num_prefill_seqs == 0:
+        return
+    cu, ctx, row_lens = st.prefill_seq_start_locs_with_end, st.prefill_ctx_lens, st.verify_row_lens
+    rows = st.num_prefill_tokens
+    h, d = model_config.num_q_heads, model_config.head_dim
+    assert cu.dtype == torch.int32 and cu.is_contiguous() and cu.numel() == st.num_prefill_seqs + 1
+    assert ctx is not None and ctx.dtype == torch.int32 and ctx.is_contiguous() and ctx.numel() == st.num_prefill_seqs
+    assert row_lens is not None and row_lens.dtype == torch.int32 and row_lens.is_contiguous() and row_lens.numel() == rows
+    assert k_cache.is_contiguous() and v_cache.is_contiguous() and block_table.is_contiguous()
+    if k_cache.dtype == torch.float8_e4m3fn:
+        raise _hip.HipLibraryError("paged_attention_verify serves 16-bit KV pools only (no FP8 instantiation)")
+    assert q.dtype == o.dtype == k_cache.dtype == v_cache.dtype
+    assert st.seq_block_size % engine_config.block_size == 0
+    if o.dim() == 2:
+        o = o.view(o.shape[0], h, d)
+    nsb = st.num_seq_blocks
+    scratch = None
+    if nsb > 1:
+        need = _hip.scratch_bytes(rows, h, d, nsb)
+        scratch = getattr(st, "paged_attn_scratch", None)
+        if scratch is None or scratch.numel() * scratch.element_size() < need:
+            scratch = torch.empty(need // 4, dtype=torch.float32, device=q.device)
+    _hip.call("swl_paged_attn_verify", _hip.ptr(o), _hip.ptr(q), _hip.ptr(k_cache), _hip.ptr(v_cache),
+              _hip.ptr(block_table), _hip.ptr(st.seq_ids), _hip.ptr(cu), _hip.ptr(ctx), _hip.ptr(row_lens),
+              _hip.ptr(scratch), st.softmax_scale, st.num_prefill_seqs, rows, st.max_prefill_len,
+              st.max_prefill_total_len, h, model_config.num_kv_heads, d, model_config.num_layers,
+              engine_config.block_size, cur_layer, block_table.shape[1], st.seq_block_size, nsb,
+              token_stride(q, "q"), token_stride(o, "o"), _hip.dtype_code(q.dtype), _hip.stream())

@@ -51,7 +51,7 @@ from ..kernels.rotary_emb import (rotary_embedding_inplace, rotary_embedding_and
                                   rotary_embedding_and_store_kvcache_prefill)
 from ..kernels.kvcache_mgmt import store_kvcache
 from ..kernels.prefill_attn import prefill_attention, prefill_attention_paged
-from ..kernels.paged_attn import paged_attention, paged_attention_from_qkv_splitk
+from ..kernels.paged_attn import paged_attention, paged_attention_from_qkv_splitk, paged_attention_verify
 from ..kernels.silu_and_mul import silu_and_mul_inplace
 
 
@@ -300,7 +300,11 @@ class LlamaTransformerLayer:
     def _prefill_attention(self, q, k, v, o, k_cache, v_cache, block_table, st):
         """Whole prompts attend to their fresh projections; prompt chunks behind a resident context (chunked prefill:
         st.prefill_ctx_lens) attend to the pool, which the store above has just extended by the chunk."""
-        if getattr(st, "prefill_ctx_lens", None) is not None:
+        if getattr(st, "verify", False):    # speculative decoding: the rows of a verify step, decode-kernel geometry
+            assert not st.ignore_kvcache and st.prefill_ctx_lens is not None
+            paged_attention_verify(q, k_cache, v_cache, block_table, o, self.model_config, self.engine_config, st,
+                                   self.layer_id)
+        elif getattr(st, "prefill_ctx_lens", None) is not None:
             assert not st.ignore_kvcache
             prefill_attention_paged(q, k_cache, v_cache, block_table, o, self.model_config, self.engine_config, st,
                                     self.layer_id)

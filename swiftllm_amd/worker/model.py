@@ -32,12 +32,13 @@ from swiftllm_amd.model_config import LlamaModelConfig
 from swiftllm_amd.sampling_params import SamplingParams, is_greedy
 from swiftllm_amd.utils import GB
 
-from .batch_plan import BatchPlan, plan_batch
+from .batch_plan import BatchPlan, plan_batch, plan_verify
 from .block_manager import BlockManager
 from . import decode_engine as _decode_engine
 from .infer_state import LlamaInferState
 from .kernels.block_swapping import swap_blocks
 from .kernels.linear import RawResidual
+from .kernels.paged_attn import verify_max_tokens
 from .kernels.rmsnorm import fused_add_rmsnorm_from_splitk, rmsnorm_inplace
 from .kernels.sampling import device_args, pack_params
 from .layers.pre_layer import LlamaPreLayer
@@ -120,6 +121,9 @@ class LlamaModel:
         # per-row sampling parameters of a sampled step: pinned staging + its device twin (fixed address: a sampled
         # hipGraph reads it on every replay), laid out by kernels/sampling.pack_params; one H2D copy per sampled step
         self._sample_host = self._sample_host_np = self._sample_dev = self._sample_done = None
+        # speculative decoding: drafts one verify step takes per sequence (forward_verify) = the verify attention kernel's
+        # tokens per sequence (16 / G) minus the last accepted token that leads them; 0 with FP8 pools (no instantiation)
+        self.max_draft_tokens = 0 if self.kv_fp8 else max(0, verify_max_tokens(self.model_config) - 1)
 
     # ------------------------------------------------------------------------------------------------
     @torch.inference_mode()
@@ -439,7 +443,8 @@ class LlamaModel:
             paged_attn_scratch=self._scratch if nsb > 1 else None,
             sampling=device_args(self._sample_dev, dev["seq_lengths"]) if sampled else None,
             prefill_ctx_lens=dev.get("prefill_ctx_lens"), max_prefill_total_len=plan.max_prefill_total_len,
-            kv_scales=self.kv_scales, kv_inv_scales=self.kv_inv_scales)
+            kv_scales=self.kv_scales, kv_inv_scales=self.kv_inv_scales,
+            verify=plan.verify_row_lens is not None, verify_row_lens=dev.get("verify_row_lens"))
 
     @torch.inference_mode()
     def _forward(self, input_ids: torch.Tensor, infer_state: LlamaInferState) -> torch.Tensor:
@@ -811,6 +816,63 @@ class LlamaModel:
             prof[name] = prof.get(name, 0.0) + dt
         return out
 
+    @torch.inference_mode()
+    def forward_verify(self, input_ids_list: List[List[int]], seq_ids_list: List[int],
+                       ctx_lens: List[int]) -> List[List[int]]:
+        """One speculative-decoding verify step (greedy; no reference counterpart). Sequence s has `ctx_lens[s]` tokens
+        resident in the KV pool and brings `input_ids_list[s]`: its last accepted token followed by its drafts,
+        1 .. max_draft_tokens + 1 tokens. Returns, per sequence, the greedy token after EVERY one of its inputs: the
+        caller keeps the longest prefix of drafts that equal the tokens before them (server/speculative.py: accept).
+        All inputs' K/V are stored at positions [ctx, ctx + n); what a rejected draft wrote lies past the sequence's
+        length afterwards, where every kernel masks it and the next step overwrites it.
+
+        It is the chunked-prefill forward of the same arguments with three differences: the infer state is marked
+        `verify`, attention is kernels/paged_attn.paged_attention_verify (the decode kernel's geometry, split over the
+        total lengths), and every row is a last token. Eager launches, no hipGraph."""
+        if len(input_ids_list) == 0:
+            return []
+        _require_hip_device()
+        if len(seq_ids_list) != len(input_ids_list) or len(ctx_lens) != len(input_ids_list):
+            raise ValueError("forward_verify needs one sequence id and one context length per sequence")
+        limit = self.max_draft_tokens + 1
+        if self.kv_fp8 or self.max_draft_tokens <= 0:
+            raise RuntimeError("forward_verify is not available for this model: FP8 KV pools, or a q-head / kv-head ratio "
+                               "the verify attention kernel does not take (G in {1, 2, 4, 8})")
+        for sid, ids in zip(seq_ids_list, input_ids_list):
+            if len(ids) == 0:
+                raise ValueError(f"sequence {sid}: an empty token list (a verify step brings at least the last accepted "
+                                 "token)")
+            if len(ids) > limit:
+                raise ValueError(f"sequence {sid}: {len(ids)} tokens, a verify step takes at most {limit} "
+                                 f"(max_draft_tokens = {self.max_draft_tokens})")
+        if self.gpu_block_manager is None or self.k_cache is None:
+            raise RuntimeError("forward_verify before init_kvcache_and_swap: there is no KV pool to verify against")
+        ctx = [int(c) for c in ctx_lens]
+        self._check_prefill_ctx(input_ids_list, seq_ids_list, [], False, ctx)     # (all-zero contexts pass: None)
+        self._lookahead = None      # a prepared decode step does not survive a verify step
+        self.gpu_block_manager.host.surplus_ok.update(seq_ids_list)     # rejected drafts leave their block with the sequence
+        plan = plan_verify(input_ids_list, seq_ids_list, ctx, self.model_config.num_kv_heads, self._num_slots)
+        plan.num_real_seqs = len(input_ids_list)
+        self.gpu_block_manager.allocate_blocks_for_seqs(seq_ids_list, plan.seq_lengths_list)
+        dev = self._upload_plan(plan)
+        nsb = plan.num_seq_blocks
+        if nsb > 1:
+            need = _hip.scratch_bytes(plan.num_tokens, self.model_config.num_q_heads, self.model_config.head_dim, nsb) // 4
+            if self._scratch is None or self._scratch.numel() < need:
+                self._scratch = torch.empty(need, dtype=torch.float32, device=self.device)
+                self._drop_decode_graphs()
+        state = self._make_infer_state(plan, dev, False)
+        state.paged_attn_scratch = self._scratch if nsb > 1 else None
+        tokens = self._forward(dev["input_ids"], state)
+        if self.after_launch_hook is not None:
+            self.after_launch_hook()
+        flat = tokens.tolist()
+        out, at = [], 0
+        for ids in input_ids_list:
+            out.append(flat[at:at + len(ids)])
+            at += len(ids)
+        return out
+
     def host_profile(self, reset: bool = True) -> dict:
         """Mean host seconds per forward() call by section (SWL_HOST_PROFILE=1), {} when profiling is off."""
         prof = self._host_prof or {}
@@ -831,7 +893,9 @@ class LlamaModel:
         dst_mgr = self.gpu_block_manager if is_swap_in else self.cpu_block_manager
         counts = src_mgr.get_num_allocated_blocks_host(seq_ids_list)
         src_ids = [b for s in seq_ids_list for b in src_mgr.get_block_ids_host(s)]
+        surplus = [s for s in seq_ids_list if s in src_mgr.host.surplus_ok]    # (a block of rejected drafts moves with its owner)
         src_mgr.gather_allocated_blocks_and_free(seq_ids_list)
+        dst_mgr.host.surplus_ok.update(surplus)
         dst_mgr.allocate_blocks_for_seqs(seq_ids_list, [c * self.engine_config.block_size for c in counts])
         dst_ids = [b for s in seq_ids_list for b in dst_mgr.get_block_ids_host(s)]
         swap_blocks(src_ids, dst_ids, is_swap_in, self.k_cache, self.v_cache, self.k_swap, self.v_swap)
