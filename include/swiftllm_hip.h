@@ -184,6 +184,22 @@ int swl_sample(int64_t *out, const void *x, int64_t num_rows, int32_t n, int64_t
                const float *temperature, const int32_t *top_k, const float *top_p, const uint32_t *seed,
                const int32_t *pos, swl_stream_t stream);
 
+/* ---- Logits adjustment (penalties / logit bias / min-p), in place, before swl_argmax / swl_sample ------------
+ * reference: none (post_layer.py:40 takes the argmax of the raw logits); this is an addition.
+ * Row r of x[num_rows, n] (row stride row_stride elements, any n >= 1) owns the entries
+ * e in [edit_offsets[r], edit_offsets[r + 1]) of edit_ids / edit_meta / edit_bias (each id at most once per row) and
+ * row_params[r][0..3] = repetition penalty, presence penalty, frequency penalty, min-p gap. Per entry, in fp32, one IEEE
+ * operation per step: f = x[id]; if ((count > 0 || in_prompt) && rep != 1) f = f > 0 ? f / rep : f * rep;
+ * f -= freq * count; if (count > 0) f -= pres; f += bias; x[id] = round-to-nearest-even(f), with count = meta bits 0..30
+ * (occurrences among the output tokens) and in_prompt = meta bit 31. An id outside [0, n) is skipped. Then, when
+ * gap > -inf (gap = fp32(T * ln(min_p)), computed by the host), every element with x_i - max(x) < gap becomes -inf; NaN
+ * elements are left alone. A row with no entries and gap == -inf is not touched. No scratch, no atomics: bit-reproducible.
+ * x needs 2-byte alignment (16-byte accesses are used when x is 16-byte aligned and row_stride % 8 == 0), the index and
+ * parameter arrays 4 bytes. The exact contract is in csrc/logits_adjust.hip. num_rows > 2^31 - 1: SWL_ERR_UNSUPPORTED. */
+int swl_logits_adjust(void *x, int64_t num_rows, int32_t n, int64_t row_stride, int32_t dtype,
+                      const int32_t *edit_offsets, const int32_t *edit_ids, const int32_t *edit_meta,
+                      const float *edit_bias, const float *row_params, swl_stream_t stream);
+
 /* ---- Paged attention, decode (flash-decoding, "paged attention v2") --------------------------
  * reference: paged_attn.py:9-108 (phase 1), :111-149 (phase 2), launcher :152-222
  * q[Bd, H, D] (token stride q_tok_stride), o[Bd, H, D] (token stride o_tok_stride).

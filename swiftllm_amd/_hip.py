@@ -135,6 +135,8 @@ _SPECIAL = {
     "swl_paged_attn_verify_max_tokens": ([_I32, _I32], _I32),
     "swl_paged_attn_verify": ([_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F32, _I32, _I32, _I32, _I32, _I32, _I32, _I32,
                                _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I64, _I32, _P], _I32),
+    # Logits adjustment (csrc/logits_adjust.hip): an "int rc = f(...)" entry too, registered here for the same reason.
+    "swl_logits_adjust": ([_P, _I64, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P], _I32),
 }
 
 _lock = threading.Lock()

@@ -33,6 +33,7 @@ SOURCES = [
     "gemm_rows.hip",
     "argmax.hip",
     "sampling.hip",
+    "logits_adjust.hip",
     "decode_engine.hip",
 ]
 HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "fp8_kv.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]

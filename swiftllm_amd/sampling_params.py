@@ -4,11 +4,18 @@ The reference samples greedily only (swiftllm/worker/layers/post_layer.py:40); g
 sampled request draws from softmax(logits / temperature), optionally restricted to the `top_k` largest logits and
 then to the smallest nucleus holding `top_p` of the remaining mass. The draw is seeded: the same (seed, position)
 gives the same token whatever batch, row, graph bucket or replica serves it (csrc/sampling.hip has the contract).
+
+Before the token is picked, greedily or not, the logits can be edited (csrc/logits_adjust.hip has the contract): a
+repetition penalty (tokens seen in the prompt or the output: positive logits divided, the others multiplied), a presence
+and a frequency penalty (output tokens only), an additive `logit_bias` per token id, and `min_p` (tokens whose
+probability is below `min_p` times the largest one are removed before top-k / top-p act). `stop_token_ids` end the
+request at the first of them (delivered as its last token); while fewer than `min_tokens` tokens have been generated the
+stop tokens cannot be picked.
 """
 import dataclasses
 import math
 import secrets
-from typing import Optional
+from typing import Optional, Tuple
 
 
 @dataclasses.dataclass(frozen=True)
@@ -17,8 +24,62 @@ class SamplingParams:
     top_k: int = 0              # 0: off
     top_p: float = 1.0          # 1: off
     seed: Optional[int] = None  # None: a fresh 64-bit seed is drawn when the request (or forward call) takes it
+    repetition_penalty: float = 1.0     # 1: off
+    presence_penalty: float = 0.0       # 0: off
+    frequency_penalty: float = 0.0      # 0: off
+    min_p: float = 0.0                  # 0: off
+    logit_bias: Optional[Tuple[Tuple[int, float], ...]] = None  # a mapping / pairs id -> bias; stored as sorted pairs
+    stop_token_ids: Tuple[int, ...] = ()
+    min_tokens: int = 0                 # stop tokens are banned while fewer output tokens exist
 
     def __post_init__(self):
+        self._check_sampling()
+        self._check_processing()
+
+    def _check_processing(self):
+        def number(v):
+            return not isinstance(v, bool) and isinstance(v, (int, float))
+        r = self.repetition_penalty
+        if not number(r) or not math.isfinite(r) or r <= 0:
+            raise ValueError(f"repetition_penalty must be a finite number > 0, got {r!r}")
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = getattr(self, name)
+            if not number(v) or not math.isfinite(v):
+                raise ValueError(f"{name} must be a finite number, got {v!r}")
+        p = self.min_p
+        if not number(p) or not 0.0 <= p < 1.0:
+            raise ValueError(f"min_p must be a number in [0, 1), got {p!r}")
+        bias = self.logit_bias
+        if bias is not None:
+            try:
+                pairs = list(bias.items()) if hasattr(bias, "items") else [tuple(kv) for kv in bias]
+            except TypeError:
+                raise ValueError(f"logit_bias must be a mapping or pairs of id -> bias, got {bias!r}") from None
+            out = {}
+            for kv in pairs:
+                if len(kv) != 2:
+                    raise ValueError(f"logit_bias entries are (id, bias) pairs, got {kv!r}")
+                tok, b = kv
+                if isinstance(tok, bool) or not isinstance(tok, int) or not 0 <= tok < 2 ** 31:
+                    raise ValueError(f"logit_bias ids must be integers in [0, 2**31), got {tok!r}")
+                if not number(b) or math.isnan(b) or b == math.inf:
+                    raise ValueError(f"logit_bias values must be finite or -inf, got {b!r}")
+                if tok in out:
+                    raise ValueError(f"logit_bias names id {tok} twice")
+                out[tok] = float(b)
+            object.__setattr__(self, "logit_bias", tuple(sorted(out.items())) or None)
+        stops = self.stop_token_ids
+        if isinstance(stops, (str, bytes)) or not hasattr(stops, "__iter__"):
+            raise ValueError(f"stop_token_ids must be a sequence of integers, got {stops!r}")
+        stops = tuple(stops)
+        if any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 31 for t in stops):
+            raise ValueError(f"stop_token_ids must be integers in [0, 2**31), got {stops!r}")
+        object.__setattr__(self, "stop_token_ids", stops)
+        n = self.min_tokens
+        if isinstance(n, bool) or not isinstance(n, int) or n < 0:
+            raise ValueError(f"min_tokens must be an integer >= 0, got {n!r}")
+
+    def _check_sampling(self):
         t = self.temperature
         if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) or t < 0:
             raise ValueError(f"temperature must be a finite number >= 0, got {t!r}")
@@ -35,6 +96,29 @@ class SamplingParams:
     @property
     def greedy(self) -> bool:
         return self.temperature == 0
+
+    @property
+    def penalised(self) -> bool:
+        """Some penalty is on: the row's entries include the tokens of its sequence."""
+        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+
+    @property
+    def processes_logits(self) -> bool:
+        """The logits of this request are edited before its token is picked (by a step, or by some step)."""
+        return (self.penalised or self.min_p != 0.0 or self.logit_bias is not None
+                or (self.min_tokens > 0 and bool(self.stop_token_ids)))
+
+    @property
+    def plain(self) -> bool:
+        """Nothing to do beyond the argmax of the raw logits, run to output_len: what None means."""
+        return self.greedy and not self.processes_logits and not self.stop_token_ids
+
+    def min_p_gap(self) -> float:
+        """What the kernel compares x_i - max(x) with: T * ln(min_p), computed in double precision (the caller rounds it
+        to fp32); -inf when min-p is off or the row is greedy (T == 0: the argmax survives any min_p)."""
+        if self.min_p <= 0.0 or self.temperature <= 0.0:
+            return -math.inf
+        return float(self.temperature) * math.log(self.min_p)
 
     def with_seed(self) -> "SamplingParams":
         """These parameters with a concrete seed (a fresh one drawn when `seed` is None)."""

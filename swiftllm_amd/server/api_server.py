@@ -4,7 +4,8 @@
 
 `POST /generate` with JSON {prompt | prompt_token_ids, output_len, stream?, decode?} — the request
 format of the reference's swiftllm/server/api_server.py:16-84, plus optional sampling fields (temperature,
-top_k, top_p, seed; absent = greedy, as in the reference): non-streaming answers
+top_k, top_p, seed; repetition_penalty, presence_penalty, frequency_penalty, min_p, logit_bias = {"id": bias},
+stop_token_ids, min_tokens; absent = greedy to output_len, as in the reference): non-streaming answers
 {"output_token_ids": [...]} (or {"output": text} with decode), streaming sends one line per token.
 `GET /load` reports outstanding tokens (used by the replica router). Any engine failure takes the
 process down (reference api_server.py:114-119) so a supervisor can restart the replica.
@@ -51,28 +52,82 @@ def _is_int(v) -> bool:
     return isinstance(v, int) and not isinstance(v, bool)
 
 
+def _is_finite_number(v) -> bool:
+    """An int or a float that is finite AS A FLOAT (a JSON integer of hundreds of digits is not: float() overflows)."""
+    if not (_is_int(v) or isinstance(v, float)):
+        return False
+    try:
+        return math.isfinite(v)
+    except OverflowError:
+        return False
+
+
 def _validate_sampling(body) -> "str | None":
     t = body.get("temperature")
-    if t is not None and (not (_is_int(t) or isinstance(t, float)) or not math.isfinite(t) or t < 0):
+    if t is not None and (not _is_finite_number(t) or t < 0):
         return "temperature must be a finite number >= 0"
     k = body.get("top_k")
     if k is not None and (not _is_int(k) or k < 0 or k >= 2 ** 31):
         return "top_k must be an integer >= 0"
     p = body.get("top_p")
-    if p is not None and (not (_is_int(p) or isinstance(p, float)) or not 0 < p <= 1):
+    if p is not None and (not _is_finite_number(p) or not 0 < p <= 1):
         return "top_p must be a number in (0, 1]"
     s = body.get("seed")
     if s is not None and (not _is_int(s) or not 0 <= s < 2 ** 64):
         return "seed must be an integer in [0, 2**64)"
+
+    number = _is_finite_number
+    r = body.get("repetition_penalty")
+    if r is not None and (not number(r) or r <= 0):
+        return "repetition_penalty must be a finite number > 0"
+    for name in ("presence_penalty", "frequency_penalty"):
+        v = body.get(name)
+        if v is not None and not number(v):
+            return f"{name} must be a finite number"
+    m = body.get("min_p")
+    if m is not None and (not number(m) or not 0 <= m < 1):
+        return "min_p must be a number in [0, 1)"
+    bias = body.get("logit_bias")
+    if bias is not None:
+        if not isinstance(bias, dict):
+            return "logit_bias must be an object of token id -> bias"
+        for key, v in bias.items():
+            # (the length first: int() refuses strings of thousands of digits with a ValueError of its own)
+            if not (isinstance(key, str) and 0 < len(key) <= 10 and key.isascii() and key.isdigit() and int(key) < 2 ** 31):
+                return "logit_bias keys must be decimal token ids"
+            if not number(v):
+                return "logit_bias values must be finite numbers"
+        if len({int(key) for key in bias}) != len(bias):
+            return "logit_bias names a token id twice"
+    stops = body.get("stop_token_ids")
+    if stops is not None and (not isinstance(stops, list) or not all(_is_int(t) and 0 <= t < 2 ** 31 for t in stops)):
+        return "stop_token_ids must be a list of integers >= 0"
+    n = body.get("min_tokens")
+    if n is not None and (not _is_int(n) or n < 0):
+        return "min_tokens must be an integer >= 0"
     return None
 
 
+_SAMPLING_FIELDS = ("temperature", "top_k", "top_p", "seed")
+_PROCESSING_FIELDS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "min_p", "logit_bias",
+                      "stop_token_ids", "min_tokens")
+
+
 def _sampling_params(body) -> "SamplingParams | None":
-    if all(body.get(f) is None for f in ("temperature", "top_k", "top_p", "seed")):
+    if all(body.get(f) is None for f in _SAMPLING_FIELDS + _PROCESSING_FIELDS):
         return None
+    kw = {}
+    if any(body.get(f) is not None for f in _PROCESSING_FIELDS):       # (none of them: the params of always)
+        def num(name, default):
+            return float(body[name]) if body.get(name) is not None else default
+        bias = body.get("logit_bias")
+        kw = dict(repetition_penalty=num("repetition_penalty", 1.0), presence_penalty=num("presence_penalty", 0.0),
+                  frequency_penalty=num("frequency_penalty", 0.0), min_p=num("min_p", 0.0),
+                  logit_bias={int(k): float(v) for k, v in bias.items()} if bias else None,
+                  stop_token_ids=tuple(body.get("stop_token_ids") or ()), min_tokens=int(body.get("min_tokens") or 0))
     return SamplingParams(temperature=float(body.get("temperature") or 0.0), top_k=int(body.get("top_k") or 0),
                           top_p=float(body.get("top_p") if body.get("top_p") is not None else 1.0),
-                          seed=body.get("seed"))
+                          seed=body.get("seed"), **kw)
 
 
 def build_app(engine: Engine) -> fastapi.FastAPI:

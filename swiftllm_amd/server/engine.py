@@ -110,13 +110,14 @@ class Engine:
         return request
 
     async def add_request_and_stream(self, raw_request: RawRequest) -> AsyncGenerator[StepOutput, None]:
-        """Yield a StepOutput per generated token. (Ends after `output_len` deliveries, not on
-        `request.is_finished()`: the request's own token list runs one step ahead of what has been fanned out.)"""
+        """Yield a StepOutput per generated token. (Ends after `output_len` deliveries, or at the None that follows the
+        last token of a request a stop token ended early — not on `request.is_finished()`: the request's own token list
+        runs one step ahead of what has been fanned out.)"""
         request = self._enqueue(raw_request)
         delivered = 0
         while True:
             step_output = await request.output_q.get()
-            if step_output is None:     # rejected (request.error says why)
+            if step_output is None:     # rejected (request.error says why), or ended early by a stop token
                 break
             yield step_output
             request.output_q.task_done()
@@ -163,6 +164,8 @@ class Engine:
             if finished:
                 self._live.discard(req)
                 req.finished_event.set()
+                if len(req.output_token_ids) < req.output_len:      # a stop token ended it: streams do not wait for more
+                    req.output_q.put_nowait(None)
 
     def _fail_live(self, why: str):
         """The model thread is gone: wake every caller still waiting (event-loop thread). `add_request_and_wait` returns
@@ -259,7 +262,8 @@ class Engine:
     # ---- prompt-lookup speculative decoding ------------------------------------------------------------------------
     def _propose_drafts(self, batch: List[Request]) -> Optional[List[List[int]]]:
         """Drafts for every request of the batch (aligned with it), or None when this step is a plain forward: a prompt
-        (chunk) in the batch, more than speculative_max_batch requests, a sampled request, or no draft at all. Drafts are
+        (chunk) in the batch, more than speculative_max_batch requests, a request with sampling params (sampled, or greedy
+        with processed logits or stop tokens: a verify step picks the argmax of the raw logits), or no draft at all. Drafts are
         clipped so that the accepted tokens never pass output_len, positions never pass the rotary table or the block
         table row, the step's rows never pass max_tokens_in_batch, and the blocks the drafts need beyond the plain step's
         are free in the allocator right now — drafts are dropped, never swapped for."""

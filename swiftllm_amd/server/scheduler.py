@@ -84,6 +84,13 @@ class Scheduler:
             # ids index the embedding table on the device: out-of-range values must never reach a kernel
             if not all(isinstance(t, int) and not isinstance(t, bool) and 0 <= t < self.vocab_size for t in ids):
                 return f"prompt_token_ids must be integers in [0, {self.vocab_size})"
+        sp = getattr(req, "sampling_params", None)
+        if self.vocab_size is not None and sp is not None:
+            # ... and so must the ids the logits adjustment indexes a row with, and a stop token nobody can generate
+            if any(t >= self.vocab_size for t, _ in (sp.logit_bias or ())):
+                return f"logit_bias ids must be in [0, {self.vocab_size})"
+            if any(t >= self.vocab_size for t in sp.stop_token_ids):
+                return f"stop_token_ids must be in [0, {self.vocab_size})"
         if self.max_seq_len is not None and req.prompt_len + req.output_len > self.max_seq_len:
             return (f"prompt ({req.prompt_len}) + output_len ({req.output_len}) exceeds the model's "
                     f"{self.max_seq_len} rotary positions")

@@ -17,7 +17,7 @@ class StepOutput:
 class RawRequest:
     """What a user submits: a prompt and how many tokens to generate. `prompt_token_ids` may be given
     instead of text (tokenizer-less use: benchmarks, synthetic checkpoints). `sampling_params` (an addition to the
-    reference): None or temperature 0 = greedy."""
+    reference): None or temperature 0 = greedy; its stop_token_ids end the request before output_len."""
 
     def __init__(self, prompt: str, output_len: int, prompt_token_ids: Optional[List[int]] = None, *,
                  sampling_params: Optional[SamplingParams] = None):
@@ -41,8 +41,15 @@ class Request:
         self.error: Optional[str] = None    # set instead of scheduling when the request can never be served
         # None = greedy. A None seed is resolved here, once: the stream depends on (seed, position) only, so the request
         # draws the same tokens through preemption, swap-out and swap-in, in any batch, on any replica
+        # (None also stands for params that ask for nothing — `plain`; a greedy request with penalties, a bias, min_tokens
+        # or stop tokens keeps its params: the data plane processes its logits, and it is never speculated)
         sp = getattr(raw_request, "sampling_params", None)
-        self.sampling_params: Optional[SamplingParams] = None if sp is None or sp.greedy else sp.with_seed()
+        self.sampling_params: Optional[SamplingParams] = (None if sp is None or sp.plain else
+                                                          sp if sp.greedy else sp.with_seed())
+        # the request also ends at the first of these tokens (delivered as its last one) once it has generated more than
+        # min_tokens tokens — before that the data plane bans them
+        self._stop_ids = frozenset(sp.stop_token_ids) if sp is not None else frozenset()
+        self._min_tokens = sp.min_tokens if sp is not None else 0
 
         # chunked prefill: prompt tokens whose KV is resident (forwarded in earlier steps), and the tokens the scheduler
         # gave this request in the step being built (0: not a prompt chunk / the whole rest of the prompt)
@@ -57,7 +64,10 @@ class Request:
         self.ngram_proposer = None
 
     def is_finished(self) -> bool:
-        return len(self.output_token_ids) >= self.output_len
+        out = self.output_token_ids
+        if len(out) >= self.output_len:
+            return True
+        return bool(self._stop_ids) and len(out) > self._min_tokens and out[-1] in self._stop_ids
 
     def get_cur_output_len(self) -> int:
         return len(self.output_token_ids)

@@ -40,10 +40,12 @@ from .kernels.block_swapping import swap_blocks
 from .kernels.linear import RawResidual
 from .kernels.paged_attn import verify_max_tokens
 from .kernels.rmsnorm import fused_add_rmsnorm_from_splitk, rmsnorm_inplace
+from .kernels import logits_process
 from .kernels.sampling import device_args, pack_params
 from .layers.pre_layer import LlamaPreLayer
 from .layers.transformer_layer import LlamaTransformerLayer
 from .layers.post_layer import LlamaPostLayer
+from .token_history import TokenHistory, row_entries
 from .weight import load_weights, pack_decode_weights
 
 _DTYPES = {"float16": torch.float16, "fp16": torch.float16, "half": torch.float16,
@@ -65,7 +67,7 @@ class _DecodeGraph:
 
 class _DecodeLookahead:
     """Everything the NEXT decode step of the same batch needs, prepared while the GPU was still busy with this one."""
-    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev", "sampling")
+    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev", "sampling", "processed")
 
 
 class LlamaModel:
@@ -121,6 +123,13 @@ class LlamaModel:
         # per-row sampling parameters of a sampled step: pinned staging + its device twin (fixed address: a sampled
         # hipGraph reads it on every replay), laid out by kernels/sampling.pack_params; one H2D copy per sampled step
         self._sample_host = self._sample_host_np = self._sample_dev = self._sample_done = None
+        # logits processing (penalties / logit bias / min-p / min_tokens bans; kernels/logits_process.py): the token history
+        # of every sequence whose request asks for it (worker/token_history.py; started by its prefill, dropped by
+        # free_seqs_resources), and the step's entries: pinned staging + its device twin (fixed address: a processed
+        # hipGraph reads it on every replay; uploaded before every processed step, look-ahead hits included)
+        self._histories = {}
+        self._edit_host = self._edit_host_np = self._edit_dev = self._edit_done = None
+        self._edit_rows_cap = 0
         # speculative decoding: drafts one verify step takes per sequence (forward_verify) = the verify attention kernel's
         # tokens per sequence (16 / G) minus the last accepted token that leads them; 0 with FP8 pools (no instantiation)
         self.max_draft_tokens = 0 if self.kv_fp8 else max(0, verify_max_tokens(self.model_config) - 1)
@@ -153,6 +162,7 @@ class LlamaModel:
         # (allocated before profile_num_blocks measures: the largest replay bucket's rows)
         ecfg = self.engine_config
         self._ensure_sampling_rows(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
+        self._ensure_edit_buffer(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)), 0)
 
     def _tune_routes(self):
         """Which side serves the 65..256-token decode projections of THIS model on THIS device is decided here, once, before
@@ -418,8 +428,51 @@ class LlamaModel:
         self._sample_dev.copy_(self._sample_host, non_blocking=True)
         self._sample_done.record()
 
+    _MIN_EDIT_CAP = 1024     # entries the edit buffer starts with
+    _ONE_COPY_WORDS = 16384  # up to this many int32 words the whole edit buffer goes up in one H2D copy
+
+    def _ensure_edit_buffer(self, rows: int, edits: int):
+        """The persistent entry buffer holds `rows` rows and `edits` entries (kernels/logits_process.buffer_len). Growing
+        it moves it: the graphs captured against the old one are dropped. The entry capacity grows in powers of two (a
+        penalised sequence adds at most one entry per step)."""
+        cap = 0 if self._edit_dev is None else logits_process.edit_capacity(self._edit_dev.numel(), self._edit_rows_cap)
+        if self._edit_dev is not None and self._edit_rows_cap >= rows and cap >= edits:
+            return
+        rows = max(rows, self._edit_rows_cap)
+        cap = max(cap, self._MIN_EDIT_CAP)
+        while cap < edits:
+            cap *= 2
+        total = logits_process.buffer_len(rows, cap)
+        self._edit_host = torch.empty(total, dtype=torch.int32, pin_memory=True)
+        self._edit_host_np = self._edit_host.numpy()
+        self._edit_dev = torch.zeros(total, dtype=torch.int32, device=self.device)
+        self._edit_done = torch.cuda.Event()
+        self._edit_rows_cap = rows
+        self._drop_decode_graphs()     # captured processed graphs point into the old buffer
+
+    def _upload_edits(self, edits, rows: int):
+        """Pack the step's entries (one RowEdits or None per real row; rows past them: inert) and ship them: one async
+        H2D copy while the buffer is small, else the row header and the used part of each of the three arrays."""
+        need = sum(len(r.ids) for r in edits if r is not None)
+        self._ensure_edit_buffer(rows, need)
+        self._edit_done.synchronize()     # (the previous step's copy out of the pinned buffer: long done)
+        rows_cap = self._edit_rows_cap
+        used = logits_process.pack_edits(edits, self._edit_host_np, rows_cap)
+        total = self._edit_dev.numel()
+        if total <= self._ONE_COPY_WORDS:
+            self._edit_dev.copy_(self._edit_host, non_blocking=True)
+        else:
+            base = 5 * rows_cap + 1
+            cap = logits_process.edit_capacity(total, rows_cap)
+            self._edit_dev[:base].copy_(self._edit_host[:base], non_blocking=True)
+            if used:
+                for a in range(3):
+                    lo = base + a * cap
+                    self._edit_dev[lo:lo + used].copy_(self._edit_host[lo:lo + used], non_blocking=True)
+        self._edit_done.record()
+
     def _make_infer_state(self, plan: BatchPlan, dev: dict, ignore_kvcache: bool,
-                          sampled: bool = False) -> LlamaInferState:
+                          sampled: bool = False, processed: bool = False) -> LlamaInferState:
         nsb = plan.num_seq_blocks
         if nsb > 1:
             need = _hip.scratch_bytes(plan.num_decoding_seqs, self.model_config.num_q_heads,
@@ -442,6 +495,7 @@ class LlamaModel:
             position_indices=dev["position_indices"], last_token_indices=dev["last_token_indices"],
             paged_attn_scratch=self._scratch if nsb > 1 else None,
             sampling=device_args(self._sample_dev, dev["seq_lengths"]) if sampled else None,
+            adjust=logits_process.device_args(self._edit_dev, self._edit_rows_cap) if processed else None,
             prefill_ctx_lens=dev.get("prefill_ctx_lens"), max_prefill_total_len=plan.max_prefill_total_len,
             kv_scales=self.kv_scales, kv_inv_scales=self.kv_inv_scales,
             verify=plan.verify_row_lens is not None, verify_row_lens=dev.get("verify_row_lens"))
@@ -456,7 +510,8 @@ class LlamaModel:
                                   infer_state.seq_ids, infer_state.decoding_seq_lens, self._cos_cached, self._sin_cached,
                                   self.engine_config.max_blocks_per_seq)
             rmsnorm_inplace(x, self.weight.final_norm, self.model_config.rms_norm_eps)
-            return self.post_layer.forward_normed(x, out=self._engine.tok_err[:1], sampling=infer_state.sampling)
+            return self.post_layer.forward_normed(x, out=self._engine.tok_err[:1], sampling=infer_state.sampling,
+                                                  adjust=infer_state.adjust)
         x = self.pre_layer.forward(input_ids)
         residual = torch.zeros_like(x)
         block_table = None if infer_state.ignore_kvcache else self.gpu_block_manager.block_table
@@ -465,12 +520,12 @@ class LlamaModel:
         if isinstance(x, RawResidual):          # the last down projection added itself into the residual (rows_decode):
             x = residual.clone()                # pure decode, every row a last token — final norm of the residual rows
             rmsnorm_inplace(x, self.weight.final_norm, self.model_config.rms_norm_eps)
-            return self.post_layer.forward_normed(x, sampling=infer_state.sampling)
+            return self.post_layer.forward_normed(x, sampling=infer_state.sampling, adjust=infer_state.adjust)
         if not isinstance(x, torch.Tensor):     # the last down projection left as split-K partials
             if infer_state.num_prefill_seqs == 0:
                 # pure decode: every row is a last token — reduce + residual add + final norm in one launch
                 x = fused_add_rmsnorm_from_splitk(x, residual, self.weight.final_norm, self.model_config.rms_norm_eps)
-                return self.post_layer.forward_normed(x, sampling=infer_state.sampling)
+                return self.post_layer.forward_normed(x, sampling=infer_state.sampling, adjust=infer_state.adjust)
             x = x.materialize()
         x += residual
         return self.post_layer.forward(x, infer_state)
@@ -563,7 +618,8 @@ class LlamaModel:
         plan.num_real_seqs = b
         return plan
 
-    def _forward_decode_graph(self, plan: BatchPlan, dev: dict, sampled: bool = False) -> torch.Tensor:
+    def _forward_decode_graph(self, plan: BatchPlan, dev: dict, sampled: bool = False,
+                              processed: bool = False) -> torch.Tensor:
         sbs, nsb_cap = self._graph_bucket(plan)
         use_engine = self._engine is not None and plan.batch_size == 1
         tap = self.post_layer.logits_tap
@@ -571,18 +627,18 @@ class LlamaModel:
         # (the engine has one launch geometry; a graph captured while a test taps the logits keeps its [B, vocab] tensor
         # alive in the shared pool, one captured without the tap does not — up to 65 MB per graph at 256 sequences)
         # (a sampled step is a graph of its own: its sampler reads the persistent parameter buffer; greedy graphs are as
-        # they were)
-        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None, sampled)
+        # they were; so is a processed step: its adjustment kernel reads the persistent entry buffer)
+        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None, sampled, processed)
         entry = self._decode_graphs.pop(key, None)
         plan.seq_block_size, plan.num_seq_blocks = sbs, nsb_cap
         if entry is None:
             self.graph_captures += 1
             t_cap = time.perf_counter()
-            state = self._make_infer_state(plan, dev, False, sampled)
+            state = self._make_infer_state(plan, dev, False, sampled, processed)
             # one eager run on a side stream first (library handles, workspaces, allocator pools): nothing may be lazily
             # initialised while the stream is capturing. Once per BATCH BUCKET (r06b): a new split geometry at a batch size
             # that has been captured before launches the same kernels on the same shapes — only the attention grid moves.
-            warm_key = (key[0], use_engine, tap is not None, sampled)
+            warm_key = (key[0], use_engine, tap is not None, sampled, processed)
             if warm_key not in self._warmed_buckets:
                 warm = torch.cuda.Stream()
                 warm.wait_stream(torch.cuda.current_stream())
@@ -616,7 +672,8 @@ class LlamaModel:
         return entry.out_tokens[:n]
 
     # ---- decode look-ahead: the host side of step k+1 runs while the GPU executes step k ---------------------------------
-    def _prepare_next_decode(self, plan: BatchPlan, seq_ids_list: List[int], tokens_dev: torch.Tensor, sampling=None):
+    def _prepare_next_decode(self, plan: BatchPlan, seq_ids_list: List[int], tokens_dev: torch.Tensor, sampling=None,
+                             processed: bool = False):
         """Called right after the graph of a pure-decode step was launched, before the host blocks on its tokens. A
         generation loop calls forward again with the same sequences, every length + 1 and the tokens just sampled: plan
         that step now (numpy) and enqueue — behind the running graph, on the same stream — the H2D copy of its metadata and
@@ -645,16 +702,19 @@ class LlamaModel:
         la = _DecodeLookahead()
         la.seq_ids, la.lens, la.plan, la.dev, la.tokens = list(seq_ids_list), next_lens, nxt, dev, None
         la.sampling = sampling      # (the parameter buffer keeps this step's rows: the next step may reuse it as it is)
+        la.processed = processed    # (the entry buffer does NOT keep: a processed step uploads its entries on a hit too)
         return la
 
-    def _take_lookahead(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None):
+    def _take_lookahead(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
+                        processed: bool = False):
         """The prepared step, if this call is it (any other call drops the preparation). A sampled step hits only with
         the per-row parameters (seeds resolved) of the step it was prepared after: those are still on the device."""
         la, self._lookahead = self._lookahead, None
         if (la is None or la.tokens is None or ignore_kvcache or not self._decode_lookahead
                 or not getattr(self.engine_config, "use_hip_graph", False)
                 or len(input_ids_list) != len(la.lens) or list(decoding_seq_lens_list) != la.lens
-                or list(seq_ids_list) != la.seq_ids or sampling != getattr(la, "sampling", None)):
+                or list(seq_ids_list) != la.seq_ids or sampling != getattr(la, "sampling", None)
+                or processed != getattr(la, "processed", False)):
             return None
         for ids, tok in zip(input_ids_list, la.tokens):
             if len(ids) != 1 or ids[0] != tok:
@@ -700,15 +760,91 @@ class LlamaModel:
                 raise ValueError("sampling_params must be aligned with input_ids_list")
             if not all(is_greedy(p) for p in sampling_params):
                 sampling = [None if is_greedy(p) else p.with_seed() for p in sampling_params]
+        # logits processing: the histories move ONCE per call, here (the engine fallback below runs the step twice)
+        # (a step that raises — block allocation, the rotary table — takes its history updates back: the caller may repeat
+        # the call, and the other sequences of the batch stay in step)
+        edits, undo = None, []
+        if not ignore_kvcache and (self._histories or (sampling_params is not None and any(
+                p is not None and p.processes_logits for p in sampling_params))):
+            edits = self._track_histories(input_ids_list, seq_ids_list, decoding_seq_lens_list,
+                                          sampling_params or [None] * len(input_ids_list), prefill_ctx_lens, undo)
         try:
-            return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                      prefill_ctx_lens)
-        except _decode_engine.DecodeEngineError as exc:
-            # bounded hand-off timed out inside the persistent one-sequence step: its KV writes are re-done below with the
-            # same values by the multi-launch HIP path, which serves one-sequence steps from here on
-            self._engine_failed(int(str(exc)))
-            return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                      prefill_ctx_lens)
+            try:
+                return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
+                                          prefill_ctx_lens, edits)
+            except _decode_engine.DecodeEngineError as exc:
+                # bounded hand-off timed out inside the persistent one-sequence step: its KV writes are re-done below with
+                # the same values by the multi-launch HIP path, which serves one-sequence steps from here on
+                self._engine_failed(int(str(exc)))
+                return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
+                                          prefill_ctx_lens, edits)
+        except BaseException:
+            self._rollback_histories(undo)
+            raise
+
+    def _rollback_histories(self, undo):
+        for rec in reversed(undo):
+            if rec[0] == "slot":        # a history that was started, replaced or dropped
+                _, sid, old = rec
+                if old is None:
+                    self._histories.pop(sid, None)
+                else:
+                    self._histories[sid] = old
+            else:
+                _, hist, mark, words = rec
+                hist.rollback(mark, words)
+
+    def _track_histories(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, params, prefill_ctx_lens, undo):
+        """Bring the token histories up to this call and return the step's entries: one RowEdits per row whose params
+        process logits, None for the others — or None when no row does. Prefill tokens (whole prompts and chunks) are
+        prompt tokens, a decode row's input token is an output token. A history starts at a prefill call without a context
+        whose params process logits; every tracked sequence is held to its length (ValueError when out of step), and a row
+        that processes logits without a history is refused. Everything is checked before anything is changed; what is
+        changed is recorded in `undo` (see _rollback_histories: forward takes it back when the step itself raises)."""
+        n_pre = len(input_ids_list) - len(decoding_seq_lens_list)
+        ctx = prefill_ctx_lens or [0] * n_pre
+        vocab = self.model_config.vocab_size
+        for i, (ids, sid, p) in enumerate(zip(input_ids_list, seq_ids_list, params)):
+            proc = p is not None and p.processes_logits
+            h = self._histories.get(sid)
+            if i < n_pre and ctx[i] == 0:
+                if proc and (any(t >= vocab for t, _ in p.logit_bias or ()) or any(t >= vocab for t in p.stop_token_ids)):
+                    raise ValueError(f"sequence {sid}: logit_bias and stop_token_ids must name ids in [0, {vocab})")
+                continue
+            if h is None:
+                if proc:
+                    raise ValueError(f"sequence {sid}: its sampling params process logits but it has no token history "
+                                     "(the history starts at the sequence's first prefill call with such params)")
+                continue
+            have = ctx[i] if i < n_pre else decoding_seq_lens_list[i - n_pre] - 1
+            if len(h) != have or (i < n_pre and h.num_output):
+                raise ValueError(f"sequence {sid}: its token history holds {len(h)} tokens ({h.num_output} generated), "
+                                 f"this call places it at {have}: out of step")
+        rows, any_row = [], False
+        for i, (ids, sid, p) in enumerate(zip(input_ids_list, seq_ids_list, params)):
+            proc = p is not None and p.processes_logits
+            if i < n_pre and ctx[i] == 0:
+                old = self._histories.pop(sid, None)      # (a sequence id that starts over)
+                if proc:
+                    self._histories[sid] = TokenHistory(max(64, 2 * len(ids)))
+                if old is not None or proc:
+                    undo.append(("slot", sid, old))
+            h = self._histories.get(sid)
+            if h is not None:
+                words = []
+                undo.append(("meta", h, h.mark(), words))
+                if i < n_pre:
+                    h.add_prompt(ids, words)
+                else:
+                    h.add_output(ids[0], words)
+            if not proc:
+                rows.append(None)
+                continue
+            e_ids, e_meta, e_bias = row_entries(p, h)
+            rows.append(logits_process.RowEdits(e_ids, e_meta, e_bias, p.repetition_penalty, p.presence_penalty,
+                                                p.frequency_penalty, p.min_p_gap()))
+            any_row = True
+        return rows if any_row else None
 
     def _check_prefill_ctx(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, ctx):
         """Host-side refusals of a chunked-prefill call, before anything is launched or allocated. Returns the contexts
@@ -739,15 +875,18 @@ class LlamaModel:
         return ctx
 
     def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
-                      prefill_ctx_lens=None):
+                      prefill_ctx_lens=None, edits=None):
         prof = self._host_prof
         t0 = time.perf_counter() if prof is not None else 0.0
         sampled = sampling is not None
-        la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling)
+        processed = edits is not None
+        la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling, processed)
         if la is not None:      # the step that was prepared while the previous one ran: blocks, then the launch
             self.gpu_block_manager.allocate_blocks_for_seqs(la.seq_ids, la.lens)   # (the real sequences only)
-            tokens = self._forward_decode_graph(la.plan, la.dev, sampled)
-            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens, sampling)
+            if processed:       # (the entries change every step: they go up before every replay)
+                self._upload_edits(edits, la.plan.batch_size)
+            tokens = self._forward_decode_graph(la.plan, la.dev, sampled, processed)
+            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens, sampling, processed)
             if self.after_launch_hook is not None:
                 self.after_launch_hook()
             t4 = time.perf_counter() if prof is not None else 0.0
@@ -783,17 +922,20 @@ class LlamaModel:
         dev = self._upload_plan(plan)
         if sampled:
             self._upload_sampling(sampling, plan.batch_size)
+        if processed:
+            self._upload_edits(edits, plan.batch_size)
         t3 = time.perf_counter() if prof is not None else 0.0
         pure_decode = plan.num_prefill_seqs == 0
         nxt = None
         if (pure_decode and not ignore_kvcache and getattr(self.engine_config, "use_hip_graph", False)):
-            tokens = self._forward_decode_graph(plan, dev, sampled)
+            tokens = self._forward_decode_graph(plan, dev, sampled, processed)
             if self._decode_lookahead:
-                nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens, sampling)
+                nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens, sampling, processed)
         else:
             if pure_decode and not ignore_kvcache and self._eager_uses_graph_buckets:
                 plan.seq_block_size, plan.num_seq_blocks = self._graph_bucket(plan)
-            tokens = self._forward(dev["input_ids"], self._make_infer_state(plan, dev, ignore_kvcache, sampled))[:num_real]
+            tokens = self._forward(dev["input_ids"],
+                                   self._make_infer_state(plan, dev, ignore_kvcache, sampled, processed))[:num_real]
             tap = self.post_layer.logits_tap
             if tap and plan.batch_size > num_real:      # (tests) a padded eager step: the real rows only, as on replay
                 tap[-1] = tap[-1][:num_real]
@@ -847,6 +989,10 @@ class LlamaModel:
                                  f"(max_draft_tokens = {self.max_draft_tokens})")
         if self.gpu_block_manager is None or self.k_cache is None:
             raise RuntimeError("forward_verify before init_kvcache_and_swap: there is no KV pool to verify against")
+        tracked = [sid for sid in seq_ids_list if sid in self._histories]
+        if tracked:
+            raise ValueError(f"forward_verify on sequences {tracked} whose logits are processed: a verify step picks the "
+                             "argmax of the raw logits")
         ctx = [int(c) for c in ctx_lens]
         self._check_prefill_ctx(input_ids_list, seq_ids_list, [], False, ctx)     # (all-zero contexts pass: None)
         self._lookahead = None      # a prepared decode step does not survive a verify step
@@ -916,5 +1062,7 @@ class LlamaModel:
         if len(seq_ids_list) == 0:
             return
         self._lookahead = None
+        for sid in seq_ids_list:
+            self._histories.pop(sid, None)
         self.gpu_block_manager.free_blocks_for_seqs(seq_ids_list)
         self.cpu_block_manager.free_blocks_for_seqs(seq_ids_list)
