@@ -28,13 +28,19 @@ def main():
     ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8_e4m3"])
     ap.add_argument("--speculative-ngram", type=int, default=0,
                     help="prompt-lookup speculative decoding: n-gram drafts per sequence per step (0 = off)")
+    ap.add_argument("--max-loras", type=int, default=0, help="multi-LoRA serving: adapter slots (0 = off)")
+    ap.add_argument("--max-lora-rank", type=int, default=16, choices=[8, 16, 32, 64])
+    ap.add_argument("--lora", action="append", default=None, metavar="NAME=PATH",
+                    help="a PEFT adapter directory (repeatable): prompt i runs with adapter i, the prompts beyond the "
+                         "adapters with the base model")
     args = ap.parse_args()
 
     cfg = swiftllm.EngineConfig(model_path=args.model_path, use_dummy=args.use_dummy, block_size=16,
                                 gpu_mem_utilization=0.9, num_cpu_blocks=0, max_seqs_in_block_table=128,
                                 max_blocks_per_seq=2048, max_batch_size=16, max_tokens_in_batch=2048 * 16,
                                 dtype=args.dtype, use_hip_graph=True, kv_cache_dtype=args.kv_cache_dtype,
-                                speculative_ngram=args.speculative_ngram)
+                                speculative_ngram=args.speculative_ngram, max_loras=args.max_loras,
+                                max_lora_rank=args.max_lora_rank, lora_modules=args.lora)
     t0 = time.perf_counter()
     model = swiftllm.LlamaModel(cfg)
     model.load_weights()
@@ -56,12 +62,15 @@ def main():
     seq_ids = list(range(len(input_ids)))
     if args.speculative_ngram > 0:
         return generate_speculative(model, input_ids, seq_ids, args, tokenizer)
-    outputs = [model.forward(input_ids, seq_ids, [])]
+    # one adapter per prompt, in the order of --lora; None (the base model) for the rest; no --lora: the call of always
+    names = list(model.loras())
+    kw = {"lora": [names[i] if i < len(names) else None for i in seq_ids]} if names else {}
+    outputs = [model.forward(input_ids, seq_ids, [], **kw)]
     lens = [len(x) for x in input_ids]
     t0 = time.perf_counter()
     for _ in range(args.steps):
         lens = [n + 1 for n in lens]
-        outputs.append(model.forward([[t] for t in outputs[-1]], seq_ids, lens))
+        outputs.append(model.forward([[t] for t in outputs[-1]], seq_ids, lens, **kw))
     dt = time.perf_counter() - t0
     print(f"{args.steps} decode steps x {len(seq_ids)} sequences: {dt / args.steps * 1e3:.2f} ms/step")
     for i in seq_ids:

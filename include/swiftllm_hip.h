@@ -661,6 +661,31 @@ int swl_decode_engine_step(void *resid_out, const void *w_stream, const void *no
                            int32_t ffn_inter_dim, int32_t max_blocks_per_seq, float eps, float softmax_scale,
                            int32_t flags, int32_t dtype, swl_stream_t stream);
 
+/* ---- per-row low-rank adapters (multi-LoRA serving; csrc/lora.hip; no reference counterpart) ---------------------------------
+ * A projection group (one weight tensor of a layer) has `num_parts` column parts of its n outputs, each with a rank-r_max
+ * adapter: a_stack [num_slots, r_total = num_parts * r_max, k] and b_stack [num_slots, n, r_max] in the storage dtype, scale
+ * fp32 [num_slots]. The host groups the rows that have an adapter into tiles of <= 16 rows of ONE slot: tile_rows
+ * [num_tiles * 16] int32 (row index in [0, num_tokens), -1 = padding, no row twice) and tile_slots [num_tiles] int32 (device
+ * arrays). Rows in no tile are neither read nor written.
+ *   swl_lora_k_splits: k_splits = ceil(k / 1024), the number of fp32 slabs of t (0 for k <= 0): a function of k alone.
+ *   swl_lora_shrink: t[kc][row][c] = sum over k chunk kc of x[row, k] * a_stack[slot][c, k]; t is fp32
+ *     [k_splits, num_tokens, r_total], x 16-bit [num_tokens, k] with x_row_stride (elements). fp32 accumulation, no atomics.
+ *   swl_lora_expand: y[row, n] = T(float(y[row, n]) + scale[slot] * sum_r t[row, t_off(n) + r] * b_stack[slot][n, r]), in
+ *     place, ONE rounding; t is summed over its slabs in slab order and enters the MFMAs as hi + lo 16-bit halves (never
+ *     rounded to 16 bits). `parts` is a HOST array of num_parts (<= 4) triples (n_begin, n_end, t_col_offset) that tile
+ *     [0, n) in order.
+ * A row's result depends on that row's data and on (k, r_total, n) only: not on num_tokens, the tiling or the other rows.
+ * Supported: r_max in {8, 16, 32, 64}, k % 128 == 0, part widths % 16 == 0, row strides % 8 == 0 (else
+ * SWL_ERR_UNSUPPORTED); an empty batch (num_tiles == 0 or num_tokens == 0) launches nothing. */
+int swl_lora_k_splits(int32_t k);
+int swl_lora_shrink(float *t, const void *x, const void *a_stack, const int32_t *tile_rows, const int32_t *tile_slots,
+                    int32_t num_tiles, int32_t num_tokens, int32_t k, int32_t r_total, int32_t num_slots,
+                    int64_t x_row_stride, int32_t dtype, swl_stream_t stream);
+int swl_lora_expand(void *y, const float *t, const void *b_stack, const float *scale, const int32_t *tile_rows,
+                    const int32_t *tile_slots, const int32_t *parts, int32_t num_parts, int32_t num_tiles,
+                    int32_t num_tokens, int32_t n, int32_t r_max, int32_t r_total, int32_t k_splits, int32_t num_slots,
+                    int64_t y_row_stride, int32_t dtype, swl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,11 @@ _SPECIAL = {
                                _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I64, _I32, _P], _I32),
     # Logits adjustment (csrc/logits_adjust.hip): an "int rc = f(...)" entry too, registered here for the same reason.
     "swl_logits_adjust": ([_P, _I64, _I32, _I64, _I32, _P, _P, _P, _P, _P, _P], _I32),
+    # Multi-LoRA adapter updates (csrc/lora.hip): shrink and expand are "int rc = f(...)" entries, registered here for the
+    # same reason; swl_lora_k_splits is host arithmetic (the number of fp32 slabs of t: a function of K alone).
+    "swl_lora_k_splits": ([_I32], _I32),
+    "swl_lora_shrink": ([_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _P], _I32),
+    "swl_lora_expand": ([_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

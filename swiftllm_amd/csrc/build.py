@@ -34,6 +34,7 @@ SOURCES = [
     "argmax.hip",
     "sampling.hip",
     "logits_adjust.hip",
+    "lora.hip",
     "decode_engine.hip",
 ]
 HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "fp8_kv.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]

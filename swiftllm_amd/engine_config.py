@@ -73,6 +73,14 @@ class EngineConfig:
     # ... and only for decode batches of at most this many requests: with 3 drafts, 8 x 4 = 32 rows keep every projection
     # of the verify forward inside the weight-streaming GEMMs' range (kernels/linear.py: <= 32 tokens).
     speculative_max_batch: int = 8
+    # Multi-LoRA serving (worker/lora.py, csrc/lora.hip): adapter slots resident next to the base weights. 0 (default): off —
+    # nothing is allocated and every step launches what it always did. > 0: load_weights allocates zero-filled slot stacks
+    # for every projection of every layer (before the KV pool is sized) for adapters of rank <= max_lora_rank (8, 16, 32 or
+    # 64), and a request may name an adapter; a step with an adapter row runs the straight-line LoRA layer path, eagerly
+    # (16-bit KV pools only). lora_modules: "NAME=PATH" PEFT directories load_weights loads.
+    max_loras: int = 0
+    max_lora_rank: int = 16
+    lora_modules: list = None
 
     # Internal switches (all on): set through `tuning`, read by the layer code as plain attributes.
     TUNING_DEFAULTS = dict(
@@ -112,6 +120,7 @@ class EngineConfig:
     # of a 128-wide head is 4 KiB = one wave-wide 16 B/lane load x 4.
     SUPPORTED_BLOCK_SIZE = 16
     KV_CACHE_DTYPES = ("auto", "fp8_e4m3")
+    LORA_RANKS = (8, 16, 32, 64)
 
     def __post_init__(self):
         # The reference takes block_size as a Triton constexpr (paged_attn.py:27) and its CLI default is 16
@@ -131,6 +140,20 @@ class EngineConfig:
             raise ValueError(f"speculative_ngram must be >= 0 (0 = off), got {self.speculative_ngram}")
         if int(self.speculative_max_batch) < 0:
             raise ValueError(f"speculative_max_batch must be >= 0, got {self.speculative_max_batch}")
+        if int(self.max_loras) < 0:
+            raise ValueError(f"max_loras must be >= 0 (0 = off), got {self.max_loras}")
+        if int(self.max_lora_rank) not in self.LORA_RANKS:
+            raise ValueError(f"max_lora_rank must be one of {list(self.LORA_RANKS)}, got {self.max_lora_rank}")
+        if self.lora_modules:
+            if int(self.max_loras) <= 0:
+                raise ValueError("lora_modules needs max_loras > 0")
+            names = [str(m).partition("=")[0] for m in self.lora_modules]
+            if any("=" not in str(m) or not n or not str(m).partition("=")[2] for m, n in zip(self.lora_modules, names)):
+                raise ValueError(f"lora_modules entries are 'NAME=PATH' strings, got {list(self.lora_modules)}")
+            if len(set(names)) != len(names):
+                raise ValueError(f"lora_modules names an adapter twice: {names}")
+            if len(names) > int(self.max_loras):
+                raise ValueError(f"lora_modules names {len(names)} adapters, max_loras is {self.max_loras}")
         unknown = set(self.tuning or ()) - set(self.TUNING_DEFAULTS)
         if unknown:
             raise ValueError(f"unknown tuning switches {sorted(unknown)}; known: {sorted(self.TUNING_DEFAULTS)}")
@@ -139,6 +162,12 @@ class EngineConfig:
         if self.kv_cache_dtype == "fp8_e4m3" and self.decode_engine:
             raise ValueError("kv_cache_dtype='fp8_e4m3' cannot be combined with tuning={'decode_engine': True}: the "
                              "persistent one-sequence decode step reads and writes 16-bit KV pools only")
+        if int(self.max_loras) > 0 and self.kv_cache_dtype == "fp8_e4m3":
+            raise ValueError("max_loras > 0 cannot be combined with kv_cache_dtype='fp8_e4m3': the LoRA layer path stores "
+                             "and attends 16-bit KV pools only")
+        if int(self.max_loras) > 0 and self.decode_engine:
+            raise ValueError("max_loras > 0 cannot be combined with tuning={'decode_engine': True}: the persistent "
+                             "one-sequence decode step has no adapter path")
         if int(self.speculative_ngram) > 0 and self.kv_cache_dtype == "fp8_e4m3":
             raise ValueError("speculative_ngram > 0 cannot be combined with kv_cache_dtype='fp8_e4m3': the verify "
                              "attention kernel reads 16-bit KV pools only")
@@ -179,5 +208,11 @@ class EngineConfig:
                        help="Prompt-lookup speculative decoding: n-gram drafts per sequence per step (0 = off)")
         g.add_argument("--speculative-max-batch", type=int, default=8,
                        help="Speculate only in decode steps of at most this many requests")
+        g.add_argument("--max-loras", type=int, default=0,
+                       help="Multi-LoRA serving: adapter slots resident next to the base weights (0 = off)")
+        g.add_argument("--max-lora-rank", type=int, default=16, choices=list(EngineConfig.LORA_RANKS),
+                       help="Largest adapter rank a slot holds (lower ranks are zero-padded)")
+        g.add_argument("--lora", dest="lora_modules", action="append", default=None, metavar="NAME=PATH",
+                       help="A PEFT adapter directory to load at start-up under NAME (repeatable)")
         g.add_argument("--max-prefill-chunk", type=int, default=0,
                        help="Chunked prefill: prompt tokens per forward, at most (0 = off: a prompt is one forward)")

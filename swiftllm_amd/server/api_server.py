@@ -5,7 +5,8 @@
 `POST /generate` with JSON {prompt | prompt_token_ids, output_len, stream?, decode?} — the request
 format of the reference's swiftllm/server/api_server.py:16-84, plus optional sampling fields (temperature,
 top_k, top_p, seed; repetition_penalty, presence_penalty, frequency_penalty, min_p, logit_bias = {"id": bias},
-stop_token_ids, min_tokens; absent = greedy to output_len, as in the reference): non-streaming answers
+stop_token_ids, min_tokens; absent = greedy to output_len, as in the reference) and "lora": the name of a loaded LoRA
+adapter (--max-loras / --lora NAME=PATH; absent = the base model): non-streaming answers
 {"output_token_ids": [...]} (or {"output": text} with decode), streaming sends one line per token.
 `GET /load` reports outstanding tokens (used by the replica router). Any engine failure takes the
 process down (reference api_server.py:114-119) so a supervisor can restart the replica.
@@ -45,6 +46,8 @@ def _validate_body(body) -> "str | None":
             return "prompt_token_ids out of range"
     if not isinstance(body.get("prompt", ""), str):    # also when token ids are given: the handler still touches it
         return "prompt must be a string"
+    if "lora" in body and (not isinstance(body["lora"], str) or not body["lora"]):
+        return "lora must be a non-empty string (the name of a loaded adapter)"
     return _validate_sampling(body)
 
 
@@ -144,7 +147,7 @@ def build_app(engine: Engine) -> fastapi.FastAPI:
         if problem is not None:
             return JSONResponse({"error": problem}, status_code=400)
         raw = RawRequest(body.get("prompt", ""), body["output_len"], body.get("prompt_token_ids"),
-                         sampling_params=_sampling_params(body))
+                         sampling_params=_sampling_params(body), lora=body.get("lora"))
         want_text = bool(body.get("decode", False))
         cost = raw.output_len + len(raw.prompt_token_ids or raw.prompt.split())
         state["outstanding_tokens"] += cost

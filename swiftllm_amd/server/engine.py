@@ -86,6 +86,8 @@ class Engine:
         rope = getattr(self.model, "_cos_cached", None)
         if rope is not None:     # a request that would outgrow the rotary table is refused up front (HTTP 400),
             self.scheduler.max_seq_len = int(rope.shape[0])     # not left to raise inside forward mid-flight
+        if hasattr(self.model, "loras"):     # a request may only name an adapter that is loaded when it arrives
+            self.scheduler.lora_names = lambda: self.model.loras().keys()
         self.tokenization_engine = TokenizationEngine(self.engine_config)
         want_k = int(getattr(self.engine_config, "speculative_ngram", 0) or 0)
         if want_k > 0:
@@ -130,6 +132,49 @@ class Engine:
         request = self._enqueue(raw_request)
         await request.finished_event.wait()
         return request, request.output_token_ids
+
+    # ---- LoRA adapters, while serving ---------------------------------------------------------------------------------
+    def _on_model_thread(self, func):
+        """Run `func` where the model runs: on the model thread between two iterations while the serving loop is alive
+        (a callable posted through the inbox), in place otherwise. Blocks the caller until it ran; re-raises what it raised."""
+        thread = self._model_thread
+        if thread is None or not thread.is_alive() or threading.current_thread() is thread:
+            return func()
+        done, box = threading.Event(), {}
+
+        def job():
+            try:
+                box["value"] = func()
+            except BaseException as exc:     # noqa: BLE001 — handed to the caller
+                box["error"] = exc
+            finally:
+                done.set()
+        self._inbox.put(job)
+        while not done.wait(0.05):
+            if not thread.is_alive():
+                raise RuntimeError("the model thread stopped before the LoRA command ran")
+        if "error" in box:
+            raise box["error"]
+        return box.get("value")
+
+    def _lora_in_use(self, name: str) -> bool:
+        sch = self.scheduler
+        return any(r.lora == name for q in (sch.waiting_q, sch.running_q, sch.swapped_q) for r in q)
+
+    def load_lora(self, name: str, path: Optional[str] = None, **kwargs) -> int:
+        """Load an adapter while serving (LlamaModel.load_lora, on the model thread); returns its slot. Call it from any
+        thread but the event loop's (an HTTP handler: `await loop.run_in_executor(None, engine.load_lora, ...)`)."""
+        return self._on_model_thread(lambda: self.model.load_lora(name, path, **kwargs))
+
+    def unload_lora(self, name: str) -> int:
+        """Unload an adapter (on the model thread). Refused with ValueError while a waiting, running or swapped request
+        names it; requests that arrive afterwards are refused by the scheduler (the adapter is not loaded)."""
+        def unload():
+            self._drain_inbox()     # (arrivals already accepted against the loaded set count as waiting)
+            if self._lora_in_use(name):
+                raise ValueError(f"LoRA adapter {name!r} is in use by a request that is waiting, running or swapped out")
+            return self.model.unload_lora(name)
+        return self._on_model_thread(unload)
 
     # ---- asyncio side -------------------------------------------------------------------------------------------
     async def _tokenize_raw_request_event_loop(self):
@@ -191,13 +236,44 @@ class Engine:
             pass
 
     def _drain_inbox(self, wait_s: float = 0.0):
+        """Arrivals go to the scheduler; a callable (a LoRA load / unload posted by _on_model_thread) is held back and run
+        once the inbox is empty, so that it sees every arrival that was accepted before it."""
+        jobs = []
         try:
             if wait_s > 0.0:
-                self.scheduler.on_requests_arrival(self._inbox.get(timeout=wait_s))
+                self._take_inbox_item(self._inbox.get(timeout=wait_s), jobs)
             while True:
-                self.scheduler.on_requests_arrival(self._inbox.get_nowait())
+                self._take_inbox_item(self._inbox.get_nowait(), jobs)
         except queue.Empty:
             pass
+        for job in jobs:
+            job()
+
+    def _take_inbox_item(self, item, jobs: list):
+        if callable(item):
+            jobs.append(item)
+            return
+        # An adapter may have been unloaded between the check on the event loop (why_unservable) and this moment: the
+        # name is checked again here, on the thread that loads and unloads, and such a request is answered with an error
+        # instead of reaching forward() with an unknown name.
+        names = self.scheduler.lora_names
+        gone = [r for r in item if r.lora is not None and (names is None or r.lora not in names())]
+        if gone:
+            item = [r for r in item if r not in gone]
+            for r in gone:
+                r.error = f"LoRA adapter {r.lora!r} is not loaded"
+            try:
+                self.event_loop.call_soon_threadsafe(self._reject, gone)
+            except RuntimeError:        # the event loop is gone (shutdown)
+                pass
+        self.scheduler.on_requests_arrival(item)
+
+    def _reject(self, requests: List[Request]):
+        """Answer requests that will never run (event-loop thread): waiters wake up with `error` set, streams end."""
+        for req in requests:
+            self._live.discard(req)
+            req.finished_event.set()
+            req.output_q.put_nowait(None)
 
     def _iterate(self) -> bool:
         """One scheduling iteration, start to finish, on the calling (model) thread; False when there was nothing
@@ -235,6 +311,8 @@ class Engine:
                 kwargs["sampling_params"] = sampling
             if any(r.num_prefilled for r in prefills):      # (no resident context: the call of always)
                 kwargs["prefill_ctx_lens"] = [r.num_prefilled for r in prefills]
+            if any(r.lora is not None for r in batch):      # (no adapter in the batch: the call of always)
+                kwargs["lora"] = [r.lora for r in batch]
             try:
                 tokens = self.model.forward(input_ids, seq_ids, decoding_lens, **kwargs)
             finally:
@@ -263,13 +341,14 @@ class Engine:
     def _propose_drafts(self, batch: List[Request]) -> Optional[List[List[int]]]:
         """Drafts for every request of the batch (aligned with it), or None when this step is a plain forward: a prompt
         (chunk) in the batch, more than speculative_max_batch requests, a request with sampling params (sampled, or greedy
-        with processed logits or stop tokens: a verify step picks the argmax of the raw logits), or no draft at all. Drafts are
+        with processed logits or stop tokens: a verify step picks the argmax of the raw logits), a request with a LoRA
+        adapter (forward_verify takes none), or no draft at all. Drafts are
         clipped so that the accepted tokens never pass output_len, positions never pass the rotary table or the block
         table row, the step's rows never pass max_tokens_in_batch, and the blocks the drafts need beyond the plain step's
         are free in the allocator right now — drafts are dropped, never swapped for."""
         ecfg = self.engine_config
         if (len(batch) > int(getattr(ecfg, "speculative_max_batch", 0)) or not hasattr(self.model, "forward_verify")
-                or any(not r.is_prompt_resident() or r.sampling_params is not None for r in batch)):
+                or any(not r.is_prompt_resident() or r.sampling_params is not None or r.lora is not None for r in batch)):
             return None
         bs = ecfg.block_size
         limit = self.scheduler.max_seq_len

@@ -89,6 +89,24 @@ def spawn_replicas(num: int, base_port: int, passthrough: List[str]) -> List[sub
     return procs
 
 
+def lora_passthrough(max_loras, max_lora_rank, loras) -> List[str]:
+    """The replicas' flags for the router's LoRA options; refuses what every replica would refuse, before any is spawned."""
+    if loras and not max_loras:
+        raise SystemExit("--lora needs --max-loras > 0")
+    for spec in loras or ():
+        name, sep, path = spec.partition("=")
+        if not sep or not name or not path:
+            raise SystemExit(f"--lora takes NAME=PATH, got {spec!r}")
+    out: List[str] = []
+    if max_loras is not None:
+        out += ["--max-loras", str(max_loras)]
+    if max_lora_rank is not None:
+        out += ["--max-lora-rank", str(max_lora_rank)]
+    for spec in loras or ():
+        out += ["--lora", spec]
+    return out
+
+
 async def wait_until_ready(urls: List[str], timeout_s: float = 1800.0, procs=None) -> None:
     """Poll every replica's GET /load until it answers (weights loaded, KV pool profiled). `procs` (the replicas'
     subprocess.Popen objects, same order as `urls`): a replica whose process has exited fails the wait at once
@@ -119,9 +137,15 @@ def main():
     # checked here, before eight replicas load their weights, and handed on to every one of them
     ap.add_argument("--kv-cache-dtype", default=None, choices=["auto", "fp8_e4m3"],
                     help="element type of every replica's KV pools (api_server --kv-cache-dtype)")
+    # multi-LoRA serving: every replica loads the same adapters (a request's "lora" field is relayed like every field)
+    ap.add_argument("--max-loras", type=int, default=None, help="adapter slots of every replica (api_server --max-loras)")
+    ap.add_argument("--max-lora-rank", type=int, default=None, choices=[8, 16, 32, 64])
+    ap.add_argument("--lora", action="append", default=None, metavar="NAME=PATH",
+                    help="a PEFT adapter directory every replica loads at start-up (repeatable)")
     args, passthrough = ap.parse_known_args()
     if args.kv_cache_dtype is not None:
         passthrough = list(passthrough) + ["--kv-cache-dtype", args.kv_cache_dtype]
+    passthrough = list(passthrough) + lora_passthrough(args.max_loras, args.max_lora_rank, args.lora)
     procs = spawn_replicas(args.num_replicas, args.port, passthrough)
     router = ReplicaRouter([f"http://127.0.0.1:{args.port + 1 + i}" for i in range(args.num_replicas)])
     try:

@@ -56,6 +56,8 @@ class Scheduler:
         # rows of the rotary table (LlamaModel.forward raises past it) and the vocabulary size
         self.max_seq_len: Optional[int] = None
         self.vocab_size: Optional[int] = getattr(model_config, "vocab_size", None)
+        # ... and a callable returning the names of the LoRA adapters loaded right now (None: the data plane serves none)
+        self.lora_names = None
 
     # ---- budgets -------------------------------------------------------------------------------------
     def _blocks(self, req: Request, extra_tokens: int = 0) -> int:
@@ -91,6 +93,11 @@ class Scheduler:
                 return f"logit_bias ids must be in [0, {self.vocab_size})"
             if any(t >= self.vocab_size for t in sp.stop_token_ids):
                 return f"stop_token_ids must be in [0, {self.vocab_size})"
+        name = getattr(req, "lora", None)
+        if name is not None:
+            loaded = self.lora_names() if self.lora_names is not None else ()
+            if not isinstance(name, str) or name not in loaded:
+                return f"LoRA adapter {name!r} is not loaded (loaded: {sorted(loaded)})"
         if self.max_seq_len is not None and req.prompt_len + req.output_len > self.max_seq_len:
             return (f"prompt ({req.prompt_len}) + output_len ({req.output_len}) exceeds the model's "
                     f"{self.max_seq_len} rotary positions")

@@ -17,14 +17,16 @@ class StepOutput:
 class RawRequest:
     """What a user submits: a prompt and how many tokens to generate. `prompt_token_ids` may be given
     instead of text (tokenizer-less use: benchmarks, synthetic checkpoints). `sampling_params` (an addition to the
-    reference): None or temperature 0 = greedy; its stop_token_ids end the request before output_len."""
+    reference): None or temperature 0 = greedy; its stop_token_ids end the request before output_len. `lora` (an addition):
+    the name of a loaded LoRA adapter the request runs with, None = the base model."""
 
     def __init__(self, prompt: str, output_len: int, prompt_token_ids: Optional[List[int]] = None, *,
-                 sampling_params: Optional[SamplingParams] = None):
+                 sampling_params: Optional[SamplingParams] = None, lora: Optional[str] = None):
         self.prompt = prompt
         self.output_len = output_len
         self.prompt_token_ids = prompt_token_ids
         self.sampling_params = sampling_params
+        self.lora = lora
 
 
 class Request:
@@ -39,6 +41,9 @@ class Request:
         self.request_id = -1            # row of the block table, assigned when the request is admitted
         self.output_token_ids: List[int] = []
         self.error: Optional[str] = None    # set instead of scheduling when the request can never be served
+        # multi-LoRA serving: the adapter every step of this request runs with (None = the base model); such a request is
+        # never speculated
+        self.lora: Optional[str] = getattr(raw_request, "lora", None)
         # None = greedy. A None seed is resolved here, once: the stream depends on (seed, position) only, so the request
         # draws the same tokens through preemption, swap-out and swap-in, in any batch, on any replica
         # (None also stands for params that ask for nothing — `plain`; a greedy request with penalties, a bias, min_tokens

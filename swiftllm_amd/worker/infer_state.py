@@ -65,3 +65,6 @@ class LlamaInferState:
     # the total lengths, and verify_row_lens (int32 [num_tokens]) is position + 1 of every row.
     verify: bool = False
     verify_row_lens: Optional[torch.Tensor] = None
+    # A LoRA step (some row names an adapter; worker/lora.LoraStep): the step's row -> slot tiles on the device and the
+    # layers' slot stacks. Every layer then runs LlamaTransformerLayer._forward_lora. None: no adapter row — today's paths.
+    lora: Optional[object] = None

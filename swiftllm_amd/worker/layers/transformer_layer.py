@@ -33,6 +33,11 @@ Row-owned projections (rows_decode, bfloat16, on the deferred-norm path): o_proj
 csrc/gemm_rows.hip) and the next projection normalises the raw residual rows while it stages them (linear_silu_gate_nf /
 linear_splitk_nf): no slabs and no consumer launch on that side. A layer whose down projection ran that way returns a
 RawResidual marker instead of an activation tensor.
+
+LoRA steps (infer_state.lora set: some row of the batch names an adapter; EngineConfig.max_loras > 0): `forward` hands the
+whole layer to `_forward_lora`, a straight-line sequence of the plain operators with the adapters' low-rank update added to
+every projection's output (kernels/lora.py, csrc/lora.hip). None of the fused forms above run there — they consume a
+projection's output before a delta could be added — and the layer takes and returns plain tensors.
 """
 import torch
 
@@ -53,6 +58,7 @@ from ..kernels.kvcache_mgmt import store_kvcache
 from ..kernels.prefill_attn import prefill_attention, prefill_attention_paged
 from ..kernels.paged_attn import paged_attention, paged_attention_from_qkv_splitk, paged_attention_verify
 from ..kernels.silu_and_mul import silu_and_mul_inplace
+from ..kernels.lora import lora_apply
 
 
 class LlamaTransformerLayer:
@@ -98,6 +104,8 @@ class LlamaTransformerLayer:
     def forward(self, input_embds, residual_buf: torch.Tensor, k_cache: torch.Tensor,
                 v_cache: torch.Tensor, block_table: torch.Tensor, infer_state):
         cfg, ecfg, w, st = self.model_config, self.engine_config, self.weight, infer_state
+        if getattr(st, "lora", None) is not None:
+            return self._forward_lora(input_embds, residual_buf, k_cache, v_cache, block_table, st)
 
         # residual_buf <- input_embds + residual_buf ; input_embds <- rmsnorm(residual_buf)
         row_scale = None
@@ -115,6 +123,62 @@ class LlamaTransformerLayer:
         else:
             fused_add_rmsnorm_inplace(input_embds, residual_buf, w.attn_norm, cfg.rms_norm_eps)
         return self._forward_after_attn_norm(input_embds, residual_buf, k_cache, v_cache, block_table, st, row_scale)
+
+    def _forward_lora(self, x, residual_buf, k_cache, v_cache, block_table, st):
+        """The layer of a LoRA step: norm, projection + adapter update, rotary, KV store, attention (by the rules of
+        _forward_after_attn_norm), projection + update, norm, projection + update, SiLU-gate, projection + update."""
+        cfg, ecfg, w, sk = self.model_config, self.engine_config, self.weight, self.skinny
+        batch, groups = st.lora.batch, st.lora.layers[self.layer_id]
+        assert not self.kv_fp8, "the LoRA layer path stores and attends 16-bit KV pools only"
+        fused_add_rmsnorm_inplace(x, residual_buf, w.attn_norm, cfg.rms_norm_eps)
+        t = x.shape[0]
+        if w.qkv_proj is not None:
+            qkv = linear(x, w.qkv_proj, sk)
+            lora_apply(x, qkv, groups.qkv_proj, batch)
+            q, k, v = self._split_qkv(qkv)
+        else:
+            q, k, v = linear(x, w.q_proj, sk), linear(x, w.k_proj, sk), linear(x, w.v_proj, sk)
+            lora_apply(x, q, groups.q_proj, batch)
+            lora_apply(x, k, groups.k_proj, batch)
+            lora_apply(x, v, groups.v_proj, batch)
+            q = q.view(t, cfg.num_q_heads, cfg.head_dim)
+            k, v = k.view(t, cfg.num_kv_heads, cfg.head_dim), v.view(t, cfg.num_kv_heads, cfg.head_dim)
+        rotary_embedding_inplace(q, k, st)
+        if not st.ignore_kvcache:
+            store_kvcache(k, v, k_cache, v_cache, block_table, cfg, ecfg, st, self.layer_id)
+
+        # attention output overwrites the (already consumed) normed activations
+        o = x.view(-1, cfg.num_q_heads, cfg.head_dim)
+        p = st.num_prefill_tokens
+        if st.num_prefill_seqs > 0 and st.num_decoding_seqs > 0:
+            assert not st.ignore_kvcache
+            stored = torch.cuda.Event()
+            stored.record()
+            self._prefill_attention(q, k, v, o, k_cache, v_cache, block_table, st)
+            side = self.decoding_piggyback_stream
+            with torch.cuda.stream(side):
+                side.wait_event(stored)
+                paged_attention(q[p:], k_cache, v_cache, block_table, cfg, ecfg, st, self.layer_id, o[p:])
+                decoded = torch.cuda.Event()
+                decoded.record()
+            torch.cuda.current_stream().wait_event(decoded)
+        elif st.num_prefill_seqs > 0:
+            self._prefill_attention(q, k, v, o, k_cache, v_cache, block_table, st)
+        elif st.num_decoding_seqs > 0:
+            assert not st.ignore_kvcache
+            paged_attention(q, k_cache, v_cache, block_table, cfg, ecfg, st, self.layer_id, o)
+        q = k = v = qkv = None
+
+        attn_out = linear(x, w.o_proj, sk)
+        lora_apply(x, attn_out, groups.o_proj, batch)
+        fused_add_rmsnorm_inplace(attn_out, residual_buf, w.ffn_norm, cfg.rms_norm_eps)
+        up_gate = linear(attn_out, w.up_gate_proj, sk)
+        lora_apply(attn_out, up_gate, groups.up_gate_proj, batch)
+        silu_and_mul_inplace(up_gate)
+        act = up_gate[:, :cfg.ffn_inter_dim]
+        down = linear(act, w.down_proj, sk)
+        lora_apply(act, down, groups.down_proj, batch)
+        return down
 
     def _slab_fed_attention_applies(self, st) -> bool:
         """Pure-decode batch on the path `fused qkv slabs -> (rotary + KV store + paged attention)` in one launch."""

@@ -42,6 +42,7 @@ from .kernels.paged_attn import verify_max_tokens
 from .kernels.rmsnorm import fused_add_rmsnorm_from_splitk, rmsnorm_inplace
 from .kernels import logits_process
 from .kernels.sampling import device_args, pack_params
+from .lora import LoraBatch, LoraStaging, LoraStep, LoraStore, parse_lora_modules, rows_of_sequences
 from .layers.pre_layer import LlamaPreLayer
 from .layers.transformer_layer import LlamaTransformerLayer
 from .layers.post_layer import LlamaPostLayer
@@ -133,6 +134,10 @@ class LlamaModel:
         # speculative decoding: drafts one verify step takes per sequence (forward_verify) = the verify attention kernel's
         # tokens per sequence (16 / G) minus the last accepted token that leads them; 0 with FP8 pools (no instantiation)
         self.max_draft_tokens = 0 if self.kv_fp8 else max(0, verify_max_tokens(self.model_config) - 1)
+        # multi-LoRA serving (EngineConfig.max_loras > 0): the slot stacks of every layer's projections (worker/lora.py),
+        # allocated by load_weights; None = off
+        self.lora_store = None
+        self._lora_staging = LoraStaging()      # pinned staging of a LoRA step's tile lists + the t workspace, reused
 
     # ------------------------------------------------------------------------------------------------
     @torch.inference_mode()
@@ -163,6 +168,36 @@ class LlamaModel:
         ecfg = self.engine_config
         self._ensure_sampling_rows(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
         self._ensure_edit_buffer(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)), 0)
+        # (... and so are the adapter slot stacks: the KV pool is sized with them)
+        if int(getattr(ecfg, "max_loras", 0) or 0) > 0:
+            self.lora_store = LoraStore(self.model_config, int(ecfg.max_loras), int(ecfg.max_lora_rank), self.dtype,
+                                        self.device, fuse_qkv=self.weight.layers[0].qkv_proj is not None)
+            print(f"[Model] LoRA: {ecfg.max_loras} adapter slots of rank <= {ecfg.max_lora_rank}, "
+                  f"{self.lora_store.nbytes() / 2**20:.1f} MiB", flush=True)
+            for name, path in parse_lora_modules(getattr(ecfg, "lora_modules", None)).items():
+                self.load_lora(name, path)
+
+    # ---- multi-LoRA serving ------------------------------------------------------------------------------------------
+    def _require_lora_store(self) -> LoraStore:
+        if self.lora_store is None:
+            raise ValueError("this model serves no LoRA adapters: EngineConfig.max_loras is 0 (or load_weights has not run)")
+        return self.lora_store
+
+    @torch.inference_mode()
+    def load_lora(self, name: str, path: Optional[str] = None, *, state_dict: Optional[dict] = None,
+                  config: Optional[dict] = None) -> int:
+        """Load a PEFT adapter (a directory, or its state dict + adapter config) into a free slot; returns the slot.
+        Raises ValueError (worker/lora.LoraError) with the reason for anything the LoRA layer path cannot serve."""
+        return self._require_lora_store().load(name, path, state_dict=state_dict, config=config)
+
+    @torch.inference_mode()
+    def unload_lora(self, name: str) -> int:
+        """Zero the adapter's slot and free it. The caller makes sure no sequence in flight names it."""
+        return self._require_lora_store().unload(name)
+
+    def loras(self) -> dict:
+        """Loaded adapters: name -> slot ({} when the model serves none)."""
+        return {} if self.lora_store is None else self.lora_store.names()
 
     def _tune_routes(self):
         """Which side serves the 65..256-token decode projections of THIS model on THIS device is decided here, once, before
@@ -531,7 +566,7 @@ class LlamaModel:
         return self.post_layer.forward(x, infer_state)
 
     def _engine_applies(self, st) -> bool:
-        return (self._engine is not None and st.num_prefill_seqs == 0 and st.batch_size == 1
+        return (self._engine is not None and getattr(st, "lora", None) is None and st.num_prefill_seqs == 0 and st.batch_size == 1
                 and st.num_decoding_seqs == 1 and not st.ignore_kvcache and self.k_cache is not None)
 
     def _engine_failed(self, code: int):
@@ -737,7 +772,7 @@ class LlamaModel:
     def forward(self, input_ids_list: List[List[int]], seq_ids_list: List[int],
                 decoding_seq_lens_list: List[int], ignore_kvcache: bool = False,
                 sampling_params: Optional[List[Optional[SamplingParams]]] = None,
-                prefill_ctx_lens: Optional[List[int]] = None) -> List[int]:
+                prefill_ctx_lens: Optional[List[int]] = None, lora: Optional[List[Optional[str]]] = None) -> List[int]:
         """One iteration: prefill sequences first, then decoding sequences (one token each, their
         lengths in `decoding_seq_lens_list` INCLUDE that token). Returns the next token of every
         sequence: greedy (the reference, model.py:252-359), or — for the entries of `sampling_params`
@@ -748,9 +783,14 @@ class LlamaModel:
         in the KV pool from earlier calls. Its `input_ids` are then the next chunk of its prompt: the chunk is stored
         behind the context and attends to the pool (csrc/prefill_attn_paged.hip). The token returned for it follows the
         chunk's last token — the caller ignores it for every chunk but the last; a sampled draw is keyed by position, so
-        the final chunk draws what a whole-prompt prefill draws from the same logits. None or all zeros: today's path."""
+        the final chunk draws what a whole-prompt prefill draws from the same logits. None or all zeros: today's path.
+
+        `lora` (multi-LoRA serving; aligned with `input_ids_list`): the name of a loaded adapter, or None, per sequence.
+        None or all None: today's call, launch for launch. Otherwise the step runs the LoRA layer path eagerly (no
+        hipGraph, no look-ahead): every row of a named sequence gets its adapter's low-rank update on every projection."""
         if len(input_ids_list) == 0:
             return []   # the reference's idle engine calls forward([], [], []) in a loop
+        lora_slots = self._resolve_lora(lora, len(input_ids_list))
         _require_hip_device()
         prefill_ctx_lens = self._check_prefill_ctx(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache,
                                                    prefill_ctx_lens)
@@ -771,16 +811,28 @@ class LlamaModel:
         try:
             try:
                 return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                          prefill_ctx_lens, edits)
+                                          prefill_ctx_lens, edits, lora_slots)
             except _decode_engine.DecodeEngineError as exc:
                 # bounded hand-off timed out inside the persistent one-sequence step: its KV writes are re-done below with
                 # the same values by the multi-launch HIP path, which serves one-sequence steps from here on
                 self._engine_failed(int(str(exc)))
                 return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                          prefill_ctx_lens, edits)
+                                          prefill_ctx_lens, edits, lora_slots)
         except BaseException:
             self._rollback_histories(undo)
             raise
+
+    def _resolve_lora(self, lora, num_seqs: int):
+        """Per-sequence slots (-1 = no adapter) of a LoRA step, or None when no sequence names an adapter. Host only: an
+        unknown name is refused before anything is allocated or launched."""
+        if lora is None:
+            return None
+        if len(lora) != num_seqs:
+            raise ValueError("lora must be aligned with input_ids_list")
+        if all(n is None for n in lora):
+            return None
+        store = self._require_lora_store()
+        return [-1 if n is None else store.slot_of(n) for n in lora]
 
     def _rollback_histories(self, undo):
         for rec in reversed(undo):
@@ -875,11 +927,14 @@ class LlamaModel:
         return ctx
 
     def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
-                      prefill_ctx_lens=None, edits=None):
+                      prefill_ctx_lens=None, edits=None, lora_slots=None):
         prof = self._host_prof
         t0 = time.perf_counter() if prof is not None else 0.0
         sampled = sampling is not None
         processed = edits is not None
+        if lora_slots is not None:
+            return self._forward_step_lora(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
+                                           prefill_ctx_lens, edits, lora_slots)
         la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling, processed)
         if la is not None:      # the step that was prepared while the previous one ran: blocks, then the launch
             self.gpu_block_manager.allocate_blocks_for_seqs(la.seq_ids, la.lens)   # (the real sequences only)
@@ -957,6 +1012,39 @@ class LlamaModel:
                          ("wait_tokens", t5 - t4), ("calls", 1.0)):
             prof[name] = prof.get(name, 0.0) + dt
         return out
+
+    def _forward_step_lora(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
+                           prefill_ctx_lens, edits, lora_slots):
+        """A step with at least one adapter row: the plain plan of the batch (never padded to a replay bucket), eager
+        launches, the prepared look-ahead dropped; the row -> slot tiles go up in a buffer of their own."""
+        self._lookahead = None
+        num_real = len(input_ids_list)
+        plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
+                          self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
+        plan.num_real_seqs = num_real
+        longest = max(plan.seq_lengths_list)
+        if longest > self._cos_cached.shape[0]:
+            raise RuntimeError(
+                f"sequence length {longest} exceeds the rotary table ({self._cos_cached.shape[0]} positions = "
+                "max_position_embeddings * rope_scaling + 128); use a checkpoint with rope scaling")
+        if not ignore_kvcache:
+            self.gpu_block_manager.allocate_blocks_for_seqs(seq_ids_list, plan.seq_lengths_list[:num_real])
+        dev = self._upload_plan(plan)
+        if sampling is not None:
+            self._upload_sampling(sampling, plan.batch_size)
+        if edits is not None:
+            self._upload_edits(edits, plan.batch_size)
+        num_prefill = num_real - len(decoding_seq_lens_list)
+        row_slots = rows_of_sequences(lora_slots, [len(ids) for ids in input_ids_list[:num_prefill]])
+        state = self._make_infer_state(plan, dev, ignore_kvcache, sampling is not None, edits is not None)
+        state.lora = LoraStep(LoraBatch(row_slots, self.lora_store.max_loras, self.device, self._lora_staging),
+                              self.lora_store.layers)
+        tokens = self._forward(dev["input_ids"], state)[:num_real]
+        if self.after_launch_hook is not None:
+            self.after_launch_hook()
+        if self._host_prof is not None:
+            self._host_prof["calls"] = self._host_prof.get("calls", 0.0) + 1.0
+        return self._tokens_to_host(tokens)
 
     @torch.inference_mode()
     def forward_verify(self, input_ids_list: List[List[int]], seq_ids_list: List[int],
