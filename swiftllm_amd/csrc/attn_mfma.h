@@ -1,7 +1,6 @@
 // attn_mfma.h — the matrix-core pieces the attention kernels share (gfx950): MFMA wrappers, the LDS transpose read, the
-// 16-lane-row reductions, the wave-private tile of decode attention, and the end of decode phase 1, which does not depend
-// on how the KV pool is stored (paged_attn.hip: 16-bit pools, paged_attn_fp8.hip: e4m3 pools): the merge of a workgroup's
-// waves.
+// 16-lane-row reductions and the wave-private tile of decode attention with its attend_block (what the decode kernels
+// share beyond that: decode_attn.h).
 #pragma once
 
 #include "swl_common.h"
@@ -150,42 +149,6 @@ __device__ __forceinline__ void attend_block_mfma(const vec8_t<T> (&qb)[MfmaTile
         const short4_t vf = lds_tr_read(stage + (4 * q + (i16 >> 2)) * MT::VRS + 16 * mm + 4 * (i16 & 3));
         acc[mm] = mfma16x16(vf, ph, acc[mm]);
         acc[mm] = mfma16x16(vf, pl, acc[mm]);
-    }
-}
-
-// ---- decode phase 1, end of the kernel -------------------------------------------------------------------------------
-// Merge the NW waves of the workgroup (after the barrier that follows their LDS writes) and write the partial of this
-// split — or the final output when there is one split. P = the kernel's parameter struct (o_direct, mid_o, mid_lse, H,
-// num_seq_blocks, o_tok_stride). VSCALE: the normalised output is multiplied by v_scale in fp32 before the one rounding
-// (FP8 pools); without it the argument is not read and no multiply is emitted.
-template <typename T, int D, int G, int NW, bool VSCALE, typename P>
-__device__ __forceinline__ void merge_waves_write(const P &p, const float (&sm_ml)[NW][G][2],
-                                                  const float (&sm_acc)[NW][G][D], float c, float v_scale, int kvh,
-                                                  int seq, int split) {
-    const int nsb = p.num_seq_blocks;
-    for (int oidx = threadIdx.x; oidx < G * D; oidx += NW * 64) {
-        const int g = oidx / D;
-        const int d = oidx % D;
-        float M = sm_ml[0][g][0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) M = fmaxf(M, sm_ml[w][g][0]);
-        float Lsum = 0.f, A = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const float wgt = fast_exp2((sm_ml[w][g][0] - M) * c);
-            Lsum = fmaf(sm_ml[w][g][1], wgt, Lsum);
-            A = fmaf(sm_acc[w][g][d], wgt, A);
-        }
-        float out = A / Lsum;
-        if constexpr (VSCALE) out *= v_scale;
-        const int head = kvh * G + g;
-        if (nsb == 1) {
-            static_cast<T *>(p.o_direct)[seq * p.o_tok_stride + static_cast<int64_t>(head) * D + d] = to_t<T>(out);
-        } else {
-            const int64_t part = (static_cast<int64_t>(seq) * p.H + head) * nsb + split;
-            p.mid_o[part * D + d] = out;
-            if (d == 0) p.mid_lse[part] = fast_log2(Lsum) + M * c;
-        }
     }
 }
 

@@ -27,28 +27,11 @@
 // paged_attn.py:72-73; ours is closer to the exact value). Partials use the reference's format:
 // mid_o = acc/sum (normalised), mid_lse = log2(sum) + max in the scaled base-2 domain
 // (paged_attn.py:106-108), so phase 1 can be compared with the reference's phase 1 directly.
-#include "attn_mfma.h"
+#include "decode_attn.h"
 
 namespace swl {
 
-template <int V>
-struct IntTag {
-    static constexpr int value = V;
-};
-
-struct PagedAttnParams {
-    void *o_direct;
-    const void *q;
-    const void *k_cache;
-    const void *v_cache;
-    const int *block_table;
-    const int *seq_ids;
-    const int *seq_lens;
-    float *mid_o;
-    float *mid_lse;
-    float scale_log2e;
-    int H, KVH, L, layer, max_blocks_per_seq, seq_block_size, num_seq_blocks;
-    int64_t q_tok_stride, o_tok_stride;
+struct PagedAttnParams : DecodeAttnParams {
     // QKV variant: q/k/v of the new token are still the split-K partial slabs of the fused qkv projection
     const float *qkv_slabs; // [ks][Bd][(H + 2*KVH) * D] fp32
     int ks;
@@ -156,9 +139,6 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_phase1_kernel(PagedAttnPar
             Vd[i] = load8_nt(vc + base + i * 512);
         }
     };
-    auto load_block = [&](int b, vec8_t<T>(&Kd)[NI], vec8_t<T>(&Vd)[NI]) {
-        load_phys(bt[b], Kd, Vd); // scalar load: b is wave-uniform
-    };
     auto attend = [&](int b, vec8_t<T>(&Kd)[NI], vec8_t<T>(&Vd)[NI]) {
         const int tok0 = b * kBlk;
         if constexpr (MF)
@@ -186,9 +166,7 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_phase1_kernel(PagedAttnPar
     };
     // the first ND blocks of this wave go into slots 0..ND-1 (QKV: issued from inside the prologue)
     auto prefetch_kv = [&](int b0, auto lo_tag, auto hi_tag) {
-#pragma unroll
-        for (int d = decltype(lo_tag)::value; d < decltype(hi_tag)::value; ++d)
-            if (b0 + d * NW < blk_end) load_block(b0 + d * NW, Kr[d], Vr[d]);
+        kv_ring_prefetch<decltype(lo_tag)::value, decltype(hi_tag)::value, NW>(b0, blk_end, bt, Kr, Vr, load_phys);
     };
     constexpr int NDP = ND < 2 ? ND : 2;    // QKV: slots requested while the slab loads of the prologue are pending
 
@@ -332,65 +310,10 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_phase1_kernel(PagedAttnPar
     }
 #pragma unroll
     for (int mm = 0; mm < MT::OS; ++mm) acc4[mm] = float4_t{0.f, 0.f, 0.f, 0.f};
-    // steady state: every refill is unconditional, so the waits between slots are exact counted vmcnt waits (a
-    // conditional load in the body makes the compiler wait for one slot more than needed); slot d attends block
-    // b + d*NW and is refilled with block b + (d+ND)*NW
-    if (b + (2 * ND - 1) * NW < blk_end) {
-        // The first ND requests above are conditional (short sequence blocks), so on entry the compiler cannot know how
-        // many loads are outstanding and would size EVERY wait of the loop for the fewest — i.e. wait for the newest
-        // slot before touching the oldest (seen in the ISA of the r01 kernel as well: its prefetch never overlapped
-        // its own compute). One full wait here — all ND slots were requested long ago, this is the pipeline fill —
-        // hands the loop an exact state; from then on every wait in it is a counted vmcnt.
-        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0), expcnt/lgkmcnt untouched
-      do {
-#pragma unroll
-        for (int d = 0; d < ND; ++d) {
-            // scheduling fences: left alone, the compiler computes all ND blocks back to back behind ONE vmcnt(0)
-            // and sinks every refill to the end of the iteration — nothing in flight while it computes (seen in
-            // the ISA: 34 us instead of 27 at batch 32 x 1k). Pinned, the wait before slot d+1 is a counted one.
-            // (the block-table entry of the refill is requested BEFORE the block is attended: behind the fence its
-            // scalar-load round trip would sit between every attend and the refill it feeds)
-            const int64_t phys_next = bt[b + (d + ND) * NW];
-            __builtin_amdgcn_sched_barrier(0);
-            attend(b + d * NW, Kr[d], Vr[d]);
-            __builtin_amdgcn_sched_barrier(0);
-            load_phys(phys_next, Kr[d], Vr[d]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        b += ND * NW;
-      } while (b + (2 * ND - 1) * NW < blk_end);
-    }
-    // drain: at most 2*ND-1 blocks left, the first ND of them already in their slots
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        if (b + d * NW < blk_end) {
-            attend_tail(b + d * NW, Kr[d], Vr[d]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (b + (d + ND) * NW < blk_end) load_block(b + (d + ND) * NW, Kr[d], Vr[d]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < ND - 1; ++d)
-        if (b + (d + ND) * NW < blk_end) attend_tail(b + (d + ND) * NW, Kr[d], Vr[d]);
+    kv_ring_stream<ND, NW>(b, blk_end, bt, Kr, Vr, load_phys, attend, attend_tail);
 
     if constexpr (MF) {
-        // O^T of the last block is stored by DS instructions below (swl_common.h)
-#pragma unroll
-        for (int mm = 0; mm < MT::OS; ++mm) mfma_results_tie(acc4[mm]);
-        mfma_results_ready<4>(acc4[MT::OS - 1]);
-        // the four lanes (q = 0..3) of a head share m and each hold the row sum of their own tokens; O^T is complete
-        const float lt = rows_allreduce_sum(l[0]);
-        if (mh < G) {
-            if (mq == 0) {
-                sm_ml[wave][mh][0] = m[0];
-                sm_ml[wave][mh][1] = lt;
-            }
-#pragma unroll
-            for (int mm = 0; mm < MT::OS; ++mm)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sm_acc[wave][mh][16 * mm + 4 * mq + r] = acc4[mm][r];
-        }
+        mfma_wave_finish(m[0], l[0], acc4, sm_ml, sm_acc, wave, lane);
     } else {
     // ---- merge the TPI rows of this wave (each row holds tokens == row mod TPI) ----------------
 #pragma unroll
@@ -495,39 +418,15 @@ __global__ __launch_bounds__(64) void paged_attn_phase2_kernel(
     }
 }
 
-template <typename T, int D, int G, bool QKV>
-static int launch_phase1(const PagedAttnParams &p, int Bd, hipStream_t stream) {
-    const dim3 grid(p.num_seq_blocks, p.KVH, Bd);
-    // >= 32 KV blocks per sequence block: 8-wave workgroups (>= 4 blocks per wave); else 4 waves.
-    // (the VALU variant of G = 8 would need > 256 registers per lane; the matrix-core one, G >= 2, does not.)
-    if (p.seq_block_size >= 32 * kBlk)
-        hipLaunchKernelGGL((paged_attn_phase1_kernel<T, D, G, 8, QKV>), grid, dim3(512), 0, stream, p, p.block_table,
-                           p.seq_lens, p.seq_ids);
-    else
-        hipLaunchKernelGGL((paged_attn_phase1_kernel<T, D, G, 4, QKV>), grid, dim3(256), 0, stream, p, p.block_table,
-                           p.seq_lens, p.seq_ids);
-    return check_launch();
-}
-
-template <typename T, int D, bool QKV>
-static int dispatch_phase1_g(const PagedAttnParams &p, int Bd, int G, hipStream_t stream) {
-    switch (G) {
-    case 1: return launch_phase1<T, D, 1, QKV>(p, Bd, stream);
-    case 2: return launch_phase1<T, D, 2, QKV>(p, Bd, stream);
-    case 4: return launch_phase1<T, D, 4, QKV>(p, Bd, stream);
-    case 8: return launch_phase1<T, D, 8, QKV>(p, Bd, stream);
-    default: return SWL_ERR_UNSUPPORTED;
-    }
-}
-
-template <typename T, bool QKV = false>
-static int dispatch_phase1(const PagedAttnParams &p, int Bd, int D, int G, hipStream_t stream) {
-    switch (D) {
-    case 32: return dispatch_phase1_g<T, 32, QKV>(p, Bd, G, stream);
-    case 64: return dispatch_phase1_g<T, 64, QKV>(p, Bd, G, stream);
-    case 128: return dispatch_phase1_g<T, 128, QKV>(p, Bd, G, stream);
-    default: return SWL_ERR_UNSUPPORTED;
-    }
+template <typename T, bool QKV>
+static int launch_phase1(const PagedAttnParams &p, const int *bt, const int *lens, const int *ids, int Bd, int D,
+                         hipStream_t stream) {
+    return dispatch_decode_attn(D, p.H / p.KVH, p.seq_block_size, [&](auto d, auto g, auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        hipLaunchKernelGGL((paged_attn_phase1_kernel<T, decltype(d)::value, decltype(g)::value, NW, QKV>),
+                           dim3(p.num_seq_blocks, p.KVH, Bd), dim3(NW * 64), 0, stream, p, bt, lens, ids);
+        return check_launch();
+    });
 }
 
 template <typename T>
@@ -569,47 +468,18 @@ extern "C" int swl_paged_attn_phase1(void *o_direct, const void *q, const void *
     if (num_decoding_seqs < 0) return SWL_ERR_BAD_ARG;
     if (num_decoding_seqs == 0 || num_seq_blocks == 0) return SWL_OK;
     if (!q || !k_cache || !v_cache || !block_table || !seq_ids || !seq_lens) return SWL_ERR_BAD_ARG;
-    if (num_seq_blocks < 0 || num_q_heads <= 0 || num_kv_heads <= 0 ||
-        num_q_heads % num_kv_heads != 0 || num_layers <= 0 || cur_layer < 0 ||
-        cur_layer >= num_layers || max_blocks_per_seq <= 0)
-        return SWL_ERR_BAD_ARG;
-    if (block_size != swl::kBlk) return SWL_ERR_UNSUPPORTED;
-    if (seq_block_size <= 0 || seq_block_size % block_size != 0) return SWL_ERR_BAD_ARG;
-    if (num_seq_blocks == 1 ? !o_direct : (!mid_o || !mid_lse)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(q) || !swl::aligned16(k_cache) || !swl::aligned16(v_cache) ||
-        (q_tok_stride & 7) || q_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim)
-        return SWL_ERR_BAD_ARG;
-    // o is only looked at when it is given (it may be NULL when the sequences are split)
-    if (o_direct && (!swl::aligned16(o_direct) || (o_tok_stride & 7) ||
-                     o_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim))
-        return SWL_ERR_BAD_ARG;
-    if (num_seq_blocks > 1 && ((reinterpret_cast<uintptr_t>(mid_o) | reinterpret_cast<uintptr_t>(mid_lse)) & 3u))
-        return SWL_ERR_BAD_ARG;
-    if (num_decoding_seqs > 65535 || num_kv_heads > 65535) return SWL_ERR_UNSUPPORTED;
+    const swl::DecodeAttnArgs a{o_direct, q, k_cache, v_cache, q_tok_stride, o_tok_stride, num_q_heads, num_kv_heads,
+                                head_dim, num_layers, block_size, cur_layer, max_blocks_per_seq, seq_block_size,
+                                num_seq_blocks};
+    if (const int rc = swl::check_decode_geometry(a)) return rc;
+    if (const int rc = swl::check_decode_layout(a)) return rc;
+    if (!swl::phase1_outputs_ok(o_direct, mid_o, mid_lse, num_seq_blocks)) return SWL_ERR_BAD_ARG;
+    if (!swl::decode_grid_fits(num_decoding_seqs, num_kv_heads)) return SWL_ERR_UNSUPPORTED;
     swl::PagedAttnParams p{};
-    p.o_direct = o_direct;
-    p.q = q;
-    p.k_cache = k_cache;
-    p.v_cache = v_cache;
-    p.block_table = block_table;
-    p.seq_ids = seq_ids;
-    p.seq_lens = seq_lens;
-    p.mid_o = mid_o;
-    p.mid_lse = mid_lse;
-    p.scale_log2e = softmax_scale * 1.44269504088896340736f;
-    p.H = num_q_heads;
-    p.KVH = num_kv_heads;
-    p.L = num_layers;
-    p.layer = cur_layer;
-    p.max_blocks_per_seq = max_blocks_per_seq;
-    p.seq_block_size = seq_block_size;
-    p.num_seq_blocks = num_seq_blocks;
-    p.q_tok_stride = q_tok_stride;
-    p.o_tok_stride = o_tok_stride;
-    const int G = num_q_heads / num_kv_heads;
+    swl::fill_decode_params(p, a, mid_o, mid_lse, softmax_scale);
     SWL_DISPATCH_DTYPE(dtype, T, {
-        return swl::dispatch_phase1<T>(p, num_decoding_seqs, head_dim, G,
-                                       static_cast<hipStream_t>(stream));
+        return swl::launch_phase1<T, false>(p, block_table, seq_lens, seq_ids, num_decoding_seqs, head_dim,
+                                            static_cast<hipStream_t>(stream));
     });
 }
 
@@ -648,13 +518,9 @@ extern "C" int swl_paged_attn_decode(void *o, const void *q, const void *k_cache
     if (num_decoding_seqs < 0) return SWL_ERR_BAD_ARG;
     if (num_decoding_seqs == 0 || num_seq_blocks == 0) return SWL_OK;
     if (!o) return SWL_ERR_BAD_ARG;
-    float *mid_o = nullptr, *mid_lse = nullptr;
-    if (num_seq_blocks > 1) {
-        if (!scratch || !swl::aligned16(scratch)) return SWL_ERR_BAD_ARG;
-        mid_o = static_cast<float *>(scratch);
-        mid_lse = mid_o + static_cast<size_t>(num_decoding_seqs) * num_q_heads * num_seq_blocks *
-                              head_dim;
-    }
+    float *mid_o, *mid_lse;
+    if (!swl::split_scratch(scratch, num_decoding_seqs, num_q_heads, head_dim, num_seq_blocks, mid_o, mid_lse))
+        return SWL_ERR_BAD_ARG;
     int rc = swl_paged_attn_phase1(o, q, k_cache, v_cache, block_table, seq_ids, seq_lens, mid_o,
                                    mid_lse, softmax_scale, num_decoding_seqs, num_q_heads,
                                    num_kv_heads, head_dim, num_layers, block_size, cur_layer,
@@ -669,14 +535,49 @@ extern "C" int swl_paged_attn_decode(void *o, const void *q, const void *k_cache
 /* Decode attention fed by the split-K slabs of the fused qkv projection: rotary + KV-store of the new token run
  * in the attention kernel's prologue (no launch of their own), the new k/v are attended from registers. */
 static int paged_attn_decode_qkv_impl(void *o, const float *qkv_slabs, int32_t k_splits, const void *cos_table,
-                                      const void *sin_table, const int32_t *pos_idx, void *k_cache, void *v_cache,
-                                      const int32_t *block_table, const int32_t *seq_ids, const int32_t *seq_lens,
-                                      void *scratch, float softmax_scale, int32_t num_decoding_seqs,
-                                      int32_t num_q_heads, int32_t num_kv_heads, int32_t head_dim, int32_t num_layers,
-                                      int32_t block_size, int32_t cur_layer, int32_t max_blocks_per_seq,
-                                      int32_t seq_block_size, int32_t num_seq_blocks, int64_t o_tok_stride, int32_t dtype,
-                                      swl_stream_t stream, const float *row_ssq, int32_t ssq_parts, int32_t hidden,
-                                      float eps, bool merge = true);
+                                         const void *sin_table, const int32_t *pos_idx, void *k_cache,
+                                         void *v_cache, const int32_t *block_table, const int32_t *seq_ids,
+                                         const int32_t *seq_lens, void *scratch, float softmax_scale,
+                                         int32_t num_decoding_seqs, int32_t num_q_heads, int32_t num_kv_heads,
+                                         int32_t head_dim, int32_t num_layers, int32_t block_size,
+                                         int32_t cur_layer, int32_t max_blocks_per_seq, int32_t seq_block_size,
+                                         int32_t num_seq_blocks, int64_t o_tok_stride, int32_t dtype,
+                                         swl_stream_t stream, const float *row_ssq, int32_t ssq_parts, int32_t hidden,
+                                         float eps, bool merge) {
+    if (num_decoding_seqs < 0) return SWL_ERR_BAD_ARG;
+    if (num_decoding_seqs == 0 || num_seq_blocks == 0) return SWL_OK;
+    if ((!o && (merge || num_seq_blocks == 1)) || !qkv_slabs || !cos_table || !sin_table || !k_cache || !v_cache ||
+        !block_table || !seq_ids || !seq_lens || k_splits <= 0)
+        return SWL_ERR_BAD_ARG;
+    const swl::DecodeAttnArgs a{o, qkv_slabs, k_cache, v_cache, 0, o_tok_stride, num_q_heads, num_kv_heads, head_dim,
+                                num_layers, block_size, cur_layer, max_blocks_per_seq, seq_block_size, num_seq_blocks};
+    if (const int rc = swl::check_decode_geometry(a)) return rc;
+    if (const int rc = swl::check_decode_layout(a, false)) return rc;
+    if (!swl::aligned16(cos_table) || !swl::aligned16(sin_table)) return SWL_ERR_BAD_ARG;
+    if (!swl::decode_grid_fits(num_decoding_seqs, num_kv_heads)) return SWL_ERR_UNSUPPORTED;
+    float *mid_o, *mid_lse;
+    if (!swl::split_scratch(scratch, num_decoding_seqs, num_q_heads, head_dim, num_seq_blocks, mid_o, mid_lse))
+        return SWL_ERR_BAD_ARG;
+    swl::PagedAttnParams p{};
+    swl::fill_decode_params(p, a, mid_o, mid_lse, softmax_scale);
+    p.qkv_slabs = qkv_slabs;
+    p.ks = k_splits;
+    p.cos_t = cos_table;
+    p.sin_t = sin_table;
+    p.pos_idx = pos_idx;
+    p.row_ssq = row_ssq;
+    p.ssq_parts = ssq_parts;
+    p.hidden = hidden;
+    p.eps = eps;
+    int rc;
+    SWL_DISPATCH_DTYPE(dtype, T, {
+        rc = swl::launch_phase1<T, true>(p, block_table, seq_lens, seq_ids, num_decoding_seqs, head_dim,
+                                         static_cast<hipStream_t>(stream));
+    });
+    if (rc != SWL_OK || num_seq_blocks == 1 || !merge) return rc;
+    return swl_paged_attn_phase2(o, mid_o, mid_lse, seq_lens, num_decoding_seqs, num_q_heads, head_dim,
+                                 seq_block_size, num_seq_blocks, o_tok_stride, dtype, stream);
+}
 
 extern "C" int swl_paged_attn_decode_qkv(void *o, const float *qkv_slabs, int32_t k_splits, const void *cos_table,
                                          const void *sin_table, const int32_t *pos_idx, void *k_cache,
@@ -690,7 +591,8 @@ extern "C" int swl_paged_attn_decode_qkv(void *o, const float *qkv_slabs, int32_
     return paged_attn_decode_qkv_impl(o, qkv_slabs, k_splits, cos_table, sin_table, pos_idx, k_cache, v_cache, block_table,
                                       seq_ids, seq_lens, scratch, softmax_scale, num_decoding_seqs, num_q_heads,
                                       num_kv_heads, head_dim, num_layers, block_size, cur_layer, max_blocks_per_seq,
-                                      seq_block_size, num_seq_blocks, o_tok_stride, dtype, stream, nullptr, 0, 0, 0.f);
+                                      seq_block_size, num_seq_blocks, o_tok_stride, dtype, stream, nullptr, 0, 0, 0.f,
+                                      true);
 }
 
 /* swl_paged_attn_decode_qkv on the slabs of a qkv projection whose input had its RMSNorm scale deferred
@@ -714,76 +616,7 @@ extern "C" int swl_paged_attn_decode_qkv_rs(void *o, const float *qkv_slabs, int
                                       seq_ids, seq_lens, scratch, softmax_scale, num_decoding_seqs, num_q_heads,
                                       num_kv_heads, head_dim, num_layers, block_size, cur_layer, max_blocks_per_seq,
                                       seq_block_size, num_seq_blocks, o_tok_stride, dtype, stream, row_ssq, ssq_parts,
-                                      hidden, eps);
-}
-
-static int paged_attn_decode_qkv_impl(void *o, const float *qkv_slabs, int32_t k_splits, const void *cos_table,
-                                         const void *sin_table, const int32_t *pos_idx, void *k_cache,
-                                         void *v_cache, const int32_t *block_table, const int32_t *seq_ids,
-                                         const int32_t *seq_lens, void *scratch, float softmax_scale,
-                                         int32_t num_decoding_seqs, int32_t num_q_heads, int32_t num_kv_heads,
-                                         int32_t head_dim, int32_t num_layers, int32_t block_size,
-                                         int32_t cur_layer, int32_t max_blocks_per_seq, int32_t seq_block_size,
-                                         int32_t num_seq_blocks, int64_t o_tok_stride, int32_t dtype,
-                                         swl_stream_t stream, const float *row_ssq, int32_t ssq_parts, int32_t hidden,
-                                         float eps, bool merge) {
-    if (num_decoding_seqs < 0) return SWL_ERR_BAD_ARG;
-    if (num_decoding_seqs == 0 || num_seq_blocks == 0) return SWL_OK;
-    if ((!o && (merge || num_seq_blocks == 1)) || !qkv_slabs || !cos_table || !sin_table || !k_cache || !v_cache || !block_table || !seq_ids ||
-        !seq_lens || k_splits <= 0)
-        return SWL_ERR_BAD_ARG;
-    if (num_seq_blocks < 0 || num_q_heads <= 0 || num_kv_heads <= 0 || num_q_heads % num_kv_heads != 0 ||
-        num_layers <= 0 || cur_layer < 0 || cur_layer >= num_layers || max_blocks_per_seq <= 0)
-        return SWL_ERR_BAD_ARG;
-    if (block_size != swl::kBlk) return SWL_ERR_UNSUPPORTED;
-    if (seq_block_size <= 0 || seq_block_size % block_size != 0) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(qkv_slabs) || !swl::aligned16(k_cache) || !swl::aligned16(v_cache) ||
-        !swl::aligned16(cos_table) || !swl::aligned16(sin_table))
-        return SWL_ERR_BAD_ARG;
-    if (o && (!swl::aligned16(o) || (o_tok_stride & 7) || o_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim))
-        return SWL_ERR_BAD_ARG;
-    if (num_decoding_seqs > 65535 || num_kv_heads > 65535) return SWL_ERR_UNSUPPORTED;
-    float *mid_o = nullptr, *mid_lse = nullptr;
-    if (num_seq_blocks > 1) {
-        if (!scratch || !swl::aligned16(scratch)) return SWL_ERR_BAD_ARG;
-        mid_o = static_cast<float *>(scratch);
-        mid_lse = mid_o + static_cast<size_t>(num_decoding_seqs) * num_q_heads * num_seq_blocks * head_dim;
-    }
-    swl::PagedAttnParams p{};
-    p.o_direct = o;
-    p.k_cache = k_cache;
-    p.v_cache = v_cache;
-    p.block_table = block_table;
-    p.seq_ids = seq_ids;
-    p.seq_lens = seq_lens;
-    p.mid_o = mid_o;
-    p.mid_lse = mid_lse;
-    p.scale_log2e = softmax_scale * 1.44269504088896340736f;
-    p.H = num_q_heads;
-    p.KVH = num_kv_heads;
-    p.L = num_layers;
-    p.layer = cur_layer;
-    p.max_blocks_per_seq = max_blocks_per_seq;
-    p.seq_block_size = seq_block_size;
-    p.num_seq_blocks = num_seq_blocks;
-    p.o_tok_stride = o_tok_stride;
-    p.qkv_slabs = qkv_slabs;
-    p.ks = k_splits;
-    p.cos_t = cos_table;
-    p.sin_t = sin_table;
-    p.pos_idx = pos_idx;
-    p.row_ssq = row_ssq;
-    p.ssq_parts = ssq_parts;
-    p.hidden = hidden;
-    p.eps = eps;
-    const int G = num_q_heads / num_kv_heads;
-    int rc;
-    SWL_DISPATCH_DTYPE(dtype, T, {
-        rc = swl::dispatch_phase1<T, true>(p, num_decoding_seqs, head_dim, G, static_cast<hipStream_t>(stream));
-    });
-    if (rc != SWL_OK || num_seq_blocks == 1 || !merge) return rc;
-    return swl_paged_attn_phase2(o, mid_o, mid_lse, seq_lens, num_decoding_seqs, num_q_heads, head_dim,
-                                 seq_block_size, num_seq_blocks, o_tok_stride, dtype, stream);
+                                      hidden, eps, true);
 }
 
 /* swl_paged_attn_decode_qkv_rs stopped after phase 1 when the sequences are split (num_seq_blocks > 1): the partials stay

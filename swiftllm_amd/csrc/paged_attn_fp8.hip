@@ -20,11 +20,12 @@
 //   * the masked-garbage rule: 0x7f / 0xff are NaN and a slot past the sequence's length may hold them. A block that
 //     crosses the length has the codes of its rows >= len replaced by 0x00 (= +0) in registers before conversion, K and V
 //     alike; blocks wholly past it are never loaded. p = 0 then meets v = 0, never NaN.
-#include "attn_mfma.h"
+#include "decode_attn.h"
 #include "fp8_kv.h"
 
 // Ring depth (16-token blocks resident per wave, one of them being attended). 2: at D = 128 the 8-wave kernel builds to
-// 181 VGPRs; the same source at depth 3 / 4 needs 256 + 320 / 596 spilled registers under the 2-waves-per-SIMD budget
+// 158 VGPRs (181 with the ring written out in this file, which is the source the deeper rings were tried on); at depth
+// 3 / 4 it needed 256 + 320 / 596 spilled registers under the 2-waves-per-SIMD budget
 // (hipcc of ROCm 7.2, -Rpass-analysis=kernel-resource-usage), so deeper rings are an experiment build
 // (python -m swiftllm_amd.csrc.build --tag d3 -D SWL_PA8_DEPTH=3), not the product.
 #ifndef SWL_PA8_DEPTH
@@ -35,17 +36,8 @@ namespace swl {
 
 constexpr int kPa8Depth = SWL_PA8_DEPTH;
 
-struct PagedAttnFp8Params {
-    void *o_direct;
-    const void *q;
-    const uint8_t *k_cache;
-    const uint8_t *v_cache;
+struct PagedAttnFp8Params : DecodeAttnParams {
     const float *kv_scales;     // [2][L][KVH]
-    float *mid_o;
-    float *mid_lse;
-    float scale_log2e;
-    int H, KVH, L, layer, max_blocks_per_seq, seq_block_size, num_seq_blocks;
-    int64_t q_tok_stride, o_tok_stride;
 };
 
 // How a wave's 16-byte lanes cover the 16-token x D-byte tile of one (block, layer, kv-head); the stage's pitches are
@@ -160,7 +152,7 @@ __device__ __forceinline__ void attend_block_fp8(const vec8_t<T> (&qb)[MfmaTile<
     }
 }
 
-// NW = waves per workgroup (4 for short sequence blocks, 8 for long ones: launch_fp8_phase1). The block table, the
+// NW = waves per workgroup (4 for short sequence blocks, 8 for long ones: dispatch_decode_attn). The block table, the
 // lengths and the sequence ids are __restrict__ kernel arguments so their reads stay scalar loads (paged_attn.hip).
 template <typename T, int D, int G, int NW>
 __global__ __launch_bounds__(NW * 64) void paged_attn_fp8_phase1_kernel(PagedAttnFp8Params p,
@@ -194,6 +186,8 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_fp8_phase1_kernel(PagedAtt
     const float v_scale = p.kv_scales[(static_cast<int64_t>(p.L) + p.layer) * p.KVH + kvh];
     const float c = p.scale_log2e * k_scale;
 
+    const uint8_t *kc = static_cast<const uint8_t *>(p.k_cache);
+    const uint8_t *vc = static_cast<const uint8_t *>(p.v_cache);
     const int64_t tile_bytes = static_cast<int64_t>(kBlk) * D;
     const int64_t layer_head = static_cast<int64_t>(p.layer) * p.KVH + kvh;
     const int64_t blk_pitch = static_cast<int64_t>(p.L) * p.KVH;
@@ -222,12 +216,9 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_fp8_phase1_kernel(PagedAtt
         const int64_t base = (phys * blk_pitch + layer_head) * tile_bytes + lane_off;
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
-            Kd[i] = load16b_nt(p.k_cache + base + i * 1024);
-            Vd[i] = load16b_nt(p.v_cache + base + i * 1024);
+            Kd[i] = load16b_nt(kc + base + i * 1024);
+            Vd[i] = load16b_nt(vc + base + i * 1024);
         }
-    };
-    auto load_block = [&](int b, u32x4_t(&Kd)[NI], u32x4_t(&Vd)[NI]) {
-        load_phys(bt[b], Kd, Vd); // scalar load: b is wave-uniform
     };
     auto attend = [&](int b, u32x4_t(&Kd)[NI], u32x4_t(&Vd)[NI]) {
         const int tok0 = b * kBlk;
@@ -235,88 +226,23 @@ __global__ __launch_bounds__(NW * 64) void paged_attn_fp8_phase1_kernel(PagedAtt
                                tok0 + kBlk > len);
     };
 
-    int b = tok_begin / kBlk + wave;
-    // the first ND blocks of this wave go into slots 0..ND-1
-#pragma unroll
-    for (int d = 0; d < ND; ++d)
-        if (b + d * NW < blk_end) load_block(b + d * NW, Kr[d], Vr[d]);
-
-    // steady state: every refill is unconditional, so the waits between slots are exact counted vmcnt waits; slot d
-    // attends block b + d*NW and is refilled with block b + (d+ND)*NW (the loop of paged_attn.hip, its fences included)
-    if (b + (2 * ND - 1) * NW < blk_end) {
-        __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): the pipeline fill, hands the loop an exact state
-        do {
-#pragma unroll
-            for (int d = 0; d < ND; ++d) {
-                const int64_t phys_next = bt[b + (d + ND) * NW];
-                __builtin_amdgcn_sched_barrier(0);
-                attend(b + d * NW, Kr[d], Vr[d]);
-                __builtin_amdgcn_sched_barrier(0);
-                load_phys(phys_next, Kr[d], Vr[d]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            b += ND * NW;
-        } while (b + (2 * ND - 1) * NW < blk_end);
-    }
-    // drain: at most 2*ND-1 blocks left, the first ND of them already in their slots
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        if (b + d * NW < blk_end) {
-            attend(b + d * NW, Kr[d], Vr[d]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (b + (d + ND) * NW < blk_end) load_block(b + (d + ND) * NW, Kr[d], Vr[d]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < ND - 1; ++d)
-        if (b + (d + ND) * NW < blk_end) {
-            attend(b + (d + ND) * NW, Kr[d], Vr[d]);
-            __builtin_amdgcn_sched_barrier(0);   // one block's converted fragments live at a time
-        }
-
-    // O^T of the last block is stored by DS instructions below (swl_common.h)
-#pragma unroll
-    for (int mm = 0; mm < MT::OS; ++mm) mfma_results_tie(acc4[mm]);
-    mfma_results_ready<4>(acc4[MT::OS - 1]);
-    // the four lanes (q = 0..3) of a head share m and each hold the row sum of their own tokens; O^T is complete
-    const float lt = rows_allreduce_sum(l);
-    if (mh < G) {
-        if (mq == 0) {
-            sm_ml[wave][mh][0] = m;
-            sm_ml[wave][mh][1] = lt;
-        }
-#pragma unroll
-        for (int mm = 0; mm < MT::OS; ++mm)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) sm_acc[wave][mh][16 * mm + 4 * mq + r] = acc4[mm][r];
-    }
+    const int b = tok_begin / kBlk + wave;
+    kv_ring_prefetch<0, ND, NW>(b, blk_end, bt, Kr, Vr, load_phys);
+    kv_ring_stream<ND, NW>(b, blk_end, bt, Kr, Vr, load_phys, attend, attend);
+    mfma_wave_finish(m, l, acc4, sm_ml, sm_acc, wave, lane);
     __syncthreads();
     merge_waves_write<T, D, G, NW, true>(p, sm_ml, sm_acc, c, v_scale, kvh, seq, split);
 }
 
-template <typename T, int D, int G>
-static int launch_fp8_phase1(const PagedAttnFp8Params &p, const int *bt, const int *lens, const int *ids, int Bd,
+template <typename T>
+static int launch_fp8_phase1(const PagedAttnFp8Params &p, const int *bt, const int *lens, const int *ids, int Bd, int D,
                              hipStream_t stream) {
-    const dim3 grid(p.num_seq_blocks, p.KVH, Bd);
-    // >= 32 KV blocks per sequence block: 8-wave workgroups (>= 4 blocks per wave); else 4 waves (paged_attn.hip)
-    if (p.seq_block_size >= 32 * kBlk)
-        hipLaunchKernelGGL((paged_attn_fp8_phase1_kernel<T, D, G, 8>), grid, dim3(512), 0, stream, p, bt, lens, ids);
-    else
-        hipLaunchKernelGGL((paged_attn_fp8_phase1_kernel<T, D, G, 4>), grid, dim3(256), 0, stream, p, bt, lens, ids);
-    return check_launch();
-}
-
-template <typename T, int D>
-static int dispatch_fp8_g(const PagedAttnFp8Params &p, const int *bt, const int *lens, const int *ids, int Bd, int G,
-                          hipStream_t stream) {
-    switch (G) {
-    case 1: return launch_fp8_phase1<T, D, 1>(p, bt, lens, ids, Bd, stream);
-    case 2: return launch_fp8_phase1<T, D, 2>(p, bt, lens, ids, Bd, stream);
-    case 4: return launch_fp8_phase1<T, D, 4>(p, bt, lens, ids, Bd, stream);
-    case 8: return launch_fp8_phase1<T, D, 8>(p, bt, lens, ids, Bd, stream);
-    default: return SWL_ERR_UNSUPPORTED;
-    }
+    return dispatch_decode_attn(D, p.H / p.KVH, p.seq_block_size, [&](auto d, auto g, auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        hipLaunchKernelGGL((paged_attn_fp8_phase1_kernel<T, decltype(d)::value, decltype(g)::value, NW>),
+                           dim3(p.num_seq_blocks, p.KVH, Bd), dim3(NW * 64), 0, stream, p, bt, lens, ids);
+        return check_launch();
+    });
 }
 
 } // namespace swl
@@ -331,50 +257,23 @@ extern "C" int swl_paged_attn_phase1_fp8(void *o_direct, const void *q, const vo
     if (num_decoding_seqs < 0) return SWL_ERR_BAD_ARG;
     if (num_decoding_seqs == 0 || num_seq_blocks == 0) return SWL_OK;
     if (!q || !k_cache || !v_cache || !kv_scales || !block_table || !seq_ids || !seq_lens) return SWL_ERR_BAD_ARG;
-    if (num_seq_blocks < 0 || num_q_heads <= 0 || num_kv_heads <= 0 || num_q_heads % num_kv_heads != 0 ||
-        num_layers <= 0 || cur_layer < 0 || cur_layer >= num_layers || max_blocks_per_seq <= 0)
+    const swl::DecodeAttnArgs a{o_direct, q, k_cache, v_cache, q_tok_stride, o_tok_stride, num_q_heads, num_kv_heads,
+                                head_dim, num_layers, block_size, cur_layer, max_blocks_per_seq, seq_block_size,
+                                num_seq_blocks};
+    // this entry refuses a head_dim or dtype it has no kernel for up front, as a bad argument (the 16-bit entries leave
+    // them to the launch ladder: SWL_ERR_UNSUPPORTED for the head_dim, after every other check)
+    if (!(head_dim == 32 || head_dim == 64 || head_dim == 128) || !(dtype == SWL_F16 || dtype == SWL_BF16))
         return SWL_ERR_BAD_ARG;
-    if (!(head_dim == 32 || head_dim == 64 || head_dim == 128)) return SWL_ERR_BAD_ARG;
-    if (!(dtype == SWL_F16 || dtype == SWL_BF16)) return SWL_ERR_BAD_ARG;
-    if (block_size != swl::kBlk) return SWL_ERR_UNSUPPORTED;
-    if (seq_block_size <= 0 || seq_block_size % block_size != 0) return SWL_ERR_BAD_ARG;
-    if (num_seq_blocks == 1 ? !o_direct : (!mid_o || !mid_lse)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(q) || !swl::aligned16(k_cache) || !swl::aligned16(v_cache) || (q_tok_stride & 7) ||
-        q_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim)
-        return SWL_ERR_BAD_ARG;
-    // o is only looked at when it is given (it may be NULL when the sequences are split)
-    if (o_direct && (!swl::aligned16(o_direct) || (o_tok_stride & 7) ||
-                     o_tok_stride < static_cast<int64_t>(num_q_heads) * head_dim))
-        return SWL_ERR_BAD_ARG;
-    if (num_seq_blocks > 1 && ((reinterpret_cast<uintptr_t>(mid_o) | reinterpret_cast<uintptr_t>(mid_lse)) & 3u))
-        return SWL_ERR_BAD_ARG;
-    if (num_decoding_seqs > 65535 || num_kv_heads > 65535) return SWL_ERR_UNSUPPORTED;
+    if (const int rc = swl::check_decode_geometry(a)) return rc;
+    if (const int rc = swl::check_decode_layout(a)) return rc;
+    if (!swl::phase1_outputs_ok(o_direct, mid_o, mid_lse, num_seq_blocks)) return SWL_ERR_BAD_ARG;
+    if (!swl::decode_grid_fits(num_decoding_seqs, num_kv_heads)) return SWL_ERR_UNSUPPORTED;
     swl::PagedAttnFp8Params p{};
-    p.o_direct = o_direct;
-    p.q = q;
-    p.k_cache = static_cast<const uint8_t *>(k_cache);
-    p.v_cache = static_cast<const uint8_t *>(v_cache);
+    swl::fill_decode_params(p, a, mid_o, mid_lse, softmax_scale);
     p.kv_scales = kv_scales;
-    p.mid_o = mid_o;
-    p.mid_lse = mid_lse;
-    p.scale_log2e = softmax_scale * 1.44269504088896340736f;
-    p.H = num_q_heads;
-    p.KVH = num_kv_heads;
-    p.L = num_layers;
-    p.layer = cur_layer;
-    p.max_blocks_per_seq = max_blocks_per_seq;
-    p.seq_block_size = seq_block_size;
-    p.num_seq_blocks = num_seq_blocks;
-    p.q_tok_stride = q_tok_stride;
-    p.o_tok_stride = o_tok_stride;
-    const int G = num_q_heads / num_kv_heads;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     SWL_DISPATCH_DTYPE(dtype, T, {
-        switch (head_dim) {
-        case 32: return swl::dispatch_fp8_g<T, 32>(p, block_table, seq_lens, seq_ids, num_decoding_seqs, G, s);
-        case 64: return swl::dispatch_fp8_g<T, 64>(p, block_table, seq_lens, seq_ids, num_decoding_seqs, G, s);
-        default: return swl::dispatch_fp8_g<T, 128>(p, block_table, seq_lens, seq_ids, num_decoding_seqs, G, s);
-        }
+        return swl::launch_fp8_phase1<T>(p, block_table, seq_lens, seq_ids, num_decoding_seqs, head_dim,
+                                         static_cast<hipStream_t>(stream));
     });
 }
 
@@ -388,13 +287,10 @@ extern "C" int swl_paged_attn_decode_fp8(void *o, const void *q, const void *k_c
     if (num_decoding_seqs < 0) return SWL_ERR_BAD_ARG;
     if (num_decoding_seqs == 0 || num_seq_blocks == 0) return SWL_OK;
     if (!o) return SWL_ERR_BAD_ARG;
-    float *mid_o = nullptr, *mid_lse = nullptr;
-    if (num_seq_blocks > 1) {
-        if (!scratch || !swl::aligned16(scratch)) return SWL_ERR_BAD_ARG;
-        if (num_q_heads <= 0 || head_dim <= 0) return SWL_ERR_BAD_ARG;
-        mid_o = static_cast<float *>(scratch);
-        mid_lse = mid_o + static_cast<size_t>(num_decoding_seqs) * num_q_heads * num_seq_blocks * head_dim;
-    }
+    if (num_seq_blocks > 1 && (num_q_heads <= 0 || head_dim <= 0)) return SWL_ERR_BAD_ARG;
+    float *mid_o, *mid_lse;
+    if (!swl::split_scratch(scratch, num_decoding_seqs, num_q_heads, head_dim, num_seq_blocks, mid_o, mid_lse))
+        return SWL_ERR_BAD_ARG;
     const int rc = swl_paged_attn_phase1_fp8(o, q, k_cache, v_cache, kv_scales, block_table, seq_ids, seq_lens, mid_o,
                                              mid_lse, softmax_scale, num_decoding_seqs, num_q_heads, num_kv_heads,
                                              head_dim, num_layers, block_size, cur_layer, max_blocks_per_seq,

@@ -30,6 +30,12 @@ struct Vec2 {
 template <typename T>
 using vec2_t = typename Vec2<T>::type;
 
+// A compile-time int as a function argument (generic lambdas take their template parameters this way).
+template <int V>
+struct IntTag {
+    static constexpr int value = V;
+};
+
 typedef float float4_t __attribute__((ext_vector_type(4)));
 typedef float float16_t __attribute__((ext_vector_type(16)));
 

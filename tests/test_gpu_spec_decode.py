@@ -194,6 +194,36 @@ def test_verify_attention_is_deterministic(dtype):
         assert torch.equal(o.view(torch.int16), outs[0].view(torch.int16))
 
 
+# ---- 3b. one new token per sequence is the decode step ---------------------------------------------------------------
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("sbs,lengths", [(64, [1, 17, 100]), (512, [600])])
+@pytest.mark.parametrize("H,KVH,D", [(4, 2, 64), (32, 8, 128), (16, 2, 32)])
+def test_verify_of_one_token_is_the_decode_step_bit_for_bit(dtype, H, KVH, D, sbs, lengths):
+    """n = 1, ctx = len - 1: swl_paged_attn_verify and swl_paged_attn_decode run the same attend_block_mfma with the same
+    mask limit, the same ring, wave merge and phase 2 over the same finite pools, so their outputs are the same bits —
+    with one split (lengths 1 and 17) and with two (100 at 64, 600 at 512). G >= 2 only: decode's G = 1 is the VALU path."""
+    from swiftllm_amd.worker.kernels.paged_attn import paged_attention
+    assert H // KVH >= 2
+    g = gen(D + sbs)
+    mc, ec = NS(num_q_heads=H, num_kv_heads=KVH, head_dim=D, num_layers=NUM_LAYERS), NS(block_size=16)
+    for length in lengths:
+        ctxs = [length - 1, length - 1]
+        seqs = [_make_seq(c, 1, H, KVH, D, sbs, dtype, g, i) for i, c in enumerate(ctxs)]
+        kc, vc, bt, seq_ids = _fill_pools(seqs, ctxs, KVH, D, dtype, 0.0, -(-length // 16) + 3)
+        kc, vc, bt = kc.cuda(), vc.cuda(), bt.cuda()
+        q = torch.cat([s[0] for s in seqs]).cuda()
+        o_verify, o_decode = torch.full_like(q, float("nan")), torch.full_like(q, float("nan"))
+        st = _state(ctxs, [1, 1], D, sbs, seq_ids)
+        _verify()(q, kc, vc, bt, o_verify, mc, ec, st, LAYER)
+        dec = NS(num_decoding_seqs=2, num_prefill_seqs=0, seq_block_size=sbs, num_seq_blocks=st.num_seq_blocks,
+                 softmax_scale=st.softmax_scale, seq_ids=st.seq_ids, paged_attn_scratch=None,
+                 decoding_seq_lens=torch.tensor([length, length], dtype=torch.int32).cuda())
+        paged_attention(q, kc, vc, bt, mc, ec, dec, LAYER, o_decode)
+        torch.cuda.synchronize()
+        assert torch.isfinite(o_decode.float()).all(), length
+        assert torch.equal(o_verify.view(torch.int16), o_decode.view(torch.int16)), length
+
+
 # ---- 4. the model: logits against the oracle -------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", ["TINY", "SMALL128"])
 @pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
