@@ -611,7 +611,9 @@ int swl_gemm_skinny_packed_silu_gate_nf(void *out, const void *x, const void *no
  *   swl_gemm_skinny_packed_silu_gate_nx / swl_gemm_skinny_packed_partial_nx: the consuming projections add the ssq_parts
  *     (= hidden / 16, % 64 == 0) partials of every row in a fixed order before their first tile and stage
  *     round(r * rstd * norm_w); outputs as swl_gemm_skinny_packed_silu_gate / swl_gemm_skinny_packed_partial (nothing
- *     pending: the slabs go to swl_paged_attn_decode_qkv as they are). */
+ *     pending: the slabs go to swl_paged_attn_decode_qkv as they are). k_splits of swl_gemm_skinny_packed_partial_nx: as
+ *     for every slab entry, a power of two from 1 to 16 (anything else is SWL_ERR_BAD_ARG) with K % (128 * k_splits) == 0
+ *     (else SWL_ERR_UNSUPPORTED). */
 int swl_gemm_rows_add_ssq(void *residual, float *ssq_out, const void *x, const void *w_packed, int32_t M, int32_t N, int32_t K,
                           int64_t x_row_stride, int32_t dtype, swl_stream_t stream);
 int swl_gemm_skinny_packed_silu_gate_nx(void *out, const void *x, const void *norm_w, float eps, const float *ssq_in,

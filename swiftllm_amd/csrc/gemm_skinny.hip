@@ -36,7 +36,8 @@
 //   * N/32 tiles alone do not fill 256 CUs for N = 4096..6144, so K is split across workgroups
 //     (grid.y): each split writes an fp32 partial slab, a second tiny kernel adds the slabs in a fixed
 //     order and rounds once. Deterministic, no atomics.
-#include "swl_common.h"
+// The entry points' argument checks and the split-K driver are shared with gemm_wide.hip: gemm_host.h.
+#include "gemm_host.h"
 
 namespace swl {
 
@@ -550,38 +551,49 @@ static int choose_k_splits_packed(int N, int K, bool *uneven) {
 // K-chunks of >= 8 tiles amortise the ring's barriers; shorter ones keep the barrier-free kernel.
 static bool use_ring(int kc) { return kc / kKT >= 8; }
 
-// reduce == false: stop after the partial slabs (a fused consumer sums them: swl_splitk_*)
 template <typename T>
-static int run_gemm(T *out, const T *x, const T *w, float *ws, size_t ws_bytes, int M, int N, int K,
-                    int64_t xs, int64_t os, int ks, hipStream_t stream, bool reduce = true) {
-    if (ks <= 0) ks = choose_k_splits(N, K);
-    if (K % (kKT * ks) != 0) return SWL_ERR_UNSUPPORTED;
-    const int tiles = N / 32;
-    const dim3 grid((tiles + kGemmWaves - 1) / kGemmWaves, ks);
-    const int kc = K / ks;
-    const bool ring = use_ring(kc);
-    if (ks == 1 && reduce) {
-        if (ring)
-            hipLaunchKernelGGL((gemm_skinny_ring_kernel<T, kGemmDirect>), grid, dim3(kGemmWaves * 64), 0, stream,
-                               out, x, w, M, N, K, kc, xs, os, GemmExtra{});
-        else
-            hipLaunchKernelGGL((gemm_skinny_kernel<T, kGemmDirect>), grid, dim3(kGemmWaves * 64), 0, stream, out,
-                               x, w, M, N, K, kc, xs, os);
-        return check_launch();
-    }
-    if (!ws || ws_bytes < static_cast<size_t>(ks) * M * N * sizeof(float)) return SWL_ERR_BAD_ARG;
-    if (ring)
-        hipLaunchKernelGGL((gemm_skinny_ring_kernel<T, kGemmPartial>), grid, dim3(kGemmWaves * 64), 0, stream, ws,
-                           x, w, M, N, K, kc, xs, static_cast<int64_t>(N), GemmExtra{});
-    else
-        hipLaunchKernelGGL((gemm_skinny_kernel<T, kGemmPartial>), grid, dim3(kGemmWaves * 64), 0, stream, ws, x, w,
-                           M, N, K, kc, xs, static_cast<int64_t>(N));
-    if (!reduce) return check_launch();
+void launch_splitk_reduce(T *out, const float *slabs, int ks, int M, int N, int64_t out_row_stride, hipStream_t stream) {
     const int64_t items = static_cast<int64_t>(M) * (N / 4);
-    const unsigned rgrid = static_cast<unsigned>((items + 255) / 256);
-    hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(rgrid), dim3(256), 0, stream, out, ws, M, N, ks,
-                       os);
-    return check_launch();
+    hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(static_cast<unsigned>((items + 255) / 256)), dim3(256), 0, stream,
+                       out, slabs, M, N, ks, out_row_stride);
+}
+template void launch_splitk_reduce<f16>(f16 *, const float *, int, int, int, int64_t, hipStream_t); // (for gemm_wide.hip)
+template void launch_splitk_reduce<bf16>(bf16 *, const float *, int, int, int, int64_t, hipStream_t);
+
+// Workgroups of kGemmWaves waves over the N / 32 column tiles: a tile per wave — SiLU-gate: two `up` tiles and their `gate` tiles.
+template <int MODE>
+static int four_wave_groups(int N) {
+    return MODE == kGemmSiluGate ? (N / 32 + 1) / 2 : (N / 32 + kGemmWaves - 1) / kGemmWaves;
+}
+
+// What a SiLU-gate entry is handed: N = I, K is never split.
+static GemmArgs silu_gate_args(void *out, const void *x, const void *w, int M, int I, int K, int64_t x_row_stride,
+                               int64_t out_row_stride, int max_m = 32) {
+    return GemmArgs{out, x, w, nullptr, 0, M, I, K, x_row_stride, out_row_stride, 1, max_m, kKT};
+}
+
+// Row-major W, any mode (SiLU-gate: N = I, one K-chunk): the ring kernel where use_ring(kc), else the barrier-free one.
+template <typename T, int MODE>
+static void launch_rowmajor(const GemmArgs &a, hipStream_t stream, void *dst, int64_t dst_stride, int kc, int ks) {
+    const dim3 grid(four_wave_groups<MODE>(a.N), ks);
+    const T *x = static_cast<const T *>(a.x), *w = static_cast<const T *>(a.w);
+    if (use_ring(kc))
+        hipLaunchKernelGGL((gemm_skinny_ring_kernel<T, MODE>), grid, dim3(kGemmWaves * 64), 0, stream, dst, x, w, a.M, a.N,
+                           a.K, kc, a.x_row_stride, dst_stride, GemmExtra{});
+    else
+        hipLaunchKernelGGL((gemm_skinny_kernel<T, MODE>), grid, dim3(kGemmWaves * 64), 0, stream, dst, x, w, a.M, a.N, a.K,
+                           kc, a.x_row_stride, dst_stride);
+}
+
+template <typename T>
+static int run_gemm(const GemmArgs &a, hipStream_t stream) {
+    const int ks = a.k_splits > 0 ? a.k_splits : choose_k_splits(a.N, a.K);
+    if (a.K % (kKT * ks) != 0) return SWL_ERR_UNSUPPORTED;
+    const int kc = a.K / ks;
+    return run_splitk<T>(
+        a, ks, stream,
+        [&](void *out) { launch_rowmajor<T, kGemmDirect>(a, stream, out, a.out_row_stride, kc, ks); },
+        [&](float *slabs) { launch_rowmajor<T, kGemmPartial>(a, stream, slabs, a.N, kc, ks); });
 }
 
 } // namespace swl
@@ -597,22 +609,10 @@ extern "C" int swl_gemm_skinny(void *out, const void *x, const void *w, void *wo
                                size_t workspace_bytes, int32_t M, int32_t N, int32_t K,
                                int64_t x_row_stride, int64_t out_row_stride, int32_t k_splits,
                                int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || N <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
-    if (M == 0) return SWL_OK;
-    if (!out || !x || !w) return SWL_ERR_BAD_ARG;
-    if (M > 32 || (N & 31) || (K & (swl::kKT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < N || (x_row_stride & 7) || (out_row_stride & 3))
-        return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(x) || !swl::aligned16(w) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
-        (workspace && !swl::aligned16(workspace)))
-        return SWL_ERR_BAD_ARG;
-    if (k_splits < 0 || k_splits > 16 || (k_splits & (k_splits - 1))) return SWL_ERR_BAD_ARG;
-    SWL_DISPATCH_DTYPE(dtype, T, {
-        return swl::run_gemm<T>(static_cast<T *>(out), static_cast<const T *>(x),
-                                static_cast<const T *>(w), static_cast<float *>(workspace),
-                                workspace_bytes, M, N, K, x_row_stride, out_row_stride, k_splits,
-                                static_cast<hipStream_t>(stream));
-    });
+    const swl::GemmArgs a{out, x, w, workspace, workspace_bytes, M, N, K, x_row_stride, out_row_stride, k_splits, 32, swl::kKT};
+    int rc;
+    if (swl::gemm_args_settled(a, rc)) return rc;
+    SWL_DISPATCH_DTYPE(dtype, T, { return swl::run_gemm<T>(a, static_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int swl_gemm_skinny_choose_splits(int32_t N, int32_t K) {
@@ -632,19 +632,10 @@ extern "C" int swl_gemm_skinny_packed_choose_splits(int32_t N, int32_t K) {
 extern "C" int swl_gemm_skinny_partial(float *slabs, size_t slabs_bytes, const void *x, const void *w,
                                        int32_t M, int32_t N, int32_t K, int64_t x_row_stride,
                                        int32_t k_splits, int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || N <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
-    if (M == 0) return SWL_OK;
-    if (!slabs || !x || !w || k_splits < 1 || k_splits > 16 || (k_splits & (k_splits - 1)))
-        return SWL_ERR_BAD_ARG;
-    if (M > 32 || (N & 31) || (K & (swl::kKT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || (x_row_stride & 7) || !swl::aligned16(x) || !swl::aligned16(w) ||
-        !swl::aligned16(slabs))
-        return SWL_ERR_BAD_ARG;
-    SWL_DISPATCH_DTYPE(dtype, T, {
-        return swl::run_gemm<T>(static_cast<T *>(nullptr), static_cast<const T *>(x),
-                                static_cast<const T *>(w), slabs, slabs_bytes, M, N, K, x_row_stride, N,
-                                k_splits, static_cast<hipStream_t>(stream), false);
-    });
+    const swl::GemmArgs a{slabs, x, w, slabs, slabs_bytes, M, N, K, x_row_stride, N, k_splits, 32, swl::kKT, true};
+    int rc;
+    if (swl::gemm_args_settled(a, rc)) return rc;
+    SWL_DISPATCH_DTYPE(dtype, T, { return swl::run_gemm<T>(a, static_cast<hipStream_t>(stream)); });
 }
 
 /* out[M, N] = round(sum_k slabs[k]) in slab order (what swl_gemm_skinny does internally). */
@@ -654,12 +645,9 @@ extern "C" int swl_splitk_reduce(void *out, const float *slabs, int32_t k_splits
     if (M == 0) return SWL_OK;
     if (!out || !slabs || out_row_stride < N || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
     if (!swl::aligned16(slabs) || (reinterpret_cast<uintptr_t>(out) & 7u)) return SWL_ERR_BAD_ARG;   // float4 loads, 8-byte stores
-    const int64_t items = static_cast<int64_t>(M) * (N / 4);
-    const unsigned grid = static_cast<unsigned>((items + 255) / 256);
     SWL_DISPATCH_DTYPE(dtype, T, {
-        hipLaunchKernelGGL((swl::splitk_reduce_kernel<T>), dim3(grid), dim3(256), 0,
-                           static_cast<hipStream_t>(stream), static_cast<T *>(out), slabs, M, N,
-                           k_splits, out_row_stride);
+        swl::launch_splitk_reduce<T>(static_cast<T *>(out), slabs, k_splits, M, N, out_row_stride,
+                                     static_cast<hipStream_t>(stream));
     });
     return swl::check_launch();
 }
@@ -671,26 +659,11 @@ extern "C" int swl_splitk_reduce(void *out, const float *slabs, int32_t k_splits
 extern "C" int swl_gemm_skinny_silu_gate(void *out, const void *x, const void *w_up_gate, int32_t M,
                                          int32_t I, int32_t K, int64_t x_row_stride,
                                          int64_t out_row_stride, int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || I <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
-    if (M == 0) return SWL_OK;
-    if (!out || !x || !w_up_gate) return SWL_ERR_BAD_ARG;
-    if (M > 32 || (I & 31) || (K & (swl::kKT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < I || (x_row_stride & 7) || (out_row_stride & 3))
-        return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(x) || !swl::aligned16(w_up_gate) || (reinterpret_cast<uintptr_t>(out) & 7u))
-        return SWL_ERR_BAD_ARG;
-    const dim3 grid((I / 32 + 1) / 2, 1);
+    const swl::GemmArgs a = swl::silu_gate_args(out, x, w_up_gate, M, I, K, x_row_stride, out_row_stride);
+    int rc;
+    if (swl::gemm_args_settled(a, rc)) return rc;
     SWL_DISPATCH_DTYPE(dtype, T, {
-        if (swl::use_ring(K))
-            hipLaunchKernelGGL((swl::gemm_skinny_ring_kernel<T, swl::kGemmSiluGate>), grid,
-                               dim3(swl::kGemmWaves * 64), 0, static_cast<hipStream_t>(stream), out,
-                               static_cast<const T *>(x), static_cast<const T *>(w_up_gate), M, I, K, K,
-                               x_row_stride, out_row_stride, swl::GemmExtra{});
-        else
-            hipLaunchKernelGGL((swl::gemm_skinny_kernel<T, swl::kGemmSiluGate>), grid,
-                               dim3(swl::kGemmWaves * 64), 0, static_cast<hipStream_t>(stream), out,
-                               static_cast<const T *>(x), static_cast<const T *>(w_up_gate), M, I, K, K,
-                               x_row_stride, out_row_stride);
+        swl::launch_rowmajor<T, swl::kGemmSiluGate>(a, static_cast<hipStream_t>(stream), out, out_row_stride, K, 1);
     });
     return swl::check_launch();
 }
@@ -720,52 +693,66 @@ static bool prefer_three_waves(int N, int ks) {
     return wg4 < 256 && wg3 <= 256;
 }
 
-template <typename T>
-static void launch_packed_partial3(hipStream_t stream, void *out, const T *x, const T *wp, int M, int N, int K, int kc,
-                                   int ks, int64_t xs) {
-    const dim3 grid(N / 32 / 3, ks);
-    if (use_ring(kc))
-        hipLaunchKernelGGL((gemm_skinny_ring_kernel<T, kGemmPartial, true, 3, 3>), grid, dim3(3 * 64), 0,
-                           stream, out, x, wp, M, N, K, kc, xs, static_cast<int64_t>(N), GemmExtra{});
-    else
-        hipLaunchKernelGGL((gemm_skinny_ring_kernel<T, kGemmPartial, true, 2, 3>), grid, dim3(3 * 64), 0,
-                           stream, out, x, wp, M, N, K, kc, xs, static_cast<int64_t>(N), GemmExtra{});
+// SWL_SILU_WAVES=2 / 4 forces one workgroup form of the NF SiLU-gate for every M (A/B runs); unset: two waves up to 8 tokens.
+static bool silu_gate_two_waves(int M) {
+    static const int forced = [] { const char *e = getenv("SWL_SILU_WAVES"); return !e ? 0 : e[0] == '2' ? 2 : e[0] == '4' ? 4 : 0; }();
+    return forced ? forced == 2 : M <= 8;
 }
 
-template <typename T, int MODE>
-static void launch_packed(dim3 grid, hipStream_t stream, void *out, const T *x, const T *wp, int M, int N, int K, int kc,
-                          int64_t xs, int64_t os, const GemmExtra &fuse = GemmExtra{}) {
-    if (use_ring(kc))
-        hipLaunchKernelGGL((gemm_skinny_ring_kernel<T, MODE, true, 3>), grid, dim3(kGemmWaves * 64), 0,
-                           stream, out, x, wp, M, N, K, kc, xs, os, fuse);
-    else
-        hipLaunchKernelGGL((gemm_skinny_ring_kernel<T, MODE, true, 2>), grid, dim3(kGemmWaves * 64), 0,
-                           stream, out, x, wp, M, N, K, kc, xs, os, fuse);
-}
-
-template <typename T>
-static int run_gemm_packed(T *out, const T *x, const T *wp, float *ws, size_t ws_bytes, int M, int N, int K, int64_t xs,
-                           int64_t os, int ks, hipStream_t stream, bool reduce) {
-    bool uneven = false;
-    if (ks <= 0) ks = choose_k_splits_packed(N, K, &uneven);
-    else uneven = K % (kKT * ks) != 0;
-    if (uneven && (K / kKT) / ks < 8) return SWL_ERR_UNSUPPORTED; // (uneven splits run the ring kernel only)
-    const dim3 grid((N / 32 + kGemmWaves - 1) / kGemmWaves, ks);
-    const int kc = uneven ? (K / kKT / ks) * kKT : K / ks;  // (uneven: the shorter chunk — selects the ring depth)
-    if (ks == 1 && reduce) {
-        launch_packed<T, kGemmDirect>(grid, stream, out, x, wp, M, N, K, kc, xs, os);
-        return check_launch();
+// The launch ladder of the packed ring kernel: ring depth RD, NWV waves per workgroup and the grid for one mode of
+// gemm_skinny_ring_kernel<T, MODE, true, RD, NWV, NF, NX>. dst: out[M, N] or the slabs, kc: the K-chunk of a split (the
+// shorter one when they are uneven: fuse.k_tiles_total), ks: the splits.
+//   RD    3 where use_ring(kc), else 2 — except three-wave NF, below;
+//   NWV   4: a workgroup owns 4 tiles (SiLU-gate: 2 `up` + 2 `gate`);
+//         3: partial slabs over even splits where prefer_three_waves(N, ks);
+//         2: NF SiLU-gate up to 8 tokens on the deep ring (NX: its entry takes nothing but the deep ring).
+template <typename T, int MODE, bool NF = false, bool NX = false>
+static void launch_packed_ring(const GemmArgs &a, hipStream_t stream, void *dst, int64_t dst_stride, int kc, int ks,
+                               const GemmExtra &fuse = GemmExtra{}) {
+    const int tiles = a.N / 32;
+    auto launch = [&](auto rd, auto nwv, int groups) {
+        constexpr int RD = decltype(rd)::value, NWV = decltype(nwv)::value;
+        hipLaunchKernelGGL((gemm_skinny_ring_kernel<T, MODE, true, RD, NWV, NF, NX>), dim3(groups, ks), dim3(NWV * 64), 0,
+                           stream, dst, static_cast<const T *>(a.x), static_cast<const T *>(a.w), a.M, a.N, a.K, kc,
+                           a.x_row_stride, dst_stride, fuse);
+    };
+    const bool deep = use_ring(kc);
+    if constexpr (MODE == kGemmPartial) {
+        if (fuse.k_tiles_total == 0 && prefer_three_waves(a.N, ks)) {
+            // (NF: three-wave workgroups stage 3 row groups per wave: with the norm weights and the fp32 staging temporaries
+            // a 3-deep weight ring no longer fits 256 registers — 11-30 spilled; they run the 2-deep ring. A/B on MI355X:
+            // the spilling deep ring and 4-wave workgroups with the deep ring — 192 instead of 256 of them for Llama-3-8B
+            // — are within noise of it in the layer chain: profiles/r05c_rows_layer_micro_nf_rd3 / _nf_4w.jsonl.)
+            if (NF || !deep) return launch(IntTag<2>{}, IntTag<3>{}, tiles / 3);
+            if constexpr (!NF) return launch(IntTag<3>{}, IntTag<3>{}, tiles / 3);
+        }
     }
-    if (!ws || ws_bytes < static_cast<size_t>(ks) * M * N * sizeof(float)) return SWL_ERR_BAD_ARG;
+    if constexpr (MODE == kGemmSiluGate && NF) {
+        // r06b: up to 8 tokens, workgroups of ONE up tile + ONE gate tile (448 workgroups for Llama-3-8B instead of 224:
+        // every CU streams; one wave per SIMD, two workgroups per CU) — same K order per tile, hence the same bits. Each
+        // wave then stages twice the x rows, which costs more than the idle CUs from 9 tokens on
+        // (tools/gpu_silu_waves_ab.sh, four interleaved rounds, profiles/r06b_silu_gate_two_wave_groups_ab.jsonl: 39.2 vs
+        // 39.8 us at 1 token, 39.2 vs 40.0 at 8, 41.2 vs 40.3 at 32).
+        if (deep && (NX ? a.M <= 8 : silu_gate_two_waves(a.M))) return launch(IntTag<3>{}, IntTag<2>{}, tiles);
+    }
+    const int groups = four_wave_groups<MODE>(a.N);
+    if (deep) return launch(IntTag<3>{}, IntTag<kGemmWaves>{}, groups);
+    if constexpr (!(MODE == kGemmSiluGate && NX)) launch(IntTag<2>{}, IntTag<kGemmWaves>{}, groups);
+}
+
+template <typename T>
+static int run_gemm_packed(const GemmArgs &a, hipStream_t stream) {
+    bool uneven = false;
+    int ks = a.k_splits;
+    if (ks <= 0) ks = choose_k_splits_packed(a.N, a.K, &uneven);
+    else uneven = a.K % (kKT * ks) != 0;
+    if (uneven && (a.K / kKT) / ks < 8) return SWL_ERR_UNSUPPORTED; // (uneven splits run the ring kernel only)
+    const int kc = uneven ? (a.K / kKT / ks) * kKT : a.K / ks;  // (uneven: the shorter chunk — selects the ring depth)
     GemmExtra fuse{};
-    fuse.k_tiles_total = uneven ? K / kKT : 0;
-    if (!uneven && prefer_three_waves(N, ks)) launch_packed_partial3<T>(stream, ws, x, wp, M, N, K, kc, ks, xs);
-    else launch_packed<T, kGemmPartial>(grid, stream, ws, x, wp, M, N, K, kc, xs, static_cast<int64_t>(N), fuse);
-    if (!reduce) return check_launch();
-    const int64_t items = static_cast<int64_t>(M) * (N / 4);
-    hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(static_cast<unsigned>((items + 255) / 256)), dim3(256), 0,
-                       stream, out, ws, M, N, ks, os);
-    return check_launch();
+    fuse.k_tiles_total = uneven ? a.K / kKT : 0;
+    return run_splitk<T>(
+        a, ks, stream, [&](void *out) { launch_packed_ring<T, kGemmDirect>(a, stream, out, a.out_row_stride, kc, ks); },
+        [&](float *slabs) { launch_packed_ring<T, kGemmPartial>(a, stream, slabs, a.N, kc, ks, fuse); });
 }
 
 } // namespace swl
@@ -791,56 +778,30 @@ extern "C" int swl_gemm_pack_weight(void *dst, const void *src, int32_t N, int32
 extern "C" int swl_gemm_skinny_packed(void *out, const void *x, const void *w_packed, void *workspace,
                                       size_t workspace_bytes, int32_t M, int32_t N, int32_t K, int64_t x_row_stride,
                                       int64_t out_row_stride, int32_t k_splits, int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || N <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
-    if (M == 0) return SWL_OK;
-    if (!out || !x || !w_packed) return SWL_ERR_BAD_ARG;
-    if (M > 32 || (N & 31) || (K & (swl::kKT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < N || (x_row_stride & 7) || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(x) || !swl::aligned16(w_packed) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
-        (workspace && !swl::aligned16(workspace)))
-        return SWL_ERR_BAD_ARG;
-    if (k_splits < 0 || k_splits > 16 || (k_splits & (k_splits - 1))) return SWL_ERR_BAD_ARG;
-    SWL_DISPATCH_DTYPE(dtype, T, {
-        return swl::run_gemm_packed<T>(static_cast<T *>(out), static_cast<const T *>(x),
-                                       static_cast<const T *>(w_packed), static_cast<float *>(workspace),
-                                       workspace_bytes, M, N, K, x_row_stride, out_row_stride, k_splits,
-                                       static_cast<hipStream_t>(stream), true);
-    });
+    const swl::GemmArgs a{out, x, w_packed, workspace, workspace_bytes, M, N, K, x_row_stride, out_row_stride, k_splits, 32,
+                          swl::kKT};
+    int rc;
+    if (swl::gemm_args_settled(a, rc)) return rc;
+    SWL_DISPATCH_DTYPE(dtype, T, { return swl::run_gemm_packed<T>(a, static_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int swl_gemm_skinny_packed_partial(float *slabs, size_t slabs_bytes, const void *x, const void *w_packed,
                                               int32_t M, int32_t N, int32_t K, int64_t x_row_stride,
                                               int32_t k_splits, int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || N <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
-    if (M == 0) return SWL_OK;
-    if (!slabs || !x || !w_packed || k_splits < 1 || k_splits > 16 || (k_splits & (k_splits - 1)))
-        return SWL_ERR_BAD_ARG;
-    if (M > 32 || (N & 31) || (K & (swl::kKT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || (x_row_stride & 7) || !swl::aligned16(x) || !swl::aligned16(w_packed) ||
-        !swl::aligned16(slabs))
-        return SWL_ERR_BAD_ARG;
-    SWL_DISPATCH_DTYPE(dtype, T, {
-        return swl::run_gemm_packed<T>(static_cast<T *>(nullptr), static_cast<const T *>(x),
-                                       static_cast<const T *>(w_packed), slabs, slabs_bytes, M, N, K, x_row_stride, N,
-                                       k_splits, static_cast<hipStream_t>(stream), false);
-    });
+    const swl::GemmArgs a{slabs, x, w_packed, slabs, slabs_bytes, M, N, K, x_row_stride, N, k_splits, 32, swl::kKT, true};
+    int rc;
+    if (swl::gemm_args_settled(a, rc)) return rc;
+    SWL_DISPATCH_DTYPE(dtype, T, { return swl::run_gemm_packed<T>(a, static_cast<hipStream_t>(stream)); });
 }
 
 extern "C" int swl_gemm_skinny_packed_silu_gate(void *out, const void *x, const void *w_up_gate_packed, int32_t M,
                                                 int32_t I, int32_t K, int64_t x_row_stride, int64_t out_row_stride,
                                                 int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || I <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
-    if (M == 0) return SWL_OK;
-    if (!out || !x || !w_up_gate_packed) return SWL_ERR_BAD_ARG;
-    if (M > 32 || (I & 31) || (K & (swl::kKT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < I || (x_row_stride & 7) || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(x) || !swl::aligned16(w_up_gate_packed) || (reinterpret_cast<uintptr_t>(out) & 7u))
-        return SWL_ERR_BAD_ARG;
-    const dim3 grid((I / 32 + 1) / 2, 1);
+    const swl::GemmArgs a = swl::silu_gate_args(out, x, w_up_gate_packed, M, I, K, x_row_stride, out_row_stride);
+    int rc;
+    if (swl::gemm_args_settled(a, rc)) return rc;
     SWL_DISPATCH_DTYPE(dtype, T, {
-        swl::launch_packed<T, swl::kGemmSiluGate>(grid, static_cast<hipStream_t>(stream), out, static_cast<const T *>(x),
-                                                  static_cast<const T *>(w_up_gate_packed), M, I, K, K, x_row_stride,
-                                                  out_row_stride);
+        swl::launch_packed_ring<T, swl::kGemmSiluGate>(a, static_cast<hipStream_t>(stream), out, out_row_stride, K, 1);
     });
     return swl::check_launch();
 }
@@ -854,22 +815,21 @@ extern "C" int swl_gemm_skinny_packed_silu_gate_rs(void *out, const void *x, con
                                                    const float *row_ssq, int32_t ssq_parts, float eps, int32_t M,
                                                    int32_t I, int32_t K, int64_t x_row_stride, int64_t out_row_stride,
                                                    int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || I <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
+    const swl::GemmArgs a = swl::silu_gate_args(out, x, w_up_gate_packed, M, I, K, x_row_stride, out_row_stride);
+    SWL_GEMM_CHECK(swl::check_gemm_counts(a));
     if (M == 0) return SWL_OK;
-    if (!out || !x || !w_up_gate_packed || !row_ssq || ssq_parts <= 0) return SWL_ERR_BAD_ARG;
-    if (M > 32 || (I & 31) || (K & (swl::kKT - 1)) || ssq_parts > 8) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < I || (x_row_stride & 7) || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(x) || !swl::aligned16(w_up_gate_packed) || (reinterpret_cast<uintptr_t>(out) & 7u))
-        return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_operands(a));
+    if (!row_ssq || ssq_parts <= 0) return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_shape(a));
+    if (ssq_parts > 8) return SWL_ERR_UNSUPPORTED;
+    SWL_GEMM_CHECK(swl::check_gemm_strides(a));
+    SWL_GEMM_CHECK(swl::check_gemm_alignment(a));
     swl::GemmExtra f{};
     f.ssq_in = row_ssq;
     f.ssq_parts = ssq_parts;
     f.eps = eps;
-    const dim3 grid((I / 32 + 1) / 2, 1);
     SWL_DISPATCH_DTYPE(dtype, T, {
-        swl::launch_packed<T, swl::kGemmSiluGate>(grid, static_cast<hipStream_t>(stream), out, static_cast<const T *>(x),
-                                                  static_cast<const T *>(w_up_gate_packed), M, I, K, K, x_row_stride,
-                                                  out_row_stride, f);
+        swl::launch_packed_ring<T, swl::kGemmSiluGate>(a, static_cast<hipStream_t>(stream), out, out_row_stride, K, 1, f);
     });
     return swl::check_launch();
 }
@@ -885,40 +845,25 @@ extern "C" int swl_gemm_skinny_packed_partial_nf(float *slabs, size_t slabs_byte
                                                  const void *norm_w, const void *w_packed, int32_t M, int32_t N, int32_t K,
                                                  int64_t x_row_stride, int32_t k_splits, int32_t dtype,
                                                  swl_stream_t stream) {
-    if (M < 0 || N <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
+    const swl::GemmArgs a{slabs, x, w_packed, slabs, slabs_bytes, M, N, K, x_row_stride, N, k_splits, 32, swl::kKT, true};
+    SWL_GEMM_CHECK(swl::check_gemm_counts(a));
     if (M == 0) return SWL_OK;
-    if (!slabs || !ssq_out || !x || !norm_w || !w_packed || k_splits < 1 || k_splits > 16 || (k_splits & (k_splits - 1)))
-        return SWL_ERR_BAD_ARG;
-    if (M > 32 || (N & 31) || K % (swl::kKT * k_splits)) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || (x_row_stride & 7) || !swl::aligned16(x) || !swl::aligned16(w_packed) ||
-        !swl::aligned16(norm_w) || !swl::aligned16(slabs))
-        return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_operands(a));
+    if (!ssq_out || !norm_w) return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_k_splits(a));
+    SWL_GEMM_CHECK(swl::check_gemm_shape(a));
+    if (K % (swl::kKT * k_splits)) return SWL_ERR_UNSUPPORTED;
+    SWL_GEMM_CHECK(swl::check_gemm_strides(a));
+    SWL_GEMM_CHECK(swl::check_gemm_alignment(a));
+    if (!swl::aligned16(norm_w)) return SWL_ERR_BAD_ARG;
     if (slabs_bytes < static_cast<size_t>(k_splits) * M * N * sizeof(float)) return SWL_ERR_BAD_ARG;
     swl::GemmExtra f{};
     f.norm_w = norm_w;
     f.ssq_out = ssq_out;
-    const int kc = K / k_splits;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t n64 = N;
-#define SWL_NF_PARTIAL(RD_, NWV_)                                                                                        \
-    hipLaunchKernelGGL((swl::gemm_skinny_ring_kernel<T, swl::kGemmPartial, true, RD_, NWV_, true>), grid,          \
-                       dim3(NWV_ * 64), 0, s, static_cast<void *>(slabs), static_cast<const T *>(x),                     \
-                       static_cast<const T *>(w_packed), M, N, K, kc, x_row_stride, n64, f)
     SWL_DISPATCH_DTYPE(dtype, T, {
-        // (three-wave workgroups stage 3 row groups per wave: with the norm weights and the fp32 staging temporaries a
-        // 3-deep weight ring no longer fits 256 registers — 11-30 spilled; they run the 2-deep ring. A/B on MI355X: the
-        // spilling deep ring and 4-wave workgroups with the deep ring — 192 instead of 256 of them for Llama-3-8B — are
-        // within noise of it in the layer chain: profiles/r05c_rows_layer_micro_nf_rd3 / _nf_4w.jsonl.)
-        if (swl::prefer_three_waves(N, k_splits)) {
-            const dim3 grid(N / 32 / 3, k_splits);
-            SWL_NF_PARTIAL(2, 3);
-        } else {
-            const dim3 grid((N / 32 + swl::kGemmWaves - 1) / swl::kGemmWaves, k_splits);
-            if (swl::use_ring(kc)) SWL_NF_PARTIAL(3, 4);
-            else SWL_NF_PARTIAL(2, 4);
-        }
+        swl::launch_packed_ring<T, swl::kGemmPartial, true>(a, static_cast<hipStream_t>(stream), slabs, N, K / k_splits,
+                                                            k_splits, f);
     });
-#undef SWL_NF_PARTIAL
     return swl::check_launch();
 }
 
@@ -926,43 +871,20 @@ extern "C" int swl_gemm_skinny_packed_silu_gate_nf(void *out, const void *x, con
                                                    const void *w_up_gate_packed, int32_t M, int32_t I, int32_t K,
                                                    int64_t x_row_stride, int64_t out_row_stride, int32_t dtype,
                                                    swl_stream_t stream) {
-    if (M < 0 || I <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
+    const swl::GemmArgs a = swl::silu_gate_args(out, x, w_up_gate_packed, M, I, K, x_row_stride, out_row_stride);
+    SWL_GEMM_CHECK(swl::check_gemm_counts(a));
     if (M == 0) return SWL_OK;
-    if (!out || !x || !norm_w || !w_up_gate_packed) return SWL_ERR_BAD_ARG;
-    if (M > 32 || (I & 31) || (K & (swl::kKT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < I || (x_row_stride & 7) || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(x) || !swl::aligned16(w_up_gate_packed) || !swl::aligned16(norm_w) ||
-        (reinterpret_cast<uintptr_t>(out) & 7u))
-        return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_operands(a));
+    if (!norm_w) return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_shape(a));
+    SWL_GEMM_CHECK(swl::check_gemm_strides(a));
+    SWL_GEMM_CHECK(swl::check_gemm_alignment(a));
+    if (!swl::aligned16(norm_w)) return SWL_ERR_BAD_ARG;
     swl::GemmExtra f{};
     f.norm_w = norm_w;
     f.eps = eps;
-    const dim3 grid((I / 32 + 1) / 2, 1);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // r06b: up to 8 tokens, workgroups of ONE up tile + ONE gate tile (448 workgroups for Llama-3-8B instead of 224: every CU
-    // streams; one wave per SIMD, two workgroups per CU) — same K order per tile, hence the same bits. Each wave then stages
-    // twice the x rows, which costs more than the idle CUs from 9 tokens on (tools/gpu_silu_waves_ab.sh, four interleaved
-    // rounds, profiles/r06b_silu_gate_two_wave_groups_ab.jsonl: 39.2 vs 39.8 us at 1 token, 39.2 vs 40.0 at 8, 41.2 vs 40.3
-    // at 32). A/B switch: SWL_SILU_WAVES=2 / 4 forces one form for every M.
-    static const int forced = [] { const char *e = getenv("SWL_SILU_WAVES"); return !e ? 0 : e[0] == '2' ? 2 : e[0] == '4' ? 4 : 0; }();
-    const bool two_waves = forced ? forced == 2 : M <= 8;
-    if (two_waves && swl::use_ring(K)) {
-        SWL_DISPATCH_DTYPE(dtype, T, {
-            hipLaunchKernelGGL((swl::gemm_skinny_ring_kernel<T, swl::kGemmSiluGate, true, 3, 2, true>), dim3(I / 32, 1),
-                               dim3(128), 0, s, out, static_cast<const T *>(x), static_cast<const T *>(w_up_gate_packed), M,
-                               I, K, K, x_row_stride, out_row_stride, f);
-        });
-        return swl::check_launch();
-    }
     SWL_DISPATCH_DTYPE(dtype, T, {
-        if (swl::use_ring(K))
-            hipLaunchKernelGGL((swl::gemm_skinny_ring_kernel<T, swl::kGemmSiluGate, true, 3, swl::kGemmWaves, true>),
-                               grid, dim3(swl::kGemmWaves * 64), 0, s, out, static_cast<const T *>(x),
-                               static_cast<const T *>(w_up_gate_packed), M, I, K, K, x_row_stride, out_row_stride, f);
-        else
-            hipLaunchKernelGGL((swl::gemm_skinny_ring_kernel<T, swl::kGemmSiluGate, true, 2, swl::kGemmWaves, true>),
-                               grid, dim3(swl::kGemmWaves * 64), 0, s, out, static_cast<const T *>(x),
-                               static_cast<const T *>(w_up_gate_packed), M, I, K, K, x_row_stride, out_row_stride, f);
+        swl::launch_packed_ring<T, swl::kGemmSiluGate, true>(a, static_cast<hipStream_t>(stream), out, out_row_stride, K, 1, f);
     });
     return swl::check_launch();
 }
@@ -976,29 +898,24 @@ extern "C" int swl_gemm_skinny_packed_silu_gate_nx(void *out, const void *x, con
                                                    int32_t ssq_parts, const void *w_up_gate_packed, int32_t M, int32_t I,
                                                    int32_t K, int64_t x_row_stride, int64_t out_row_stride, int32_t dtype,
                                                    swl_stream_t stream) {
-    if (M < 0 || I <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
+    const swl::GemmArgs a = swl::silu_gate_args(out, x, w_up_gate_packed, M, I, K, x_row_stride, out_row_stride);
+    SWL_GEMM_CHECK(swl::check_gemm_counts(a));
     if (M == 0) return SWL_OK;
-    if (!out || !x || !norm_w || !w_up_gate_packed || !ssq_in) return SWL_ERR_BAD_ARG;
-    if (M > 32 || (I & 31) || (K & (swl::kKT - 1)) || ssq_parts <= 0 || (ssq_parts & 63) || !swl::use_ring(K)) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < I || (x_row_stride & 7) || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(x) || !swl::aligned16(w_up_gate_packed) || !swl::aligned16(norm_w) || !swl::aligned16(ssq_in) ||
-        (reinterpret_cast<uintptr_t>(out) & 7u))
-        return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_operands(a));
+    if (!norm_w || !ssq_in) return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_shape(a));
+    if (ssq_parts <= 0 || (ssq_parts & 63) || !swl::use_ring(K)) return SWL_ERR_UNSUPPORTED;
+    SWL_GEMM_CHECK(swl::check_gemm_strides(a));
+    SWL_GEMM_CHECK(swl::check_gemm_alignment(a));
+    if (!swl::aligned16(norm_w) || !swl::aligned16(ssq_in)) return SWL_ERR_BAD_ARG;
     swl::GemmExtra f{};
     f.norm_w = norm_w;
     f.eps = eps;
     f.ssq_in = ssq_in;
     f.ssq_parts = ssq_parts;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     SWL_DISPATCH_DTYPE(dtype, T, {
-        if (M <= 8)     // (two-wave workgroups: see swl_gemm_skinny_packed_silu_gate_nf)
-            hipLaunchKernelGGL((swl::gemm_skinny_ring_kernel<T, swl::kGemmSiluGate, true, 3, 2, true, true>), dim3(I / 32, 1),
-                               dim3(128), 0, s, out, static_cast<const T *>(x), static_cast<const T *>(w_up_gate_packed), M,
-                               I, K, K, x_row_stride, out_row_stride, f);
-        else
-            hipLaunchKernelGGL((swl::gemm_skinny_ring_kernel<T, swl::kGemmSiluGate, true, 3, swl::kGemmWaves, true, true>),
-                               dim3((I / 32 + 1) / 2, 1), dim3(swl::kGemmWaves * 64), 0, s, out, static_cast<const T *>(x),
-                               static_cast<const T *>(w_up_gate_packed), M, I, K, K, x_row_stride, out_row_stride, f);
+        swl::launch_packed_ring<T, swl::kGemmSiluGate, true, true>(a, static_cast<hipStream_t>(stream), out, out_row_stride, K,
+                                                                   1, f);
     });
     return swl::check_launch();
 }
@@ -1009,38 +926,27 @@ extern "C" int swl_gemm_skinny_packed_partial_nx(float *slabs, size_t slabs_byte
                                                  const float *ssq_in, int32_t ssq_parts, const void *w_packed, int32_t M,
                                                  int32_t N, int32_t K, int64_t x_row_stride, int32_t k_splits, int32_t dtype,
                                                  swl_stream_t stream) {
-    if (M < 0 || N <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
+    const swl::GemmArgs a{slabs, x, w_packed, slabs, slabs_bytes, M, N, K, x_row_stride, N, k_splits, 32, swl::kKT, true};
+    SWL_GEMM_CHECK(swl::check_gemm_counts(a));
     if (M == 0) return SWL_OK;
-    if (!slabs || !x || !norm_w || !w_packed || !ssq_in || k_splits < 1 || k_splits > 16) return SWL_ERR_BAD_ARG;
-    if (M > 32 || (N & 31) || (K & (swl::kKT - 1)) || K % (swl::kKT * k_splits) || ssq_parts <= 0 || (ssq_parts & 63))
-        return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || (x_row_stride & 7)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(x) || !swl::aligned16(w_packed) || !swl::aligned16(norm_w) || !swl::aligned16(slabs) || !swl::aligned16(ssq_in))
-        return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_operands(a));
+    if (!norm_w || !ssq_in) return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_k_splits(a));
+    SWL_GEMM_CHECK(swl::check_gemm_shape(a));
+    if (K % (swl::kKT * k_splits) || ssq_parts <= 0 || (ssq_parts & 63)) return SWL_ERR_UNSUPPORTED;
+    SWL_GEMM_CHECK(swl::check_gemm_strides(a));
+    SWL_GEMM_CHECK(swl::check_gemm_alignment(a));
+    if (!swl::aligned16(norm_w) || !swl::aligned16(ssq_in)) return SWL_ERR_BAD_ARG;
     if (slabs_bytes < static_cast<size_t>(k_splits) * M * N * sizeof(float)) return SWL_ERR_BAD_ARG;
     swl::GemmExtra f{};
     f.norm_w = norm_w;
     f.eps = eps;
     f.ssq_in = ssq_in;
     f.ssq_parts = ssq_parts;
-    const int kc = K / k_splits;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int64_t n64 = N;
-#define SWL_NX_PARTIAL(RD_, NWV_)                                                                                        \
-    hipLaunchKernelGGL((swl::gemm_skinny_ring_kernel<T, swl::kGemmPartial, true, RD_, NWV_, true, true>), grid,    \
-                       dim3(NWV_ * 64), 0, s, static_cast<void *>(slabs), static_cast<const T *>(x),                     \
-                       static_cast<const T *>(w_packed), M, N, K, kc, x_row_stride, n64, f)
     SWL_DISPATCH_DTYPE(dtype, T, {
-        if (swl::prefer_three_waves(N, k_splits)) {
-            const dim3 grid(N / 32 / 3, k_splits);
-            SWL_NX_PARTIAL(2, 3);
-        } else {
-            const dim3 grid((N / 32 + swl::kGemmWaves - 1) / swl::kGemmWaves, k_splits);
-            if (swl::use_ring(kc)) SWL_NX_PARTIAL(3, 4);
-            else SWL_NX_PARTIAL(2, 4);
-        }
+        swl::launch_packed_ring<T, swl::kGemmPartial, true, true>(a, static_cast<hipStream_t>(stream), slabs, N,
+                                                                  K / k_splits, k_splits, f);
     });
-#undef SWL_NX_PARTIAL
     return swl::check_launch();
 }
 
@@ -1229,26 +1135,21 @@ static int choose_k_splits_mt(int M, int N, int K) {
     return ks;
 }
 
-// reduce == false: stop after the partial slabs (ks >= 1) for a fused consumer
+template <typename T, int MODE>
+static void launch_packed_mt(const GemmArgs &a, hipStream_t stream, void *dst, int64_t dst_stride, int kc, int ks) {
+    const dim3 grid(four_wave_groups<MODE>(a.N), ks);
+    hipLaunchKernelGGL((gemm_packed_mt_kernel<T, 2, MODE>), grid, dim3(kGemmWaves * 64), 0, stream, dst,
+                       static_cast<const T *>(a.x), static_cast<const T *>(a.w), a.M, a.N, a.K, kc, a.x_row_stride, dst_stride);
+}
+
 template <typename T>
-static int run_gemm_packed_mt(T *out, const T *x, const T *wp, float *ws, size_t ws_bytes, int M, int N, int K,
-                              int64_t xs, int64_t os, int ks, hipStream_t stream, bool reduce = true) {
-    if (ks <= 0) ks = choose_k_splits_mt(M, N, K);
-    if (K % (kKT * ks) != 0) return SWL_ERR_UNSUPPORTED;
-    const dim3 grid((N / 32 + kGemmWaves - 1) / kGemmWaves, ks), block(kGemmWaves * 64);
-    const int kc = K / ks;
-    if (ks == 1 && reduce) {
-        hipLaunchKernelGGL((gemm_packed_mt_kernel<T, 2, kGemmDirect>), grid, block, 0, stream, out, x, wp, M, N, K, kc, xs, os);
-        return check_launch();
-    }
-    if (!ws || ws_bytes < static_cast<size_t>(ks) * M * N * sizeof(float)) return SWL_ERR_BAD_ARG;
-    const int64_t n64 = N;
-    hipLaunchKernelGGL((gemm_packed_mt_kernel<T, 2, kGemmPartial>), grid, block, 0, stream, ws, x, wp, M, N, K, kc, xs, n64);
-    if (!reduce) return check_launch();
-    const int64_t items = static_cast<int64_t>(M) * (N / 4);
-    hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(static_cast<unsigned>((items + 255) / 256)), dim3(256), 0,
-                       stream, out, ws, M, N, ks, os);
-    return check_launch();
+static int run_gemm_packed_mt(const GemmArgs &a, hipStream_t stream) {
+    const int ks = a.k_splits > 0 ? a.k_splits : choose_k_splits_mt(a.M, a.N, a.K);
+    if (a.K % (kKT * ks) != 0) return SWL_ERR_UNSUPPORTED;
+    const int kc = a.K / ks;
+    return run_splitk<T>(
+        a, ks, stream, [&](void *out) { launch_packed_mt<T, kGemmDirect>(a, stream, out, a.out_row_stride, kc, ks); },
+        [&](float *slabs) { launch_packed_mt<T, kGemmPartial>(a, stream, slabs, a.N, kc, ks); });
 }
 
 } // namespace swl
@@ -1259,21 +1160,11 @@ static int run_gemm_packed_mt(T *out, const T *x, const T *wp, float *ws, size_t
 extern "C" int swl_gemm_packed_mid(void *out, const void *x, const void *w_packed, void *workspace,
                                    size_t workspace_bytes, int32_t M, int32_t N, int32_t K, int64_t x_row_stride,
                                    int64_t out_row_stride, int32_t k_splits, int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || N <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
-    if (M == 0) return SWL_OK;
-    if (!out || !x || !w_packed) return SWL_ERR_BAD_ARG;
-    if (M > swl::kMidMaxM || (N & 31) || (K & (swl::kKT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < N || (x_row_stride & 7) || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(x) || !swl::aligned16(w_packed) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
-        (workspace && !swl::aligned16(workspace)))
-        return SWL_ERR_BAD_ARG;
-    if (k_splits < 0 || k_splits > 16 || (k_splits & (k_splits - 1))) return SWL_ERR_BAD_ARG;
-    SWL_DISPATCH_DTYPE(dtype, T, {
-        return swl::run_gemm_packed_mt<T>(static_cast<T *>(out), static_cast<const T *>(x),
-                                          static_cast<const T *>(w_packed), static_cast<float *>(workspace),
-                                          workspace_bytes, M, N, K, x_row_stride, out_row_stride, k_splits,
-                                          static_cast<hipStream_t>(stream));
-    });
+    const swl::GemmArgs a{out, x, w_packed, workspace, workspace_bytes, M, N, K, x_row_stride, out_row_stride, k_splits,
+                          swl::kMidMaxM, swl::kKT};
+    int rc;
+    if (swl::gemm_args_settled(a, rc)) return rc;
+    SWL_DISPATCH_DTYPE(dtype, T, { return swl::run_gemm_packed_mt<T>(a, static_cast<hipStream_t>(stream)); });
 }
 
 /* The split count swl_gemm_packed_mid picks for k_splits = 0 (0 = shape unsupported). */
@@ -1287,19 +1178,11 @@ extern "C" int swl_gemm_packed_mid_choose_splits(int32_t M, int32_t N, int32_t K
 extern "C" int swl_gemm_packed_mid_partial(float *slabs, size_t slabs_bytes, const void *x, const void *w_packed,
                                            int32_t M, int32_t N, int32_t K, int64_t x_row_stride, int32_t k_splits,
                                            int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || N <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
-    if (M == 0) return SWL_OK;
-    if (!slabs || !x || !w_packed || k_splits < 1 || k_splits > 16 || (k_splits & (k_splits - 1)))
-        return SWL_ERR_BAD_ARG;
-    if (M > swl::kMidMaxM || (N & 31) || (K & (swl::kKT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || (x_row_stride & 7) || !swl::aligned16(x) || !swl::aligned16(w_packed) ||
-        !swl::aligned16(slabs))
-        return SWL_ERR_BAD_ARG;
-    SWL_DISPATCH_DTYPE(dtype, T, {
-        return swl::run_gemm_packed_mt<T>(static_cast<T *>(nullptr), static_cast<const T *>(x),
-                                          static_cast<const T *>(w_packed), slabs, slabs_bytes, M, N, K, x_row_stride, N,
-                                          k_splits, static_cast<hipStream_t>(stream), false);
-    });
+    const swl::GemmArgs a{slabs, x, w_packed, slabs, slabs_bytes, M, N, K, x_row_stride, N, k_splits, swl::kMidMaxM, swl::kKT,
+                          true};
+    int rc;
+    if (swl::gemm_args_settled(a, rc)) return rc;
+    SWL_DISPATCH_DTYPE(dtype, T, { return swl::run_gemm_packed_mt<T>(a, static_cast<hipStream_t>(stream)); });
 }
 
 /* out[M, I] = up * silu(gate) of x . [up ; gate]^T for 32 < M <= 64 tokens on a packed weight (the medium-batch
@@ -1307,19 +1190,12 @@ extern "C" int swl_gemm_packed_mid_partial(float *slabs, size_t slabs_bytes, con
 extern "C" int swl_gemm_packed_mid_silu_gate(void *out, const void *x, const void *w_up_gate_packed, int32_t M,
                                              int32_t I, int32_t K, int64_t x_row_stride, int64_t out_row_stride,
                                              int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || I <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
-    if (M == 0) return SWL_OK;
-    if (!out || !x || !w_up_gate_packed) return SWL_ERR_BAD_ARG;
-    if (M > swl::kMidMaxM || (I & 31) || (K & (swl::kKT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < I || (x_row_stride & 7) || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
-    if (!swl::aligned16(x) || !swl::aligned16(w_up_gate_packed) || (reinterpret_cast<uintptr_t>(out) & 7u))
-        return SWL_ERR_BAD_ARG;
-    const dim3 grid((I / 32 + 1) / 2, 1), block(swl::kGemmWaves * 64);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const swl::GemmArgs a =
+        swl::silu_gate_args(out, x, w_up_gate_packed, M, I, K, x_row_stride, out_row_stride, swl::kMidMaxM);
+    int rc;
+    if (swl::gemm_args_settled(a, rc)) return rc;
     SWL_DISPATCH_DTYPE(dtype, T, {
-        hipLaunchKernelGGL((swl::gemm_packed_mt_kernel<T, 2, swl::kGemmSiluGate>), grid, block, 0, s, out,
-                           static_cast<const T *>(x), static_cast<const T *>(w_up_gate_packed), M, I, K, K,
-                           x_row_stride, out_row_stride);
+        swl::launch_packed_mt<T, swl::kGemmSiluGate>(a, static_cast<hipStream_t>(stream), out, out_row_stride, K, 1);
     });
     return swl::check_launch();
 }

@@ -32,10 +32,7 @@
 //     192 tokens). Timing-only ablations of the loop: tools/make_gemm_wide_ablations.py.
 // Bits: every output is the fp32 sum over k in ascending 16-element steps inside a K-chunk, chunks added in slab
 // order — the summation order of the M <= 64 kernels at the same split count.
-#include "swl_common.h"
-
-extern "C" int swl_splitk_reduce(void *out, const float *slabs, int32_t k_splits, int32_t M, int32_t N,
-                                 int64_t out_row_stride, int32_t dtype, swl_stream_t stream);
+#include "gemm_host.h"
 
 namespace swl {
 
@@ -308,9 +305,23 @@ static WidePlan gemm_wide_plan(int M, int N, int K, int forced_nwv, int forced_k
     return p;
 }
 
+// The checks of the wide entries alone, between the shared steps of gemm_host.h. The kernels index x rows in 32 bits:
+// SWL_ERR_UNSUPPORTED, behind the stride step.
+static int check_wide_x_extent(const GemmArgs &a) {
+    return static_cast<int64_t>(a.M) * a.x_row_stride >= (1ll << 31) ? SWL_ERR_UNSUPPORTED : SWL_OK;
+}
+static int check_wide_waves(int waves_per_group) {
+    return waves_per_group == 0 || waves_per_group == 4 || waves_per_group == 8 ? SWL_OK : SWL_ERR_BAD_ARG;
+}
+
+// dst: out[M, N] or the slabs, ks: the K splits (SiLU-gate: N = I, ks = 1, the workgroup owns nwv / 2 column tiles).
 template <typename T, int MODE>
-static void launch_wide(int mt, int nwv, int ts, dim3 grid, hipStream_t s, void *out, const T *x, const T *wp, int M, int N,
-                        int K, int kc, int64_t xs, int64_t os) {
+static void launch_wide(const GemmArgs &a, int nwv, int ts, int ks, hipStream_t s, void *out, int64_t os) {
+    const int M = a.M, N = a.N, K = a.K, mt = (M + 31) / 32, kc = K / ks;
+    const int wg_tiles = MODE == kWideSiluGate ? nwv / 2 : nwv;
+    const dim3 grid((N / 32 + wg_tiles - 1) / wg_tiles, ks);
+    const T *x = static_cast<const T *>(a.x), *wp = static_cast<const T *>(a.w);
+    const int64_t xs = a.x_row_stride;
 #define SWL_W_LAUNCH(MT_, NWV_, TS_)                                                                                \
     hipLaunchKernelGGL((gemm_packed_wide_kernel<T, MT_, NWV_, MODE, TS_>), grid, dim3(NWV_ * 64), 0, s, out, x, wp, M, N, \
                        K, kc, xs, os)
@@ -349,38 +360,25 @@ extern "C" int swl_gemm_packed_wide(void *out, const void *x, const void *w_pack
                                     size_t workspace_bytes, int32_t M, int32_t N, int32_t K, int64_t x_row_stride,
                                     int64_t out_row_stride, int32_t waves_per_group, int32_t k_splits, int32_t dtype,
                                     swl_stream_t stream) {
-    if (M < 0 || N <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
+    const swl::GemmArgs a{out, x, w_packed, workspace, workspace_bytes, M, N, K, x_row_stride, out_row_stride, k_splits, 256,
+                          swl::kWT};
+    SWL_GEMM_CHECK(swl::check_gemm_counts(a));
     if (M == 0) return SWL_OK;
-    if (!out || !x || !w_packed) return SWL_ERR_BAD_ARG;
-    if (M > 256 || (N & 31) || (K & (swl::kWT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < N || (x_row_stride & 7) || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
-    if (static_cast<int64_t>(M) * x_row_stride >= (1ll << 31)) return SWL_ERR_UNSUPPORTED;
-    if (!swl::aligned16(x) || !swl::aligned16(w_packed) || (reinterpret_cast<uintptr_t>(out) & 7u) ||
-        (workspace && !swl::aligned16(workspace)))
-        return SWL_ERR_BAD_ARG;
-    if (!(waves_per_group == 0 || waves_per_group == 4 || waves_per_group == 8)) return SWL_ERR_BAD_ARG;
-    if (k_splits < 0 || k_splits > 16 || (k_splits & (k_splits - 1))) return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_operands(a));
+    SWL_GEMM_CHECK(swl::check_gemm_shape(a));
+    SWL_GEMM_CHECK(swl::check_gemm_strides(a));
+    SWL_GEMM_CHECK(swl::check_wide_x_extent(a));
+    SWL_GEMM_CHECK(swl::check_gemm_alignment(a));
+    SWL_GEMM_CHECK(swl::check_wide_waves(waves_per_group));
+    SWL_GEMM_CHECK(swl::check_gemm_k_splits(a));
     const swl::WidePlan p = swl::gemm_wide_plan(M, N, K, waves_per_group, k_splits);
     if (K % (swl::kWT * p.ks) != 0) return SWL_ERR_UNSUPPORTED;
-    const int mt = (M + 31) / 32;
-    const int kc = K / p.ks;
-    const dim3 grid((N / 32 + p.nwv - 1) / p.nwv, p.ks);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (p.ks == 1) {
-        SWL_DISPATCH_DTYPE(dtype, T, {
-            swl::launch_wide<T, swl::kWideDirect>(mt, p.nwv, p.ts, grid, s, out, static_cast<const T *>(x),
-                                                  static_cast<const T *>(w_packed), M, N, K, kc, x_row_stride,
-                                                  out_row_stride);
-        });
-        return swl::check_launch();
-    }
-    if (!workspace || workspace_bytes < static_cast<size_t>(p.ks) * M * N * sizeof(float)) return SWL_ERR_BAD_ARG;
     SWL_DISPATCH_DTYPE(dtype, T, {
-        swl::launch_wide<T, swl::kWidePartial>(mt, p.nwv, p.ts, grid, s, workspace, static_cast<const T *>(x),
-                                               static_cast<const T *>(w_packed), M, N, K, kc, x_row_stride, N);
+        return swl::run_splitk<T>(
+            a, p.ks, s, [&](void *o) { swl::launch_wide<T, swl::kWideDirect>(a, p.nwv, p.ts, p.ks, s, o, out_row_stride); },
+            [&](float *slabs) { swl::launch_wide<T, swl::kWidePartial>(a, p.nwv, p.ts, p.ks, s, slabs, N); });
     });
-    if (swl::check_launch() != SWL_OK) return SWL_ERR_LAUNCH;
-    return swl_splitk_reduce(out, static_cast<const float *>(workspace), p.ks, M, N, out_row_stride, dtype, stream);
 }
 
 /* The split count swl_gemm_packed_wide picks for k_splits = 0 (0 = shape unsupported). */
@@ -396,21 +394,21 @@ extern "C" int swl_gemm_packed_wide_partial(float *slabs, size_t slabs_bytes, co
                                             int32_t M, int32_t N, int32_t K, int64_t x_row_stride,
                                             int32_t waves_per_group, int32_t k_splits, int32_t dtype,
                                             swl_stream_t stream) {
-    if (M < 0 || N <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
+    const swl::GemmArgs a{slabs, x, w_packed, slabs, slabs_bytes, M, N, K, x_row_stride, N, k_splits, 256, swl::kWT, true};
+    SWL_GEMM_CHECK(swl::check_gemm_counts(a));
     if (M == 0) return SWL_OK;
-    if (!slabs || !x || !w_packed || k_splits < 1 || k_splits > 16 || (k_splits & (k_splits - 1))) return SWL_ERR_BAD_ARG;
-    if (M > 256 || (N & 31) || (K & (swl::kWT - 1)) || K % (swl::kWT * k_splits)) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || (x_row_stride & 7) || !swl::aligned16(x) || !swl::aligned16(w_packed) || !swl::aligned16(slabs))
-        return SWL_ERR_BAD_ARG;
-    if (static_cast<int64_t>(M) * x_row_stride >= (1ll << 31)) return SWL_ERR_UNSUPPORTED;
-    if (!(waves_per_group == 0 || waves_per_group == 4 || waves_per_group == 8)) return SWL_ERR_BAD_ARG;
+    SWL_GEMM_CHECK(swl::check_gemm_operands(a));
+    SWL_GEMM_CHECK(swl::check_gemm_k_splits(a));
+    SWL_GEMM_CHECK(swl::check_gemm_shape(a));
+    if (K % (swl::kWT * k_splits)) return SWL_ERR_UNSUPPORTED;
+    SWL_GEMM_CHECK(swl::check_gemm_strides(a));
+    SWL_GEMM_CHECK(swl::check_gemm_alignment(a));   // (this entry looks at the alignment before the extent of x)
+    SWL_GEMM_CHECK(swl::check_wide_x_extent(a));
+    SWL_GEMM_CHECK(swl::check_wide_waves(waves_per_group));
     if (slabs_bytes < static_cast<size_t>(k_splits) * M * N * sizeof(float)) return SWL_ERR_BAD_ARG;
     const swl::WidePlan p = swl::gemm_wide_plan(M, N, K, waves_per_group, k_splits);
-    const dim3 grid((N / 32 + p.nwv - 1) / p.nwv, p.ks);
     SWL_DISPATCH_DTYPE(dtype, T, {
-        swl::launch_wide<T, swl::kWidePartial>((M + 31) / 32, p.nwv, p.ts, grid, static_cast<hipStream_t>(stream), slabs,
-                                               static_cast<const T *>(x), static_cast<const T *>(w_packed), M, N, K,
-                                               K / p.ks, x_row_stride, N);
+        swl::launch_wide<T, swl::kWidePartial>(a, p.nwv, p.ts, p.ks, static_cast<hipStream_t>(stream), slabs, N);
     });
     return swl::check_launch();
 }
@@ -421,24 +419,18 @@ extern "C" int swl_gemm_packed_wide_partial(float *slabs, size_t slabs_bytes, co
 extern "C" int swl_gemm_packed_wide_silu_gate(void *out, const void *x, const void *w_up_gate_packed, int32_t M,
                                               int32_t I, int32_t K, int64_t x_row_stride, int64_t out_row_stride,
                                               int32_t waves_per_group, int32_t dtype, swl_stream_t stream) {
-    if (M < 0 || I <= 0 || K <= 0) return SWL_ERR_BAD_ARG;
+    const swl::GemmArgs a{out, x, w_up_gate_packed, nullptr, 0, M, I, K, x_row_stride, out_row_stride, 1, 256, swl::kWT};
+    SWL_GEMM_CHECK(swl::check_gemm_counts(a));
     if (M == 0) return SWL_OK;
-    if (!out || !x || !w_up_gate_packed) return SWL_ERR_BAD_ARG;
-    if (M > 256 || (I & 31) || (K & (swl::kWT - 1))) return SWL_ERR_UNSUPPORTED;
-    if (x_row_stride < K || out_row_stride < I || (x_row_stride & 7) || (out_row_stride & 3)) return SWL_ERR_BAD_ARG;
-    if (static_cast<int64_t>(M) * x_row_stride >= (1ll << 31)) return SWL_ERR_UNSUPPORTED;
-    if (!swl::aligned16(x) || !swl::aligned16(w_up_gate_packed) || (reinterpret_cast<uintptr_t>(out) & 7u))
-        return SWL_ERR_BAD_ARG;
-    if (!(waves_per_group == 0 || waves_per_group == 4 || waves_per_group == 8)) return SWL_ERR_BAD_ARG;
-    const int nwv = waves_per_group ? waves_per_group : 4;
-    const int hw = nwv / 2;
-    const int mt = (M + 31) / 32;
-    const dim3 grid((I / 32 + hw - 1) / hw, 1);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    SWL_GEMM_CHECK(swl::check_gemm_operands(a));
+    SWL_GEMM_CHECK(swl::check_gemm_shape(a));
+    SWL_GEMM_CHECK(swl::check_gemm_strides(a));
+    SWL_GEMM_CHECK(swl::check_wide_x_extent(a));
+    SWL_GEMM_CHECK(swl::check_gemm_alignment(a));
+    SWL_GEMM_CHECK(swl::check_wide_waves(waves_per_group));
     SWL_DISPATCH_DTYPE(dtype, T, {
-        swl::launch_wide<T, swl::kWideSiluGate>(mt, nwv, 1, grid, s, out, static_cast<const T *>(x),
-                                                static_cast<const T *>(w_up_gate_packed), M, I, K, K, x_row_stride,
-                                                out_row_stride);
+        swl::launch_wide<T, swl::kWideSiluGate>(a, waves_per_group ? waves_per_group : 4, 1, 1,
+                                                static_cast<hipStream_t>(stream), out, out_row_stride);
     });
     return swl::check_launch();
 }

@@ -114,25 +114,34 @@ def _mid_ok(a: torch.Tensor, w: torch.Tensor) -> bool:
 _WIDE_MAX_M = 256
 
 
-def _launch_wide(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+def _launch_out(name: str, a: torch.Tensor, wt: torch.Tensor, n: int, ws, *tail) -> torch.Tensor:
+    """One of the `out, x, w, workspace, bytes, M, N, K, strides, <tail>` entries (swl_gemm_skinny[_packed], _packed_mid,
+    _packed_wide): wt is the weight in the form the entry streams, ws the split-K scratch (None: K is not split)."""
     m, k = a.shape
-    n = w.shape[0]
     out = torch.empty((m, n), dtype=a.dtype, device=a.device)
-    need = _hip.load().swl_gemm_packed_wide_workspace_bytes(m, n, k)
-    ws = _workspace(a.device, need) if need else None
-    _hip.call("swl_gemm_packed_wide", _hip.ptr(out), _hip.ptr(a), _hip.ptr(_packed_of(w)), _hip.ptr(ws),
-              ws.numel() * 4 if ws is not None else 0, m, n, k, _row_stride(a), n, 0, 0, _hip.dtype_code(a.dtype),
-              _hip.stream())
+    _hip.call(name, _hip.ptr(out), _hip.ptr(a), _hip.ptr(wt), _hip.ptr(ws), ws.numel() * 4 if ws is not None else 0,
+              m, n, k, _row_stride(a), n, *tail, _hip.dtype_code(a.dtype), _hip.stream())
     return out
+
+
+def _launch_silu(name: str, a: torch.Tensor, wt: torch.Tensor, pre=(), tail=()) -> torch.Tensor:
+    """One of the SiLU-gate entries: `out, x, w, <pre>, M, I, K, strides, <tail>`; wt = [up ; gate] as the entry streams it."""
+    m, k = a.shape
+    inter = wt.shape[0] // 2
+    out = torch.empty((m, inter), dtype=a.dtype, device=a.device)
+    _hip.call(name, _hip.ptr(out), _hip.ptr(a), _hip.ptr(wt), *pre, m, inter, k, _row_stride(a), inter, *tail,
+              _hip.dtype_code(a.dtype), _hip.stream())
+    return out
+
+
+def _launch_wide(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    need = _hip.load().swl_gemm_packed_wide_workspace_bytes(a.shape[0], w.shape[0], a.shape[1])
+    return _launch_out("swl_gemm_packed_wide", a, _packed_of(w), w.shape[0], _workspace(a.device, need) if need else None,
+                       0, 0)
 
 
 def _launch_wide_silu(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    m, k = a.shape
-    inter = w.shape[0] // 2
-    out = torch.empty((m, inter), dtype=a.dtype, device=a.device)
-    _hip.call("swl_gemm_packed_wide_silu_gate", _hip.ptr(out), _hip.ptr(a), _hip.ptr(_packed_of(w)), m, inter, k,
-              _row_stride(a), inter, 0, _hip.dtype_code(a.dtype), _hip.stream())
-    return out
+    return _launch_silu("swl_gemm_packed_wide_silu_gate", a, _packed_of(w), tail=(0,))
 
 
 def _wide_ok(a: torch.Tensor, w: torch.Tensor) -> bool:
@@ -200,24 +209,15 @@ def linear(a: torch.Tensor, w: torch.Tensor, skinny: bool = False) -> torch.Tens
     if skinny and _mid_ok(a, w):
         m, k = a.shape
         n = w.shape[0]
-        out = torch.empty((m, n), dtype=a.dtype, device=a.device)
         ks = _hip.load().swl_gemm_packed_mid_choose_splits(m, n, k)
-        ws = _workspace(a.device, ks * m * n * 4 if ks > 1 else 0)
-        _hip.call("swl_gemm_packed_mid", _hip.ptr(out), _hip.ptr(a), _hip.ptr(_packed_of(w)), _hip.ptr(ws),
-                  ws.numel() * 4, m, n, k, _row_stride(a), n, ks, _hip.dtype_code(a.dtype), _hip.stream())
-        return out
+        return _launch_out("swl_gemm_packed_mid", a, _packed_of(w), n, _workspace(a.device, ks * m * n * 4 if ks > 1 else 0), ks)
     if skinny and _skinny_ok(a, w):
         m, k = a.shape
         n = w.shape[0]
-        out = torch.empty((m, n), dtype=a.dtype, device=a.device)
         need = _hip.load().swl_gemm_skinny_workspace_bytes(m, n, k)
-        ws = _workspace(a.device, need) if need else None
         wp = _packed_of(w)
-        _hip.call("swl_gemm_skinny_packed" if wp is not None else "swl_gemm_skinny", _hip.ptr(out), _hip.ptr(a),
-                  _hip.ptr(wp if wp is not None else w), _hip.ptr(ws),
-                  ws.numel() * 4 if ws is not None else 0, m, n, k, _row_stride(a), n, 0,
-                  _hip.dtype_code(a.dtype), _hip.stream())
-        return out
+        return _launch_out("swl_gemm_skinny_packed" if wp is not None else "swl_gemm_skinny", a, wp if wp is not None else w,
+                           n, _workspace(a.device, need) if need else None, 0)
     return _blas_linear(a, w)
 
 
@@ -262,38 +262,25 @@ def linear_splitk(a: torch.Tensor, w: torch.Tensor, always: bool = False):
     """Like linear(a, w, skinny=True) but returns SplitKPartials when the kernel splits K (the caller
     hands them to a fused consumer); falls through to `linear` otherwise. `always`: also return the
     partial form (a single fp32 slab) when K is not split — for consumers that only take slabs."""
+    m, k = a.shape if a.dim() == 2 else (0, 0)
+    n = w.shape[0]
+    wp = _packed_of(w)
+    # the tier's slab entry, the weight form it streams, its split count and what it takes between the x stride and k_splits
     if _wide_ok(a, w):                          # large batch: slabs for the add+norm / slab-fed attention consumers
-        m, k = a.shape
-        n = w.shape[0]
-        ks = _hip.load().swl_gemm_packed_wide_choose_splits(m, n, k)
-        if ks > 1 or (always and ks == 1):
-            ws = _workspace(a.device, ks * m * n * 4)
-            _hip.call("swl_gemm_packed_wide_partial", _hip.ptr(ws), ws.numel() * 4, _hip.ptr(a), _hip.ptr(_packed_of(w)),
-                      m, n, k, _row_stride(a), 0, ks, _hip.dtype_code(a.dtype), _hip.stream())
-            return SplitKPartials(ws, ks, m, n, a.dtype)
+        name, wt, ks, tail = "swl_gemm_packed_wide_partial", wp, _hip.load().swl_gemm_packed_wide_choose_splits(m, n, k), (0,)
+    elif _mid_ok(a, w):                         # medium batch on a packed weight: same contract, own kernel
+        name, wt, ks, tail = "swl_gemm_packed_mid_partial", wp, _hip.load().swl_gemm_packed_mid_choose_splits(m, n, k), ()
+    elif _skinny_ok(a, w) and wp is not None:
+        name, wt, ks, tail = "swl_gemm_skinny_packed_partial", wp, _hip.load().swl_gemm_skinny_packed_choose_splits(n, k), ()
+    elif _skinny_ok(a, w):
+        name, wt, ks, tail = "swl_gemm_skinny_partial", w, _hip.load().swl_gemm_skinny_choose_splits(n, k), ()
+    else:
         return linear(a, w, skinny=True)
-    if _mid_ok(a, w):                           # medium batch on a packed weight: same contract, own kernel
-        m, k = a.shape
-        n = w.shape[0]
-        ks = _hip.load().swl_gemm_packed_mid_choose_splits(m, n, k)
-        if ks > 1 or (always and ks == 1):
-            ws = _workspace(a.device, ks * m * n * 4)
-            _hip.call("swl_gemm_packed_mid_partial", _hip.ptr(ws), ws.numel() * 4, _hip.ptr(a), _hip.ptr(_packed_of(w)),
-                      m, n, k, _row_stride(a), ks, _hip.dtype_code(a.dtype), _hip.stream())
-            return SplitKPartials(ws, ks, m, n, a.dtype)
-        return linear(a, w, skinny=True)
-    if _skinny_ok(a, w):
-        m, k = a.shape
-        n = w.shape[0]
-        wp = _packed_of(w)
-        lib = _hip.load()
-        ks = lib.swl_gemm_skinny_packed_choose_splits(n, k) if wp is not None else lib.swl_gemm_skinny_choose_splits(n, k)
-        if ks > 1 or (always and ks == 1):
-            ws = _workspace(a.device, ks * m * n * 4)
-            _hip.call("swl_gemm_skinny_packed_partial" if wp is not None else "swl_gemm_skinny_partial", _hip.ptr(ws),
-                      ws.numel() * 4, _hip.ptr(a), _hip.ptr(wp if wp is not None else w), m, n, k,
-                      _row_stride(a), ks, _hip.dtype_code(a.dtype), _hip.stream())
-            return SplitKPartials(ws, ks, m, n, a.dtype)
+    if ks > 1 or (always and ks == 1):
+        ws = _workspace(a.device, ks * m * n * 4)
+        _hip.call(name, _hip.ptr(ws), ws.numel() * 4, _hip.ptr(a), _hip.ptr(wt), m, n, k, _row_stride(a), *tail, ks,
+                  _hip.dtype_code(a.dtype), _hip.stream())
+        return SplitKPartials(ws, ks, m, n, a.dtype)
     return linear(a, w, skinny=True)
 
 
@@ -309,32 +296,18 @@ def linear_silu_gate(a: torch.Tensor, w_up_gate: torch.Tensor, row_scale=None):
     multiplied by the pending 1/rms of their token before they are rounded."""
     if row_scale is not None:
         assert row_scaled_silu_gate_ok(a, w_up_gate) and row_scale.ssq.shape == (row_scale.parts, a.shape[0])
-        m, k = a.shape
-        inter = w_up_gate.shape[0] // 2
-        out = torch.empty((m, inter), dtype=a.dtype, device=a.device)
-        _hip.call("swl_gemm_skinny_packed_silu_gate_rs", _hip.ptr(out), _hip.ptr(a), _hip.ptr(_packed_of(w_up_gate)),
-                  _hip.ptr(row_scale.ssq), row_scale.parts, row_scale.eps, m, inter, k, _row_stride(a), inter,
-                  _hip.dtype_code(a.dtype), _hip.stream())
-        return out
+        return _launch_silu("swl_gemm_skinny_packed_silu_gate_rs", a, _packed_of(w_up_gate),
+                            pre=(_hip.ptr(row_scale.ssq), row_scale.parts, row_scale.eps))
     if _wide_silu_ok(a, w_up_gate):        # large batch, packed weight
         return _launch_wide_silu(a, w_up_gate)
     if _mid_ok(a, w_up_gate) and w_up_gate.shape[0] % 64 == 0:   # medium batch, packed weight
-        m, k = a.shape
-        inter = w_up_gate.shape[0] // 2
-        out = torch.empty((m, inter), dtype=a.dtype, device=a.device)
-        _hip.call("swl_gemm_packed_mid_silu_gate", _hip.ptr(out), _hip.ptr(a), _hip.ptr(_packed_of(w_up_gate)), m,
-                  inter, k, _row_stride(a), inter, _hip.dtype_code(a.dtype), _hip.stream())
-        return out
+        return _launch_silu("swl_gemm_packed_mid_silu_gate", a, _packed_of(w_up_gate))
     if not _skinny_ok(a, w_up_gate) or w_up_gate.shape[0] % 64 != 0:
         return None
-    m, k = a.shape
-    inter = w_up_gate.shape[0] // 2
-    out = torch.empty((m, inter), dtype=a.dtype, device=a.device)
     wp = _packed_of(w_up_gate)
-    _hip.call("swl_gemm_skinny_packed_silu_gate" if wp is not None else "swl_gemm_skinny_silu_gate", _hip.ptr(out),
-              _hip.ptr(a), _hip.ptr(wp if wp is not None else w_up_gate), m, inter, k,
-              _row_stride(a), inter, _hip.dtype_code(a.dtype), _hip.stream())
-    return out
+    if wp is not None:
+        return _launch_silu("swl_gemm_skinny_packed_silu_gate", a, wp)
+    return _launch_silu("swl_gemm_skinny_silu_gate", a, w_up_gate)
 
 
 # ---- o_proj / down_proj with K split inside the workgroup and the residual add in the epilogue (csrc/gemm_rows.hip) ----

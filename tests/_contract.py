@@ -360,7 +360,8 @@ def _rows():
         [P("slabs"), V("slabs_bytes", KS * M * N * 4), P("x"), P("norm_w"), V("eps", 1e-5), P("ssq_in"), V("ssq_parts", 64),
          P("w"), C("M", M), C("N", N), C("K", kx), S("x_row_stride", kx + 8, kx), V("k_splits", KS), DT(), ST()],
         [("M = 33", "M", 33, UNSUP), ("N % 32", "N", 100, UNSUP), ("K % 128", "K", kx - 8, UNSUP),
-         ("ssq_parts % 64", "ssq_parts", 65, UNSUP), ("k_splits 0", "k_splits", 0, BAD), ("k_splits 32", "k_splits", 32, BAD),
+         ("ssq_parts % 64", "ssq_parts", 65, UNSUP), ("k_splits 0", "k_splits", 0, BAD), ("k_splits 3", "k_splits", 3, BAD),
+         ("k_splits 32", "k_splits", 32, BAD),
          ("k_splits -1", "k_splits", -1, BAD), ("K % (128 * k_splits)", "k_splits", 16, UNSUP)] + sl_extra)
     add("swl_splitk_reduce",
         [P("out", 8), P("slabs"), V("k_splits", KS), C("M", M), V("N", N), S("out_row_stride", N + 4, N, 4), DT(), ST()],
