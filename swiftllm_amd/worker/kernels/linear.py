@@ -358,14 +358,14 @@ def nf_ok(r: torch.Tensor, w: torch.Tensor, norm_w: torch.Tensor) -> bool:
 
 def linear_splitk_nf(r: torch.Tensor, norm_w: torch.Tensor, w: torch.Tensor, eps: float):
     """linear_splitk(round(r * norm_w), w, always=True) with the rows' sums of squares on the side: returns (SplitKPartials,
-    RowScalePending) — the pending 1/rms is applied by the consumer of the slabs (paged_attention_from_qkv_splitk)."""
+    RowScalePending) — the pending 1/rms is applied by the consumer of the slabs (paged_attention_from_qkv_splitk). The kernel
+    takes even K splits of whole 128-column tiles only: the caller makes sure of that (LayerFacts.qkv_even)."""
     from .rmsnorm import RowScalePending
     assert nf_ok(r, w, norm_w)
     m, k = r.shape
     n = w.shape[0]
     ks = int(_hip.load().swl_gemm_skinny_packed_choose_splits(n, k))
-    if k % (128 * ks):
-        return None
+    assert k % (128 * ks) == 0, "K has no even split of whole 128-column tiles (the layer's route checks qkv_even)"
     ws = _workspace(r.device, ks * m * n * 4)
     ssq = torch.empty((ks, m), dtype=torch.float32, device=r.device)
     _hip.call("swl_gemm_skinny_packed_partial_nf", _hip.ptr(ws), ws.numel() * 4, _hip.ptr(ssq), _hip.ptr(r), _hip.ptr(norm_w),
@@ -395,13 +395,12 @@ def nx_ok(r: torch.Tensor, w: torch.Tensor, norm_w: torch.Tensor) -> bool:
 
 def linear_splitk_nx(r: torch.Tensor, norm_w: torch.Tensor, w: torch.Tensor, eps: float, ssq: torch.Tensor):
     """linear_splitk(rmsnorm(r) * norm_w, w, always=True) from the raw residual rows and their per-tile sums of squares
-    (linear_rows_add(..., with_ssq=True)): SplitKPartials with nothing pending, or None when K has no even split."""
+    (linear_rows_add(..., with_ssq=True)): SplitKPartials with nothing pending. K must split evenly, as for linear_splitk_nf."""
     assert nx_ok(r, w, norm_w) and ssq.dtype == torch.float32 and ssq.shape == (r.shape[0], r.shape[1] // 16) and ssq.is_contiguous()
     m, k = r.shape
     n = w.shape[0]
     ks = int(_hip.load().swl_gemm_skinny_packed_choose_splits(n, k))
-    if k % (128 * ks):
-        return None
+    assert k % (128 * ks) == 0, "K has no even split of whole 128-column tiles (the layer's route checks qkv_even)"
     ws = _workspace(r.device, ks * m * n * 4)
     _hip.call("swl_gemm_skinny_packed_partial_nx", _hip.ptr(ws), ws.numel() * 4, _hip.ptr(r), _hip.ptr(norm_w), eps,
               _hip.ptr(ssq), ssq.shape[1], _hip.ptr(_packed_of(w)), m, n, k, _row_stride(r), ks, _hip.dtype_code(r.dtype),

@@ -233,6 +233,8 @@ class LlamaModel:
                 ecfg.pack_decode_weights = False
                 return
             pack_decode_weights(self.weight)
+        for layer in self.transformer_layers or ():     # (a call after load_weights: the routes follow the packed twins)
+            layer.refresh_facts()
         self._build_decode_engine()
 
     def _build_decode_engine(self):
@@ -507,11 +509,13 @@ class LlamaModel:
         self._edit_done.record()
 
     def _make_infer_state(self, plan: BatchPlan, dev: dict, ignore_kvcache: bool,
-                          sampled: bool = False, processed: bool = False) -> LlamaInferState:
+                          sampled: bool = False, processed: bool = False, scratch_rows: int = None) -> LlamaInferState:
+        """`scratch_rows`: rows whose flash-decoding partials the persistent scratch must hold when the step splits its
+        sequences — the decoding sequences (default); a verify step: every row."""
         nsb = plan.num_seq_blocks
         if nsb > 1:
-            need = _hip.scratch_bytes(plan.num_decoding_seqs, self.model_config.num_q_heads,
-                                      self.model_config.head_dim, nsb) // 4
+            need = _hip.scratch_bytes(plan.num_decoding_seqs if scratch_rows is None else scratch_rows,
+                                      self.model_config.num_q_heads, self.model_config.head_dim, nsb) // 4
             if self._scratch is None or self._scratch.numel() < need:
                 self._scratch = torch.empty(need, dtype=torch.float32, device=self.device)
                 self._drop_decode_graphs()
@@ -926,6 +930,28 @@ class LlamaModel:
                                    f"({rope_rows} positions)")
         return ctx
 
+    def _begin_step(self, plan: BatchPlan, seq_ids_list, ignore_kvcache: bool = False, sampling=None, edits=None):
+        """What every step does between its plan and its launches: the rotary-table check, KV blocks for the caller's
+        sequences, the plan's upload and — a sampled / processed step — its parameters' and entries'. Returns the plan's
+        device views and the host times at which the checked plan and the blocks were ready (host_profile's sections)."""
+        num_real = plan.num_real_seqs = len(seq_ids_list)
+        longest = max(plan.seq_lengths_list)
+        if longest > self._cos_cached.shape[0]:
+            # the reference indexes its rope cache out of range here (model.py:350); fail on the host
+            raise RuntimeError(
+                f"sequence length {longest} exceeds the rotary table ({self._cos_cached.shape[0]} positions = "
+                "max_position_embeddings * rope_scaling + 128); use a checkpoint with rope scaling")
+        t_plan = time.perf_counter()
+        if not ignore_kvcache:
+            self.gpu_block_manager.allocate_blocks_for_seqs(seq_ids_list, plan.seq_lengths_list[:num_real])
+        t_blocks = time.perf_counter()
+        dev = self._upload_plan(plan)
+        if sampling is not None:
+            self._upload_sampling(sampling, plan.batch_size)
+        if edits is not None:
+            self._upload_edits(edits, plan.batch_size)
+        return dev, t_plan, t_blocks
+
     def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
                       prefill_ctx_lens=None, edits=None, lora_slots=None):
         prof = self._host_prof
@@ -963,22 +989,7 @@ class LlamaModel:
         else:
             plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                               self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
-            plan.num_real_seqs = num_real
-        longest = max(plan.seq_lengths_list)
-        if longest > self._cos_cached.shape[0]:
-            # the reference indexes its rope cache out of range here (model.py:350); fail on the host
-            raise RuntimeError(
-                f"sequence length {longest} exceeds the rotary table ({self._cos_cached.shape[0]} positions = "
-                "max_position_embeddings * rope_scaling + 128); use a checkpoint with rope scaling")
-        t1 = time.perf_counter() if prof is not None else 0.0
-        if not ignore_kvcache:
-            self.gpu_block_manager.allocate_blocks_for_seqs(seq_ids_list, plan.seq_lengths_list[:num_real])
-        t2 = time.perf_counter() if prof is not None else 0.0
-        dev = self._upload_plan(plan)
-        if sampled:
-            self._upload_sampling(sampling, plan.batch_size)
-        if processed:
-            self._upload_edits(edits, plan.batch_size)
+        dev, t1, t2 = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits)
         t3 = time.perf_counter() if prof is not None else 0.0
         pure_decode = plan.num_prefill_seqs == 0
         nxt = None
@@ -1021,19 +1032,7 @@ class LlamaModel:
         num_real = len(input_ids_list)
         plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                           self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
-        plan.num_real_seqs = num_real
-        longest = max(plan.seq_lengths_list)
-        if longest > self._cos_cached.shape[0]:
-            raise RuntimeError(
-                f"sequence length {longest} exceeds the rotary table ({self._cos_cached.shape[0]} positions = "
-                "max_position_embeddings * rope_scaling + 128); use a checkpoint with rope scaling")
-        if not ignore_kvcache:
-            self.gpu_block_manager.allocate_blocks_for_seqs(seq_ids_list, plan.seq_lengths_list[:num_real])
-        dev = self._upload_plan(plan)
-        if sampling is not None:
-            self._upload_sampling(sampling, plan.batch_size)
-        if edits is not None:
-            self._upload_edits(edits, plan.batch_size)
+        dev = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits)[0]
         num_prefill = num_real - len(decoding_seq_lens_list)
         row_slots = rows_of_sequences(lora_slots, [len(ids) for ids in input_ids_list[:num_prefill]])
         state = self._make_infer_state(plan, dev, ignore_kvcache, sampling is not None, edits is not None)
@@ -1086,18 +1085,8 @@ class LlamaModel:
         self._lookahead = None      # a prepared decode step does not survive a verify step
         self.gpu_block_manager.host.surplus_ok.update(seq_ids_list)     # rejected drafts leave their block with the sequence
         plan = plan_verify(input_ids_list, seq_ids_list, ctx, self.model_config.num_kv_heads, self._num_slots)
-        plan.num_real_seqs = len(input_ids_list)
-        self.gpu_block_manager.allocate_blocks_for_seqs(seq_ids_list, plan.seq_lengths_list)
-        dev = self._upload_plan(plan)
-        nsb = plan.num_seq_blocks
-        if nsb > 1:
-            need = _hip.scratch_bytes(plan.num_tokens, self.model_config.num_q_heads, self.model_config.head_dim, nsb) // 4
-            if self._scratch is None or self._scratch.numel() < need:
-                self._scratch = torch.empty(need, dtype=torch.float32, device=self.device)
-                self._drop_decode_graphs()
-        state = self._make_infer_state(plan, dev, False)
-        state.paged_attn_scratch = self._scratch if nsb > 1 else None
-        tokens = self._forward(dev["input_ids"], state)
+        dev = self._begin_step(plan, seq_ids_list)[0]
+        tokens = self._forward(dev["input_ids"], self._make_infer_state(plan, dev, False, scratch_rows=plan.num_tokens))
         if self.after_launch_hook is not None:
             self.after_launch_hook()
         flat = tokens.tolist()

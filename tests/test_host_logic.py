@@ -799,3 +799,111 @@ def test_gemm_wide_ablation_tool_still_matches_the_kernel_source():
     for name, edits in tool.EDITS.items():
         for old, _new in edits:
             assert src.count(old) == 1, (name, old[:60])
+
+
+def test_layer_route_of_llama3_8b_by_batch_size_dtype_and_switch(monkeypatch):
+    """worker/layers/transformer_layer.py: decide_route on the static facts of a Llama-3-8B layer (4096 / 32 / 8 / 128 / 14336,
+    fused qkv, packed twins; the library is loaded for its host arithmetic only) and step facts for 1..256 decoding sequences.
+    The table is written by hand from the rules the layer had before the decision was one function, and agrees with
+    tests/golden/layer_launch_traces.json. The function is pure: no kernel entry is called, no device is initialised, and
+    the facts it was given are unchanged."""
+    from swiftllm_amd.worker.layers import transformer_layer as T
+    from swiftllm_amd.worker.layers.transformer_layer import AttnNorm, Attn, Down, Input, OFfn, QKV, StepFacts
+
+    def forbidden(name, *args):
+        raise AssertionError(f"the route decision launched {name}")
+    monkeypatch.setattr(_hip, "call", forbidden)
+    device_was_up = torch.cuda.is_initialized()
+    shapes = dict(qkv=(6144, 4096), o=(4096, 4096), up_gate=(2 * 14336, 4096), down=(4096, 14336))
+
+    def facts(dtype=torch.bfloat16, tuning=None, packed=frozenset(shapes), **engine):
+        ecfg = EngineConfig(model_path="", use_dummy=True, block_size=16, gpu_mem_utilization=0.9, num_cpu_blocks=8,
+                            max_seqs_in_block_table=64, max_blocks_per_seq=32, max_batch_size=256, max_tokens_in_batch=4096,
+                            tuning=tuning, **engine)
+        return T.layer_facts(ecfg, dtype, 4096, 32, 128, shapes, packed, _hip.load())
+
+    def step(m, kind=Input.TENSOR, **kw):
+        base = dict(input=kind, prefill=False, m=m, ignore_kvcache=False, positions=True, split=False, verify=False,
+                    chunked=False, lora=False)
+        base.update(kw)
+        return StepFacts(**base)
+
+    bf16, f16 = facts(), facts(torch.float16)
+    before = tuple(bf16)
+    for m in range(1, 257):
+        for f, nf in ((bf16, True), (f16, False)):
+            first = T.decide_route(f, step(m))
+            assert (first.attn_norm, first.qkv, first.attention, first.piggyback, first.merge, first.lora) == \
+                (AttnNorm.FUSED, QKV.SLABS_ATTN, Attn.DECODE, False, False, False), (m, nf)
+            if m <= 16:         # both projections row-owned: the layers hand a RawResidual on
+                want = (OFfn.ROWS_NF, Down.ROWS) if nf else (OFfn.ROWS_NX, Down.ROWS_SSQ)
+                later = T.decide_route(f, step(m, Input.RAW if nf else Input.RAW_SSQ))
+                assert later.attn_norm is (AttnNorm.RAW_NF if nf else AttnNorm.RAW_NX)
+                with pytest.raises(AssertionError):     # (the other kind of RawResidual cannot arrive here)
+                    T.decide_route(f, step(m, Input.RAW_SSQ if nf else Input.RAW))
+            else:
+                want = ((OFfn.ROWS_NF if nf else OFfn.ROWS_NX) if m <= 32 else OFfn.SPLITK_FUSED, Down.SPLITK)
+                later = T.decide_route(f, step(m, Input.SLABS))
+                assert later.attn_norm is (AttnNorm.SCALE_PENDING if nf and m <= 32 else AttnNorm.FUSED)
+                with pytest.raises(AssertionError):     # (no RawResidual is handed on at this batch size)
+                    T.decide_route(f, step(m, Input.RAW if nf else Input.RAW_SSQ))
+            assert (first.o_ffn, first.down) == want == (later.o_ffn, later.down), (m, nf)
+            assert later._replace(attn_norm=first.attn_norm) == first
+    assert tuple(bf16) == before
+
+    # rows_decode off: <= 2 bfloat16 sequences take the tiny route once slabs are handed on; with split sequences o_proj
+    # merges the flash-decoding partials; 3..32 the deferred consumers
+    no_rows = facts(tuning=dict(rows_decode=False))
+    for m in (1, 2):
+        r = T.decide_route(no_rows, step(m, Input.SLABS))
+        assert (r.attn_norm, r.qkv, r.merge, r.o_ffn, r.down) == (AttnNorm.TINY, QKV.SLABS_ATTN, False, OFfn.TINY, Down.SPLITK)
+        assert T.decide_route(no_rows, step(m, Input.SLABS, split=True)) == r._replace(merge=True)
+        r = T.decide_route(no_rows, step(m, split=True))        # (the first layer of the step: a tensor comes in)
+        assert (r.attn_norm, r.merge, r.o_ffn, r.down) == (AttnNorm.FUSED, False, OFfn.SPLITK_DEFERRED, Down.SPLITK)
+    for m in (3, 32, 33):
+        r = T.decide_route(no_rows, step(m, Input.SLABS))
+        assert (r.attn_norm, r.o_ffn) == ((AttnNorm.SCALE_PENDING, OFfn.SPLITK_DEFERRED) if m <= 32 else
+                                          (AttnNorm.FUSED, OFfn.SPLITK_FUSED))
+    r = T.decide_route(facts(tuning=dict(rows_decode=False, tiny_decode_batches=False)), step(1, Input.SLABS))
+    assert (r.attn_norm, r.o_ffn) == (AttnNorm.SCALE_PENDING, OFfn.SPLITK_DEFERRED)
+    r = T.decide_route(facts(torch.float16, tuning=dict(rows_decode=False)), step(1, Input.SLABS))
+    assert (r.attn_norm, r.o_ffn, r.down) == (AttnNorm.FUSED, OFfn.SPLITK_FUSED, Down.SPLITK)
+    # defer_rmsnorm off: bfloat16 runs the exact norm on the fly
+    no_defer = facts(tuning=dict(defer_rmsnorm=False))
+    assert [(r.o_ffn, r.down) for r in (T.decide_route(no_defer, step(m)) for m in (1, 16, 17, 32, 33))] == \
+        [(OFfn.ROWS_NX, Down.ROWS_SSQ)] * 2 + [(OFfn.ROWS_NX, Down.SPLITK)] * 2 + [(OFfn.SPLITK_FUSED, Down.SPLITK)]
+    # the other switches, one at a time
+    r = T.decide_route(facts(tuning=dict(fuse_rope_into_attention=False)), step(8))
+    assert (r.qkv, r.o_ffn, r.down) == (QKV.SLABS_ROTARY, OFfn.SPLITK_DEFERRED, Down.SPLITK)
+    for f in (facts(tuning=dict(fuse_splitk_consumers=False)), facts(use_skinny_gemm=False)):
+        r = T.decide_route(f, step(8))
+        assert (r.attn_norm, r.qkv, r.o_ffn, r.down) == (AttnNorm.FUSED, QKV.FUSED_DECODE, OFfn.PLAIN, Down.PLAIN)
+    r = T.decide_route(facts(tuning=dict(fuse_rope_kvstore=False)), step(8))
+    assert (r.qkv, r.o_ffn, r.down) == (QKV.ROTARY_THEN_STORE, OFfn.SPLITK_DEFERRED, Down.SPLITK)
+    # without packed twins: no rows, no norm on the fly, no tiny route — the split-K consumers of the row-major kernels
+    r = T.decide_route(facts(packed=frozenset()), step(1, Input.SLABS))
+    assert (r.attn_norm, r.qkv, r.o_ffn, r.down) == (AttnNorm.SCALE_PENDING, QKV.SLABS_ATTN, OFfn.SPLITK_FUSED, Down.SPLITK)
+    # FP8 pools: rotary, then the quantising store; no slab-fed attention, nothing that hangs on it
+    fp8 = facts(kv_cache_dtype="fp8_e4m3")
+    for m in (1, 16, 32, 100):
+        r = T.decide_route(fp8, step(m))
+        assert (r.qkv, r.attention, r.down) == (QKV.ROTARY_THEN_STORE, Attn.DECODE, Down.SPLITK)
+        assert r.o_ffn is (OFfn.SPLITK_DEFERRED if m <= 32 else OFfn.SPLITK_FUSED)
+        assert T.decide_route(fp8, step(m, Input.SLABS)).attn_norm is AttnNorm.FUSED
+    # a prompt row in the batch: no split-K form anywhere; the attention that serves the prompt rows
+    for f in (bf16, f16, no_rows):
+        for m in (0, 3):
+            r = T.decide_route(f, step(m, prefill=True))
+            assert r == T.LayerRoute(AttnNorm.FUSED, QKV.FUSED_PREFILL, Attn.FRESH, m > 0, False, OFfn.PLAIN, Down.PLAIN, False)
+            assert T.decide_route(f, step(m, prefill=True, chunked=True)) == r._replace(attention=Attn.PAGED)
+            assert T.decide_route(f, step(m, prefill=True, chunked=True, verify=True)) == r._replace(attention=Attn.VERIFY)
+    r = T.decide_route(bf16, step(0, prefill=True, ignore_kvcache=True))
+    assert (r.qkv, r.attention, r.o_ffn) == (QKV.ROTARY_ONLY, Attn.FRESH, OFfn.PLAIN)
+    assert T.decide_route(fp8, step(0, prefill=True)).qkv is QKV.ROTARY_THEN_STORE
+    # a LoRA step: the LoRA body, whatever the batch
+    for kw in (dict(m=1), dict(m=40), dict(m=2, prefill=True), dict(m=0, prefill=True, ignore_kvcache=True)):
+        r = T.decide_route(bf16, step(lora=True, **kw))
+        assert r.lora and (r.attn_norm, r.o_ffn, r.down) == (AttnNorm.FUSED, OFfn.PLAIN, Down.PLAIN)
+        assert r.qkv is (QKV.ROTARY_ONLY if kw.get("ignore_kvcache") else QKV.ROTARY_THEN_STORE)
+        assert r.piggyback == (kw.get("prefill", False) and kw["m"] > 0)
+    assert torch.cuda.is_initialized() == device_was_up
