@@ -15,7 +15,7 @@ struct Vec4 {
 };
 
 // Prefill: a row moves its running maximum only when a tile raised it by more than this (base-2 exponent units), so
-// p <= 2^kLazyMax = 16 (see the softmax step of prefill_attn.hip)
+// p <= 2^kLazyMax = 16 (see the softmax step of prefill_tile.h)
 constexpr float kLazyMax = 4.0f;
 
 __device__ __forceinline__ float16_t mfma32(vec8_t<f16> a, vec8_t<f16> b, float16_t c) {

@@ -6,28 +6,22 @@
 // Attention runs over the FRESH q/k/v projections; the paged pool is not read (no chunked prefill
 // in the reference). MFMA-bound: 4 * sum_s(len_s^2) * D * H / 2 flop per layer.
 //
-// Structure (wave64 / 32x32x16 MFMA native, not a warp-tiled CUDA port):
-//   * workgroup = 4 waves = one 128-row Q block of one (sequence, q-head); wave w owns 32 q-rows;
-//     K/V are walked in 64-key tiles staged through LDS (K rows padded to D+8, V rows to D+32
-//     elements: both fragment reads below are bank-conflict free);
-//   * S^T = K.Q^T ("swapped" product): A = K rows (ds_read_b128), B = Q^T held in registers for the
-//     whole kernel. In the 32x32 C layout lane (l%32) then owns ONE q-row, so the online-softmax
-//     max/sum are in-lane reductions plus a single lane^32 exchange;
-//   * O^T = V^T.P^T: A = V^T fragments fetched with the gfx950 LDS transpose read
-//     (ds_read_b64_tr_b16) from the row-major V tile, B = P^T taken straight from the S^T
-//     accumulator registers (the k-order of the product is permuted identically on both operands,
-//     so no cross-lane shuffle is needed); the per-row rescale factor is lane-local for O^T too;
-//   * the next K/V tile is fetched from HBM/L2 into registers while the current one is consumed
-//     and written to LDS after the barrier (issue-early / write-late staging);
-//   * epilogue: the wave's 32 x D output tile goes through LDS (the dead K/V tiles) and is stored as whole 256-byte rows,
-//     16 bytes per lane (r04; r01-r03 stored 8-byte pieces of 32 rows a token pitch apart per instruction);
-//   * 1-D grid decoded XCD-aware: all Q blocks and the G q-heads of one (sequence, kv-head) land on
-//     one XCD so their shared K/V stays in that XCD's L2; long (late) Q blocks are issued first.
+// The arithmetic of a 64-key tile, the epilogue and the grid decode are prefill_tile.h's, shared with the paged kernel
+// (wave64 / 32x32x16 MFMA native: S^T = K.Q^T with Q^T in registers, so lane l%32 owns ONE q-row; O^T = V^T.P^T with V^T by
+// the LDS transpose read and P^T straight from the S^T accumulators). The two kernels here are two ways of getting the
+// FRESH K/V tiles into LDS, and each hands the tile body its two fragment readers:
+//   * prefill_attn_kernel<T, D> (head sizes 32 / 64, and 128 behind SWL_PREFILL_ATTN=v1): workgroup = 4 waves = one
+//     128-row Q block of one (sequence, q-head). Register staging: the next tile is fetched from HBM/L2 into registers
+//     while the current one is consumed and written to LDS after the barrier (issue-early / write-late), two barriers per
+//     tile; row-major tiles, K rows padded to D+8 and V rows to D+32 elements (both fragment reads bank-conflict free);
+//     s_setprio around the MFMA blocks; Q^T fragments loaded directly.
+//   * prefill_attn_dma_kernel<T> (head size 128): LDS-DMA staging into two swizzled buffers, one barrier per tile, `hpw`
+//     q-heads of a kv-head per workgroup, Q^T as full lines through LDS — see the comment above it.
 // Numerics as the reference: fp32 scores * (scale*log2e), exp2, P rounded to the storage dtype for
 // the PV product, fp32 accumulators, one rounding at the store (prefill_attn.py:62-71,100).
 #include <stdlib.h>
 
-#include "attn_mfma.h"
+#include "prefill_tile.h"
 
 namespace swl {
 
@@ -43,9 +37,6 @@ struct PrefillParams {
     int64_t q_tok_stride, k_tok_stride, v_tok_stride, o_tok_stride;
 };
 
-constexpr int kBQ = 128; // q rows per workgroup
-constexpr int kBK = 64;  // keys per LDS tile
-
 template <typename T, int D>
 __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(PrefillParams p) {
     constexpr int KRS = D + 8;   // K row pitch (elements): 16 consecutive rows hit 16 distinct 16-B slots
@@ -59,24 +50,13 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(PrefillParams p) {
     T *const Ks = smem;
     T *const Vs = smem + kBK * KRS;
 
-    // ---- XCD-aware decode of the 1-D grid ------------------------------------------------------
-    const int G = p.H / p.KVH;
-    const int per_unit = G * p.num_q_blocks;
-    const int id = blockIdx.x;
-    const int xcd = id & 7;
-    const int j = id >> 3;
-    const int unit = xcd + 8 * (j / per_unit);
-    if (unit >= p.num_seqs * p.KVH) return;
-    const int inner = j % per_unit;
-    const int g = inner % G;
-    const int qb = p.num_q_blocks - 1 - inner / G; // longest rows first
-    const int seq = unit / p.KVH;
-    const int kvh = unit % p.KVH;
-    const int head = kvh * G + g;
-
-    const int start = p.cu_seqlens[seq];
-    const int len = p.cu_seqlens[seq + 1] - start;
-    const int q0 = qb * kBQ;
+    const PrefillGrid u = PrefillGrid::decode(blockIdx.x, p.num_seqs, p.H, p.KVH, p.num_q_blocks, 1);
+    if (!u.valid) return;
+    const int kvh = u.kvh;
+    const int head = kvh * (p.H / p.KVH) + u.hgroup;
+    const int start = p.cu_seqlens[u.seq];
+    const int len = p.cu_seqlens[u.seq + 1] - start;
+    const int q0 = u.qb * kBQ;
     if (q0 >= len) return;
 
     const int tid = threadIdx.x;
@@ -92,19 +72,8 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(PrefillParams p) {
     const T *kg = static_cast<const T *>(p.k) + static_cast<int64_t>(kvh) * D;
     const T *vg = static_cast<const T *>(p.v) + static_cast<int64_t>(kvh) * D;
 
-    // ---- Q^T B-fragments: lane holds Q[qrow][kk*16 + hf*8 .. +8] ---------------------------------
     vec8_t<T> qf[KSTEPS];
-    {
-        const bool ok = qrow < len;
-        const T *qp = qg + (static_cast<int64_t>(start) + (ok ? qrow : 0)) * p.q_tok_stride +
-                      static_cast<int64_t>(head) * D + hf * 8;
-#pragma unroll
-        for (int kk = 0; kk < KSTEPS; ++kk) {
-            vec8_t<T> t = load8(qp + kk * 16);
-            if (!ok) t = vec8_t<T>{};
-            qf[kk] = t;
-        }
-    }
+    prefill_load_q<T, D>(qf, qg, start, head, p.q_tok_stride, qrow, len, hf);
 
     float16_t ot[DT];
 #pragma unroll
@@ -179,135 +148,29 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_kernel(PrefillParams p) {
         if (tile + 1 < ntiles) fetch_tile(key0 + kBK); // in flight during the MFMAs below
 
         if (key0 > q0w + 31) continue; // whole tile above this wave's diagonal
-
-        // ---- S^T = K . Q^T  (two 32-key sub-tiles) ------------------------------------------------
-        float16_t st[2];
-        __builtin_amdgcn_s_setprio(1); // favour the wave that is feeding the matrix pipe (two waves per SIMD)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            st[t] = float16_t{};
-#pragma unroll
-            for (int kk = 0; kk < KSTEPS; ++kk) {
-                const vec8_t<T> kf =
-                    *reinterpret_cast<const vec8_t<T> *>(&Ks[k_frag_off + t * 32 * KRS + kk * 16]);
-                st[t] = mfma32(kf, qf[kk], st[t]);
-            }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        // S^T is read by VALU next, behind the diagonal-tile branch (swl_common.h)
-        mfma_results_tie(st[0]);
-        mfma_results_ready<8>(st[1]);
-        // causal mask on the diagonal tiles (keys beyond len are > every valid q row as well)
-        if (key0 + kBK - 1 > q0w) {
-            const int dmask = qrow - key0 - 4 * hf;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    // key > qrow with key = key0 + 32 t + (r & 3) + 8 (r >> 2) + 4 hf: a compile-time constant against ONE
-                    // per-lane value (one compare + one select per element; r01-r06a rebuilt the key first: three)
-                    if ((r & 3) + 8 * (r >> 2) + t * 32 > dmask) st[t][r] = kNegBig;
-                }
-        }
-        // ---- online softmax: this lane owns q row l32, keys split with lane^32 ---------------------
-        float mx = st[0][0];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[t][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        // lazy running maximum (r06b): a row moves its maximum only when the tile raised it by more than kLazyMax (base-2
-        // exponent units), so p stays <= 2^kLazyMax instead of <= 1 — 16-bit floats round p to the same RELATIVE precision at
-        // either scale, l and O accumulate in fp32 — and alpha is exactly 1 for that row: the 64-multiply rescale of O below
-        // then fires on the first tile or two of a row block instead of on most tiles (any of a wave's 32 rows setting a
-        // record). Decided per ROW, so a row's arithmetic still depends on its own scores only (the causality test holds
-        // bit for bit).
-        const float m_cand = fmaxf(m_run, mx * c);
-        const float m_new = m_cand - m_run > kLazyMax ? m_cand : m_run;
-        const float alpha = fast_exp2(m_run - m_new);
-        m_run = m_new;
-        float psum = 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pv = fast_exp2(fmaf(st[t][r], c, -m_new));
-                st[t][r] = pv;
-                psum += pv;
-            }
-        l_run = fmaf(l_run, alpha, psum);
-        // rescale O only when some row of this wave actually raised its max (alpha == 1 otherwise:
-        // after the first tiles of a sequence that is the common case) — a wave-uniform branch that
-        // removes 16*DT multiplies per lane per tile
-        if (!__all(alpha == 1.0f)) {
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
-        }
-
-        // ---- O^T += V^T . P^T ------------------------------------------------------------------------
-        __builtin_amdgcn_s_setprio(1);
-        // k-step (t, ks): this lane's 8 k-slots are keys t*32 + 16*ks + 4*hf + {0..3} and + 8 + {0..3}
-        // == accumulator registers 8*ks .. 8*ks+7 of st[t] — identical order on both operands.
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                vec8_t<T> pb;
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) pb[jj] = to_t<T>(st[t][8 * ks + jj]);
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt) {
-                    const T *vp = &Vs[v_frag_off + (t * 32 + 16 * ks) * VRS + dt * 32];
-                    const short4_t lo = lds_tr_read(vp);
-                    const short4_t hi = lds_tr_read(vp + 8 * VRS);
-                    typedef short short8_t __attribute__((ext_vector_type(8)));
-                    const short8_t both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    const vec8_t<T> vf = __builtin_bit_cast(vec8_t<T>, both);
-                    ot[dt] = mfma32(vf, pb, ot[dt]);
-                }
-            }
-        __builtin_amdgcn_s_setprio(0);
+        prefill_tile<T, D, true>(
+            qf, ot, m_run, l_run, c, qrow - key0 - 4 * hf, key0 + kBK - 1 > q0w,
+            [&](int t, int kk) { return *reinterpret_cast<const vec8_t<T> *>(&Ks[k_frag_off + t * 32 * KRS + kk * 16]); },
+            [&](int t, int ks, int dt, int half) {
+                return lds_tr_read(&Vs[v_frag_off + (t * 32 + 16 * ks + 8 * half) * VRS + dt * 32]);
+            });
     }
 
-    // ---- epilogue: O[qrow][d] = O^T[d][qrow] / l ---------------------------------------------------
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) mfma_results_tie(ot[dt]);
-    mfma_results_ready<8>(ot[DT - 1]);
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-    // O[qrow][d] = O^T[d][qrow] / l, written as WHOLE ROWS: a lane holds 4 consecutive d of ONE row per register quad, so a
-    // direct store instruction touches 32 rows a token pitch apart with 2 x 8 bytes each — 16 such instructions per lane,
-    // the store-issue-bound tail the in-box guide prices at ~4 us per workgroup (T21). The wave's 32 x D tile goes through
-    // LDS instead (the K/V tiles are dead: one barrier, the waves leave the loop together) and comes back row-major,
-    // 16 bytes per lane, 16 lanes = one 256-byte row: 8 full-line stores per lane at D = 128.
-    constexpr int ORS = D + 8;                       // O row pitch in LDS (elements)
-    static_assert(4 * 32 * ORS <= kBK * KRS + kBK * VRS, "the four waves' O tiles must fit the K/V tiles' LDS");
+    static_assert(4 * 32 * (D + 8) <= kBK * KRS + kBK * VRS, "the four waves' O tiles must fit the K/V tiles' LDS");
     __syncthreads();                                 // every wave is done with the last K/V tile
-    T *ow = smem + wave * 32 * ORS;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-            typedef T vec4 __attribute__((ext_vector_type(4)));
-            vec4 ov;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = to_t<T>(ot[dt][4 * r4 + e] * inv);
-            *reinterpret_cast<vec4 *>(ow + l32 * ORS + dt * 32 + 8 * r4 + 4 * hf) = ov;
-        }
-    // (wave-private tile: LDS operations of one wave complete in order, no barrier needed)
-    constexpr int RPI = 64 / CPR;                    // rows per store instruction
     T *obase = static_cast<T *>(p.o) + static_cast<int64_t>(start) * p.o_tok_stride + static_cast<int64_t>(head) * D;
-#pragma unroll
-    for (int i = 0; i < 32 / RPI; ++i) {
-        const int row = i * RPI + lane / CPR, ch = lane % CPR;
-        const vec8_t<T> v = *reinterpret_cast<const vec8_t<T> *>(ow + row * ORS + ch * 8);
-        if (q0w + row < len)
-            store8(obase + static_cast<int64_t>(q0w + row) * p.o_tok_stride + ch * 8, v);
-    }
+    prefill_store_rows<T, D, false>(ot, l_run, 1.0f, smem + wave * 32 * (D + 8), obase, p.o_tok_stride, q0w, len, lane, l32, hf);
 }
 
+// Four 1 KiB pieces of a tile image: global `base` (wave-uniform) + per-lane byte offset off[jj] -> LDS lds + 1024 jj (M0)
+__device__ __forceinline__ void dma_4_pieces(const unsigned (&off)[4], const char *base, unsigned lds) {
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(off[jj]), "s"(base), "s"(lds + jj * 1024) : "memory");
+    }
+}
 
 // ---- r06: LDS-DMA staged variant (head_dim 128) -----------------------------------------------------------------------------
 // Same arithmetic, same fragment order, same bits as prefill_attn_kernel above; what changes is how K/V tiles reach LDS and
@@ -337,29 +200,20 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_dma_kernel(PrefillParams 
     // rows; MHA: one head x 128 rows as before; four heads x 32 rows is the other legal value). Heads of one kv-head read the
     // same K/V tiles and have the same causal extent: fewer waves idle through the last tiles of their workgroup (128-row
     // blocks: 2 of every 8i + 8 wave-tile slots) and the per-tile barrier joins waves that did more nearly the same work.
-    const int G = p.H / p.KVH;
-    const int hpw = p.hpw, hgroups = G / hpw;
+    const int hpw = p.hpw;
     const int rows_wg = (4 / hpw) * 32;
-    const int per_unit = hgroups * p.num_q_blocks;
-    const int id = blockIdx.x;
-    const int xcd = id & 7;
-    const int j = id >> 3;
-    const int unit = xcd + 8 * (j / per_unit);
-    if (unit >= p.num_seqs * p.KVH) return;
-    const int inner = j % per_unit;
-    const int qb = p.num_q_blocks - 1 - inner / hgroups; // longest rows first
-    const int seq = unit / p.KVH;
-    const int kvh = unit % p.KVH;
-
-    const int start = p.cu_seqlens[seq];
-    const int len = p.cu_seqlens[seq + 1] - start;
-    const int q0 = qb * rows_wg;
+    const PrefillGrid u = PrefillGrid::decode(blockIdx.x, p.num_seqs, p.H, p.KVH, p.num_q_blocks, hpw);
+    if (!u.valid) return;
+    const int kvh = u.kvh;
+    const int start = p.cu_seqlens[u.seq];
+    const int len = p.cu_seqlens[u.seq + 1] - start;
+    const int q0 = u.qb * rows_wg;
     if (q0 >= len) return;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int head = kvh * G + (inner % hgroups) * hpw + wave % hpw;
+    const int head = kvh * (p.H / p.KVH) + u.hgroup * hpw + wave % hpw;
     const int l32 = lane & 31;
     const int hf = lane >> 5;
     const int q0w = q0 + (wave / hpw) * 32;
@@ -401,18 +255,8 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_dma_kernel(PrefillParams 
         const char *kb = kbase + static_cast<int64_t>(tile) * kBK * kstride_b;     // (wave-uniform: SGPR pair)
         const char *vb = vbase + static_cast<int64_t>(tile) * kBK * vstride_b;
         const unsigned ldsk = lds0 + static_cast<unsigned>(buf) * 2 * TILEB + static_cast<unsigned>(wave) * 4096;
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(koff[jj]), "s"(kb), "s"(ldsk + jj * 1024) : "memory");
-        }
-#pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "v"(voff[jj]), "s"(vb), "s"(ldsk + TILEB + jj * 1024) : "memory");
-        }
+        dma_4_pieces(koff, kb, ldsk);
+        dma_4_pieces(voff, vb, ldsk + TILEB);
     };
 
     const int kv_end = min(len, q0 + rows_wg);
@@ -475,118 +319,19 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_dma_kernel(PrefillParams 
         }
         if (key0 > q0w + 31) continue; // whole tile above this wave's diagonal
         const char *bufp = smem + buf * 2 * TILEB;
-
-        // (no s_setprio around the MFMA blocks here: with two free-running workgroups per CU the per-block priority flips
-        // of the r01-r06a kernels cost 1.4-1.7 % — profiles/r06b_prefill_attn_setprio_ab.jsonl; the guide's T5 says as much)
-        float16_t st[2];
-        
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            st[t] = float16_t{};
-#pragma unroll
-            for (int kk = 0; kk < KSTEPS; ++kk) {
-                const vec8_t<T> kf = *reinterpret_cast<const vec8_t<T> *>(bufp + kfo[kk] + t * 32 * ROWB);
-                st[t] = mfma32(kf, qf[kk], st[t]);
-            }
-        }
-        
-        mfma_results_tie(st[0]);
-        mfma_results_ready<8>(st[1]);
-        if (key0 + kBK - 1 > q0w) {
-            const int dmask = qrow - key0 - 4 * hf;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    // key > qrow with key = key0 + 32 t + (r & 3) + 8 (r >> 2) + 4 hf: a compile-time constant against ONE
-                    // per-lane value (one compare + one select per element; r01-r06a rebuilt the key first: three)
-                    if ((r & 3) + 8 * (r >> 2) + t * 32 > dmask) st[t][r] = kNegBig;
-                }
-        }
-        float mx = st[0][0];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[t][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        // lazy running maximum (r06b): a row moves its maximum only when the tile raised it by more than kLazyMax (base-2
-        // exponent units), so p stays <= 2^kLazyMax instead of <= 1 — 16-bit floats round p to the same RELATIVE precision at
-        // either scale, l and O accumulate in fp32 — and alpha is exactly 1 for that row: the 64-multiply rescale of O below
-        // then fires on the first tile or two of a row block instead of on most tiles (any of a wave's 32 rows setting a
-        // record). Decided per ROW, so a row's arithmetic still depends on its own scores only (the causality test holds
-        // bit for bit).
-        const float m_cand = fmaxf(m_run, mx * c);
-        const float m_new = m_cand - m_run > kLazyMax ? m_cand : m_run;
-        const float alpha = fast_exp2(m_run - m_new);
-        m_run = m_new;
-        float psum = 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pv = fast_exp2(fmaf(st[t][r], c, -m_new));
-                st[t][r] = pv;
-                psum += pv;
-            }
-        l_run = fmaf(l_run, alpha, psum);
-        if (!__all(alpha == 1.0f)) {
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
-        }
-
-        
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                vec8_t<T> pb;
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) pb[jj] = to_t<T>(st[t][8 * ks + jj]);
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt) {
-                    const T *vp = reinterpret_cast<const T *>(bufp + vfo[dt] + (t * 32 + 16 * ks) * ROWB);
-                    const short4_t lo = lds_tr_read(vp);
-                    const short4_t hi = lds_tr_read(vp + 8 * D);
-                    typedef short short8_t __attribute__((ext_vector_type(8)));
-                    const short8_t both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    const vec8_t<T> vf = __builtin_bit_cast(vec8_t<T>, both);
-                    ot[dt] = mfma32(vf, pb, ot[dt]);
-                }
-            }
-        
+        prefill_tile<T, D, false>(
+            qf, ot, m_run, l_run, c, qrow - key0 - 4 * hf, key0 + kBK - 1 > q0w,
+            [&](int t, int kk) { return *reinterpret_cast<const vec8_t<T> *>(bufp + kfo[kk] + t * 32 * ROWB); },
+            [&](int t, int ks, int dt, int half) {
+                return lds_tr_read(reinterpret_cast<const T *>(bufp + vfo[dt] + (t * 32 + 16 * ks + 8 * half) * ROWB));
+            });
     }
 
-    // ---- epilogue: as prefill_attn_kernel (whole-row stores through LDS) ------------------------------------------------------
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) mfma_results_tie(ot[dt]);
-    mfma_results_ready<8>(ot[DT - 1]);
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;
-    constexpr int ORS = D + 8;
-    static_assert(4 * 32 * ORS * 2 <= 4 * TILEB, "the four waves' O tiles must fit the K/V buffers");
+    static_assert(4 * 32 * (D + 8) * 2 <= 4 * TILEB, "the four waves' O tiles must fit the K/V buffers");
     __syncthreads();                                 // every wave is done with the last K/V tile (no DMA is in flight)
-    T *ow = reinterpret_cast<T *>(smem) + wave * 32 * ORS;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-            typedef T vec4 __attribute__((ext_vector_type(4)));
-            vec4 ov;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) ov[e] = to_t<T>(ot[dt][4 * r4 + e] * inv);
-            *reinterpret_cast<vec4 *>(ow + l32 * ORS + dt * 32 + 8 * r4 + 4 * hf) = ov;
-        }
-    constexpr int CPR = D / 8, RPI = 64 / CPR;
     T *obase = static_cast<T *>(p.o) + static_cast<int64_t>(start) * p.o_tok_stride + static_cast<int64_t>(head) * D;
-#pragma unroll
-    for (int i = 0; i < 32 / RPI; ++i) {
-        const int row = i * RPI + lane / CPR, ch = lane % CPR;
-        const vec8_t<T> v = *reinterpret_cast<const vec8_t<T> *>(ow + row * ORS + ch * 8);
-        if (q0w + row < len)
-            store8(obase + static_cast<int64_t>(q0w + row) * p.o_tok_stride + ch * 8, v);
-    }
+    prefill_store_rows<T, D, false>(ot, l_run, 1.0f, reinterpret_cast<T *>(smem) + wave * 32 * (D + 8), obase,
+                                    p.o_tok_stride, q0w, len, lane, l32, hf);
 }
 
 } // namespace swl
@@ -627,12 +372,9 @@ extern "C" int swl_prefill_attn_varlen(void *o, const void *q, const void *k, co
     p.v_tok_stride = v_tok_stride;
     p.o_tok_stride = o_tok_stride;
     p.hpw = 1;
-    const int64_t units = static_cast<int64_t>(num_prefill_seqs) * num_kv_heads;
-    const int64_t units_padded = (units + 7) / 8 * 8;
     const int G = num_q_heads / num_kv_heads;
-    int64_t nblocks = units_padded * G * p.num_q_blocks;
-    if (nblocks > 0x7fffffffLL) return SWL_ERR_UNSUPPORTED;
-    dim3 grid(static_cast<unsigned>(nblocks));
+    dim3 grid;
+    if (!swl::prefill_grid_blocks(num_prefill_seqs, num_kv_heads, G, p.num_q_blocks, &grid)) return SWL_ERR_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
     // A/B switch for measurements: SWL_PREFILL_ATTN=v1 runs the register-staged kernel at head_dim 128 as well
     static const bool use_v1 = [] { const char *e = getenv("SWL_PREFILL_ATTN"); return e && e[0] == 'v' && e[1] == '1'; }();
@@ -648,9 +390,8 @@ extern "C" int swl_prefill_attn_varlen(void *o, const void *q, const void *k, co
             if (forced_hpw == 1 || forced_hpw == 2 || forced_hpw == 4) p.hpw = G % forced_hpw == 0 ? forced_hpw : p.hpw;
             const int rows_wg = (4 / p.hpw) * 32;
             p.num_q_blocks = (max_prefill_len + rows_wg - 1) / rows_wg;
-            nblocks = units_padded * (G / p.hpw) * p.num_q_blocks;
-            if (nblocks > 0x7fffffffLL) return SWL_ERR_UNSUPPORTED;
-            grid = dim3(static_cast<unsigned>(nblocks));
+            if (!swl::prefill_grid_blocks(num_prefill_seqs, num_kv_heads, G / p.hpw, p.num_q_blocks, &grid))
+                return SWL_ERR_UNSUPPORTED;
             hipLaunchKernelGGL((swl::prefill_attn_dma_kernel<T>), grid, dim3(256), 0, s, p);
         }
         else if (head_dim == 128)

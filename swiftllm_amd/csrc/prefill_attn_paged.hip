@@ -9,11 +9,11 @@
 // bit-exact, so the bits are those of the fresh projections. c is any value >= 0 (c = 0: a plain causal prefill);
 // n = 0 sequences launch workgroups that leave on their first branch.
 //
-// Structure = prefill_attn.hip (prefill_attn_kernel), same arithmetic, same fragment order, same error bounds:
-//   * workgroup = 4 waves = 128 chunk rows of one (sequence, q-head), wave w owns 32 rows; S^T = K.Q^T on 32x32x16 MFMA
-//     with Q^T in registers; O^T = V^T.P^T with V^T fetched by ds_read_b64_tr_b16; fp32 scores * (scale * log2 e), exp2,
-//     P rounded to the storage dtype, fp32 accumulators, the lazy running maximum (kLazyMax), one rounding at the store;
-//     O through LDS and out as whole rows; 1-D grid decoded XCD-aware, the q-blocks of a sequence longest first.
+// The grid decode, the Q^T load, the arithmetic of a 64-key tile and the epilogue are prefill_tile.h's, the body the
+// fresh-K/V kernels of prefill_attn.hip run: same arithmetic, same fragment order, same error bounds, and at c = 0 the same
+// bits by construction. Workgroup = 4 waves = 128 chunk rows of one (sequence, q-head); row-major K/V tiles at the pitches
+// of prefill_attn_kernel. What this kernel adds:
+//   * the mask compares ABSOLUTE positions (row c + i against key j);
 //   * keys are walked in 64-key tiles ALIGNED TO ABSOLUTE POSITION 0, so a tile is exactly four 16-token pool blocks.
 //     For one (block, layer, kv-head) the 16 x D slab is contiguous (4 KiB at D = 128): a staging pass reads one block
 //     id (at D = 128 the id is workgroup-uniform: a scalar load) and 16 bytes per lane from that slab. Block ids are
@@ -46,7 +46,7 @@
 // (which attends to its fresh 16-bit projections).
 #include <type_traits>
 
-#include "attn_mfma.h"
+#include "prefill_tile.h"
 #include "fp8_kv.h"
 
 namespace swl {
@@ -67,44 +67,29 @@ struct PagedPrefillParams {
     const float *kv_scales;     // FP8 pools: [2][L][KVH]; not read for 16-bit pools
 };
 
-constexpr int kPgBQ = 128;         // chunk rows per workgroup
-constexpr int kPgBK = 64;          // keys per LDS tile = four pool blocks
-
 template <typename T, int D, bool FP8>
 __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefillParams p) {
     constexpr int KRS = D + 8;   // K row pitch (elements): 16 consecutive rows hit 16 distinct 16-B slots
     constexpr int VRS = D + 32;  // V row pitch: 4 rows x two 16-col halves tile the 64 banks exactly
     constexpr int KSTEPS = D / 16;
     constexpr int DT = D / 32;
-    constexpr int CPR = D / 8;           // 16-byte chunks per row of T (epilogue)
     using Pool = std::conditional_t<FP8, uint8_t, T>;        // pool element
     using Raw = std::conditional_t<FP8, u32x4_t, vec8_t<T>>; // a lane's 16 bytes of a pool row
     constexpr int EPC = 16 / sizeof(Pool);   // pool elements per 16-byte chunk
     constexpr int SCPR = D / EPC;            // 16-byte chunks per pool row (staging)
-    constexpr int RPP = 256 / SCPR < kPgBK ? 256 / SCPR : kPgBK;   // rows staged per pass (see the header)
-    constexpr int NPASS = kPgBK / RPP;       // passes per tile
-    __shared__ __attribute__((aligned(16))) T smem[kPgBK * KRS + kPgBK * VRS];   // K tile, V tile; the O tiles of the epilogue
+    constexpr int RPP = 256 / SCPR < kBK ? 256 / SCPR : kBK;   // rows staged per pass (see the header)
+    constexpr int NPASS = kBK / RPP;       // passes per tile
+    __shared__ __attribute__((aligned(16))) T smem[kBK * KRS + kBK * VRS];   // K tile, V tile; the O tiles of the epilogue
     T *const Ks = smem;
-    T *const Vs = smem + kPgBK * KRS;
+    T *const Vs = smem + kBK * KRS;
 
-    // ---- XCD-aware decode of the 1-D grid (as prefill_attn_kernel) ---------------------------------
-    const int G = p.H / p.KVH;
-    const int per_unit = G * p.num_q_blocks;
-    const int id = blockIdx.x;
-    const int xcd = id & 7;
-    const int j = id >> 3;
-    const int unit = xcd + 8 * (j / per_unit);
-    if (unit >= p.num_seqs * p.KVH) return;
-    const int inner = j % per_unit;
-    const int g = inner % G;
-    const int qb = p.num_q_blocks - 1 - inner / G; // most tiles first
-    const int seq = unit / p.KVH;
-    const int kvh = unit % p.KVH;
-    const int head = kvh * G + g;
-
+    const PrefillGrid u = PrefillGrid::decode(blockIdx.x, p.num_seqs, p.H, p.KVH, p.num_q_blocks, 1);   // most tiles first
+    if (!u.valid) return;
+    const int seq = u.seq, kvh = u.kvh;
+    const int head = kvh * (p.H / p.KVH) + u.hgroup;
     const int start = p.cu_seqlens[seq];
     const int len = p.cu_seqlens[seq + 1] - start;      // new tokens (chunk rows)
-    const int q0 = qb * kPgBQ;
+    const int q0 = u.qb * kBQ;
     if (q0 >= len) return;
     const int ctx = p.ctx_lens[seq];
     const int total = ctx + len;                        // keys resident once the chunk is stored
@@ -130,19 +115,8 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
     const Pool *kc = static_cast<const Pool *>(p.k_cache);
     const Pool *vc = static_cast<const Pool *>(p.v_cache);
 
-    // ---- Q^T B-fragments: lane holds Q[qrow][kk*16 + hf*8 .. +8] ---------------------------------
     vec8_t<T> qf[KSTEPS];
-    {
-        const bool ok = qrow < len;
-        const T *qp = qg + (static_cast<int64_t>(start) + (ok ? qrow : 0)) * p.q_tok_stride +
-                      static_cast<int64_t>(head) * D + hf * 8;
-#pragma unroll
-        for (int kk = 0; kk < KSTEPS; ++kk) {
-            vec8_t<T> t = load8(qp + kk * 16);
-            if (!ok) t = vec8_t<T>{};
-            qf[kk] = t;
-        }
-    }
+    prefill_load_q<T, D>(qf, qg, start, head, p.q_tok_stride, qrow, len, hf);
 
     float16_t ot[DT];
 #pragma unroll
@@ -170,8 +144,8 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
         }
     };
     auto fetch_tile = [&](int tile) {
-        const int key0 = tile * kPgBK;
-        const bool whole = key0 + kPgBK <= total;        // (workgroup-uniform) every key of the tile is resident
+        const int key0 = tile * kBK;
+        const bool whole = key0 + kBK <= total;        // (workgroup-uniform) every key of the tile is resident
 #pragma unroll
         for (int ps = 0; ps < NPASS; ++ps) {
             const int r = srow + ps * RPP;
@@ -205,8 +179,8 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
         }
     };
 
-    const int kv_end = min(total, ctx + q0 + kPgBQ);     // keys this q-block can see
-    const int ntiles = (kv_end + kPgBK - 1) / kPgBK;
+    const int kv_end = min(total, ctx + q0 + kBQ);     // keys this q-block can see
+    const int ntiles = (kv_end + kBK - 1) / kBK;
 
     // per-lane LDS offsets of the fragment reads
     const int k_frag_off = l32 * KRS + hf * 8;                            // + t*32*KRS + kk*16
@@ -217,7 +191,7 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
     fetch_tile(0);
     if (ntiles > 1) load_ids(1);
     for (int tile = 0; tile < ntiles; ++tile) {
-        const int key0 = tile * kPgBK;
+        const int key0 = tile * kBK;
         __syncthreads(); // everyone finished reading the previous tile
         commit_tile();
         __syncthreads();
@@ -227,124 +201,19 @@ __global__ __launch_bounds__(256, 2) void prefill_attn_paged_kernel(PagedPrefill
         }
 
         if (key0 > qpos0w + 31) continue; // whole tile above this wave's diagonal
-
-        // ---- S^T = K . Q^T  (two 32-key sub-tiles) ------------------------------------------------
-        float16_t st[2];
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            st[t] = float16_t{};
-#pragma unroll
-            for (int kk = 0; kk < KSTEPS; ++kk) {
-                const vec8_t<T> kf =
-                    *reinterpret_cast<const vec8_t<T> *>(&Ks[k_frag_off + t * 32 * KRS + kk * 16]);
-                st[t] = mfma32(kf, qf[kk], st[t]);
-            }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        // S^T is read by VALU next, behind the diagonal-tile branch (swl_common.h)
-        mfma_results_tie(st[0]);
-        mfma_results_ready<8>(st[1]);
-        // causal mask on the diagonal tiles (keys >= c + n are > every valid row's position as well)
-        if (key0 + kPgBK - 1 > qpos0w) {
-            const int dmask = qpos - key0 - 4 * hf;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    // key > qpos with key = key0 + 32 t + (r & 3) + 8 (r >> 2) + 4 hf: a compile-time constant against ONE
-                    // per-lane value
-                    if ((r & 3) + 8 * (r >> 2) + t * 32 > dmask) st[t][r] = kNegBig;
-                }
-        }
-        // ---- online softmax: this lane owns chunk row l32, keys split with lane^32 -----------------
-        float mx = st[0][0];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[t][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        // lazy running maximum, decided per ROW (prefill_attn.hip): a row's arithmetic depends on its own scores only
-        const float m_cand = fmaxf(m_run, mx * c);
-        const float m_new = m_cand - m_run > kLazyMax ? m_cand : m_run;
-        const float alpha = fast_exp2(m_run - m_new);
-        m_run = m_new;
-        float psum = 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pv = fast_exp2(fmaf(st[t][r], c, -m_new));
-                st[t][r] = pv;
-                psum += pv;
-            }
-        l_run = fmaf(l_run, alpha, psum);
-        if (!__all(alpha == 1.0f)) {
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) ot[dt][r] *= alpha;
-        }
-
-        // ---- O^T += V^T . P^T ------------------------------------------------------------------------
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                vec8_t<T> pb;
-#pragma unroll
-                for (int jj = 0; jj < 8; ++jj) pb[jj] = to_t<T>(st[t][8 * ks + jj]);
-#pragma unroll
-                for (int dt = 0; dt < DT; ++dt) {
-                    const T *vp = &Vs[v_frag_off + (t * 32 + 16 * ks) * VRS + dt * 32];
-                    const short4_t lo = lds_tr_read(vp);
-                    const short4_t hi = lds_tr_read(vp + 8 * VRS);
-                    typedef short short8_t __attribute__((ext_vector_type(8)));
-                    const short8_t both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    const vec8_t<T> vf = __builtin_bit_cast(vec8_t<T>, both);
-                    ot[dt] = mfma32(vf, pb, ot[dt]);
-                }
-            }
-        __builtin_amdgcn_s_setprio(0);
+        // the mask compares ABSOLUTE positions (keys >= c + n are > every valid row's position as well)
+        prefill_tile<T, D, true>(
+            qf, ot, m_run, l_run, c, qpos - key0 - 4 * hf, key0 + kBK - 1 > qpos0w,
+            [&](int t, int kk) { return *reinterpret_cast<const vec8_t<T> *>(&Ks[k_frag_off + t * 32 * KRS + kk * 16]); },
+            [&](int t, int ks, int dt, int half) {
+                return lds_tr_read(&Vs[v_frag_off + (t * 32 + 16 * ks + 8 * half) * VRS + dt * 32]);
+            });
     }
 
-    // ---- epilogue: O[qrow][d] = O^T[d][qrow] / l, whole rows through LDS (prefill_attn_kernel) ------
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) mfma_results_tie(ot[dt]);
-    mfma_results_ready<8>(ot[DT - 1]);
-    const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-    const float inv = 1.0f / l_tot;                  // (FP8: then v_scale, in fp32, before the one rounding)
-    constexpr int ORS = D + 8;                       // O row pitch in LDS (elements)
-    static_assert(4 * 32 * ORS <= kPgBK * KRS + kPgBK * VRS, "the four waves' O tiles must fit the K/V tiles' LDS");
+    static_assert(4 * 32 * (D + 8) <= kBK * KRS + kBK * VRS, "the four waves' O tiles must fit the K/V tiles' LDS");
     __syncthreads();                                 // every wave is done with the last K/V tile
-    T *ow = smem + wave * 32 * ORS;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-            typedef T vec4 __attribute__((ext_vector_type(4)));
-            vec4 ov;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                // (float16, 16-bit pools: product and rounding become one v_fma_mixlo/hi_f16, the exact product rounded
-                // once; the FP8 form rounds it to fp32 first: 1 ulp apart on rare ties — DESIGN.md section 3)
-                float x = ot[dt][4 * r4 + e] * inv;
-                if constexpr (FP8) x *= v_scale;
-                ov[e] = to_t<T>(x);
-            }
-            *reinterpret_cast<vec4 *>(ow + l32 * ORS + dt * 32 + 8 * r4 + 4 * hf) = ov;
-        }
-    // (wave-private tile: LDS operations of one wave complete in order, no barrier needed)
-    constexpr int RPI = 64 / CPR;                    // rows per store instruction
     T *obase = static_cast<T *>(p.o) + static_cast<int64_t>(start) * p.o_tok_stride + static_cast<int64_t>(head) * D;
-#pragma unroll
-    for (int i = 0; i < 32 / RPI; ++i) {
-        const int row = i * RPI + lane / CPR, ch = lane % CPR;
-        const vec8_t<T> v = *reinterpret_cast<const vec8_t<T> *>(ow + row * ORS + ch * 8);
-        if (q0w + row < len)
-            store8(obase + static_cast<int64_t>(q0w + row) * p.o_tok_stride + ch * 8, v);
-    }
+    prefill_store_rows<T, D, FP8>(ot, l_run, v_scale, smem + wave * 32 * (D + 8), obase, p.o_tok_stride, q0w, len, lane, l32, hf);
 }
 
 } // namespace swl
@@ -389,7 +258,7 @@ static int launch_prefill_attn_paged(void *o, const void *q, const void *k_cache
     p.num_seqs = num_prefill_seqs;
     p.H = num_q_heads;
     p.KVH = num_kv_heads;
-    p.num_q_blocks = (max_new_len + swl::kPgBQ - 1) / swl::kPgBQ;
+    p.num_q_blocks = (max_new_len + swl::kBQ - 1) / swl::kBQ;
     p.num_layers = num_layers;
     p.cur_layer = cur_layer;
     p.max_blocks_per_seq = max_blocks_per_seq;
@@ -397,12 +266,9 @@ static int launch_prefill_attn_paged(void *o, const void *q, const void *k_cache
     p.q_tok_stride = q_tok_stride;
     p.o_tok_stride = o_tok_stride;
     p.kv_scales = kv_scales;
-    const int64_t units = static_cast<int64_t>(num_prefill_seqs) * num_kv_heads;
-    const int64_t units_padded = (units + 7) / 8 * 8;
-    const int G = num_q_heads / num_kv_heads;
-    const int64_t nblocks = units_padded * G * p.num_q_blocks;
-    if (nblocks > 0x7fffffffLL) return SWL_ERR_UNSUPPORTED;
-    const dim3 grid(static_cast<unsigned>(nblocks));
+    dim3 grid;
+    if (!swl::prefill_grid_blocks(num_prefill_seqs, num_kv_heads, num_q_heads / num_kv_heads, p.num_q_blocks, &grid))
+        return SWL_ERR_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
     SWL_DISPATCH_DTYPE(dtype, T, {
         if (head_dim == 128)
