@@ -23,7 +23,6 @@ SOURCES = [
     "paged_attn_verify.hip",
     "prefill_attn.hip",
     "prefill_attn_paged.hip",
-    "kvcache_fp8.hip",
     "paged_attn_fp8.hip",
     "block_table.hip",
     "swap_blocks.hip",
@@ -37,7 +36,7 @@ SOURCES = [
     "lora.hip",
     "decode_engine.hip",
 ]
-HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "decode_attn.h", "prefill_tile.h", "fp8_kv.h", "gemm_host.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
+HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "decode_attn.h", "prefill_tile.h", "fp8_kv.h", "kv_store.h", "gemm_host.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
 LIB = os.path.join(HERE, "libswiftllm_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 ARCH = "gfx950"

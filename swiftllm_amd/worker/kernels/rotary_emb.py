@@ -3,6 +3,18 @@ import torch
 
 from swiftllm_amd import _hip
 from ._layout import token_stride
+from .kvcache_mgmt import _decode_tables, _geometry, _prefill_ctx, _prefill_tables, _rows
+
+
+def _rope(st, pos_idx):
+    """the rope tables and the row of each token in them"""
+    return _hip.ptr(st.position_cos), _hip.ptr(st.position_sin), _hip.ptr(pos_idx)
+
+
+def _decode_geometry(cur_layer, model_config, engine_config, block_table, q_heads, kv_heads, head_dim):
+    """H KVH D cur_layer L bs mbps: the order of the two fused decode entries"""
+    return (q_heads, kv_heads, head_dim, cur_layer, model_config.num_layers, engine_config.block_size,
+            block_table.shape[1])
 
 
 def rotary_embedding_inplace(q: torch.Tensor, k: torch.Tensor, infer_state):
@@ -44,13 +56,10 @@ def rotary_embedding_and_store_kvcache_decode(q: torch.Tensor, k: torch.Tensor, 
         return
     assert k_cache.is_contiguous() and v_cache.is_contiguous() and block_table.is_contiguous()
     _hip.call("swl_rotary_store_kv_decode", _hip.ptr(q), _hip.ptr(k), _hip.ptr(v),
-              _hip.ptr(infer_state.position_cos), _hip.ptr(infer_state.position_sin),
-              _hip.ptr(infer_state.position_indices), _hip.ptr(k_cache), _hip.ptr(v_cache),
-              _hip.ptr(block_table), _hip.ptr(infer_state.seq_ids),
-              _hip.ptr(infer_state.decoding_seq_lens), nd, q.shape[1], k.shape[1], q.shape[2],
-              cur_layer, model_config.num_layers, engine_config.block_size, block_table.shape[1],
-              token_stride(q, "q"), token_stride(k, "k"), token_stride(v, "v"),
-              _hip.dtype_code(q.dtype), _hip.stream())
+              *_rope(infer_state, infer_state.position_indices), _hip.ptr(k_cache), _hip.ptr(v_cache),
+              *_decode_tables(block_table, infer_state),
+              *_decode_geometry(cur_layer, model_config, engine_config, block_table, q.shape[1], k.shape[1], q.shape[2]),
+              *_rows(q=q, k=k, v=v))
 
 
 def rotary_embedding_and_store_kvcache_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
@@ -66,33 +75,20 @@ def rotary_embedding_and_store_kvcache_prefill(q: torch.Tensor, k: torch.Tensor,
     st = infer_state
     assert st.num_prefill_seqs > 0 and st.position_indices is not None
     assert k_cache.is_contiguous() and v_cache.is_contiguous() and block_table.is_contiguous()
-    qs, ks, vs = token_stride(q, "q"), token_stride(k, "k"), token_stride(v, "v")
-    code, stream = _hip.dtype_code(q.dtype), _hip.stream()
-    ctx = getattr(st, "prefill_ctx_lens", None)
-    if ctx is not None:
-        # chunked prefill: the chunk of sequence s starts at logical position ctx[s] (csrc/kvcache.hip: the _at kernels)
-        assert ctx.dtype == torch.int32 and ctx.is_contiguous() and ctx.numel() == st.num_prefill_seqs
-        _hip.call("swl_rotary_store_kv_prefill_at", _hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(st.position_cos),
-                  _hip.ptr(st.position_sin), _hip.ptr(st.position_indices), _hip.ptr(k_cache), _hip.ptr(v_cache),
-                  _hip.ptr(block_table), _hip.ptr(st.seq_ids), _hip.ptr(st.prefill_seq_start_locs),
-                  _hip.ptr(st.prefill_seq_lens), _hip.ptr(ctx), st.num_prefill_seqs, st.max_prefill_len, cur_layer,
-                  model_config.num_layers, q.shape[1], k.shape[1], engine_config.block_size, q.shape[2],
-                  block_table.shape[1], qs, ks, vs, code, stream)
-    else:
-        _hip.call("swl_rotary_store_kv_prefill", _hip.ptr(q), _hip.ptr(k), _hip.ptr(v), _hip.ptr(st.position_cos),
-                  _hip.ptr(st.position_sin), _hip.ptr(st.position_indices), _hip.ptr(k_cache), _hip.ptr(v_cache),
-                  _hip.ptr(block_table), _hip.ptr(st.seq_ids), _hip.ptr(st.prefill_seq_start_locs),
-                  _hip.ptr(st.prefill_seq_lens), st.num_prefill_seqs, st.max_prefill_len, cur_layer,
-                  model_config.num_layers, q.shape[1], k.shape[1], engine_config.block_size, q.shape[2],
-                  block_table.shape[1], qs, ks, vs, code, stream)
-    nd = st.num_decoding_seqs
-    if nd > 0:
+    rows = _rows(q=q, k=k, v=v)
+    pools = _hip.ptr(k_cache), _hip.ptr(v_cache)
+    # chunked prefill: the chunk of sequence s starts at logical position ctx[s] (csrc/kv_store.h: the prefill block span)
+    ctx = _prefill_ctx(st)
+    entry, ctx_arg = ("swl_rotary_store_kv_prefill", ()) if ctx is None else ("swl_rotary_store_kv_prefill_at", (ctx,))
+    _hip.call(entry, _hip.ptr(q), _hip.ptr(k), _hip.ptr(v), *_rope(st, st.position_indices), *pools,
+              *_prefill_tables(block_table, st, *ctx_arg),
+              *_geometry(cur_layer, model_config, engine_config, block_table, k.shape[1], q.shape[2], q.shape[1]), *rows)
+    if st.num_decoding_seqs > 0:
         p = st.num_prefill_tokens
         _hip.call("swl_rotary_store_kv_decode", _hip.ptr(q[p:]), _hip.ptr(k[p:]), _hip.ptr(v[p:]),
-                  _hip.ptr(st.position_cos), _hip.ptr(st.position_sin), _hip.ptr(st.position_indices[p:]),
-                  _hip.ptr(k_cache), _hip.ptr(v_cache), _hip.ptr(block_table), _hip.ptr(st.seq_ids[st.num_prefill_seqs:]),
-                  _hip.ptr(st.decoding_seq_lens), nd, q.shape[1], k.shape[1], q.shape[2], cur_layer,
-                  model_config.num_layers, engine_config.block_size, block_table.shape[1], qs, ks, vs, code, stream)
+                  *_rope(st, st.position_indices[p:]), *pools, *_decode_tables(block_table, st),
+                  *_decode_geometry(cur_layer, model_config, engine_config, block_table, q.shape[1], k.shape[1], q.shape[2]),
+                  *rows)
 
 
 def rotary_embedding_and_store_kvcache_decode_from_splitk(partials, k_cache: torch.Tensor,
@@ -112,10 +108,8 @@ def rotary_embedding_and_store_kvcache_decode_from_splitk(partials, k_cache: tor
     k = qkv[:, h * d:(h + kvh) * d].view(nd, kvh, d)
     v = qkv[:, (h + kvh) * d:].view(nd, kvh, d)
     _hip.call("swl_splitk_rotary_store_kv_decode", _hip.ptr(q), _hip.ptr(k), _hip.ptr(v),
-              _hip.ptr(partials.slabs), partials.k_splits, _hip.ptr(infer_state.position_cos),
-              _hip.ptr(infer_state.position_sin), _hip.ptr(infer_state.position_indices),
-              _hip.ptr(k_cache), _hip.ptr(v_cache), _hip.ptr(block_table), _hip.ptr(infer_state.seq_ids),
-              _hip.ptr(infer_state.decoding_seq_lens), nd, h, kvh, d, cur_layer, model_config.num_layers,
-              engine_config.block_size, block_table.shape[1], n, n, n, _hip.dtype_code(partials.dtype),
-              _hip.stream())
+              _hip.ptr(partials.slabs), partials.k_splits, *_rope(infer_state, infer_state.position_indices),
+              _hip.ptr(k_cache), _hip.ptr(v_cache), *_decode_tables(block_table, infer_state),
+              *_decode_geometry(cur_layer, model_config, engine_config, block_table, h, kvh, d), n, n, n,
+              _hip.dtype_code(partials.dtype), _hip.stream())
     return q, k, v
