@@ -383,6 +383,15 @@ int swl_swap_blocks(const int64_t *src_ids, const int64_t *dst_ids, int64_t num_
                     int32_t is_swap_in, void *k_cache, void *v_cache, void *k_swap, void *v_swap,
                     int64_t block_bytes, swl_stream_t stream);
 
+/* ---- KV block copy inside the GPU pools (prefix caching by block copy; csrc/kv_copy.hip; no reference counterpart) ----
+ * ONE launch copies block src_ids[i] -> block dst_ids[i], in k_cache and in v_cache, for i in [0, n). src_ids / dst_ids
+ * are DEVICE arrays; no host sync, no runtime call per block. Bytes are copied (block_bytes = bytes of one block in one
+ * pool, a multiple of 16; pool bases 16-byte aligned), so 16-bit and FP8 pools take the same entry. A pair with
+ * src == dst, or with an id outside [0, num_blocks), is skipped — never dereferenced. The distinct destinations must be
+ * disjoint from the sources (the caller's guarantee). n == 0: SWL_OK, nothing launched. */
+int swl_kv_copy_blocks(void *k_cache, void *v_cache, const int32_t *src_ids, const int32_t *dst_ids, int64_t n,
+                       int64_t block_bytes, int64_t num_blocks, swl_stream_t stream);
+
 /* ---- Fused hot-path helpers (no reference twin; result-identical compositions) ------------------
  * Decode-only: rotary on q,k followed by the decode KV store of the rotated k and of v, in one launch
  * (= swl_rotary(pos_idx) + swl_store_kv_decode). */

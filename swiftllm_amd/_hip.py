@@ -142,6 +142,9 @@ _SPECIAL = {
     "swl_lora_k_splits": ([_I32], _I32),
     "swl_lora_shrink": ([_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _P], _I32),
     "swl_lora_expand": ([_P, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _P], _I32),
+    # KV block copy inside the GPU pools (csrc/kv_copy.hip; prefix caching): an "int rc = f(...)" entry too, registered
+    # here for the same reason (its own contract: tests/test_gpu_kv_copy.py).
+    "swl_kv_copy_blocks": ([_P, _P, _P, _P, _I64, _I64, _I64, _P], _I32),
 }
 
 _lock = threading.Lock()

@@ -26,6 +26,7 @@ SOURCES = [
     "paged_attn_fp8.hip",
     "block_table.hip",
     "swap_blocks.hip",
+    "kv_copy.hip",
     "gemm_skinny.hip",
     "gemm_tiny.hip",
     "gemm_wide.hip",

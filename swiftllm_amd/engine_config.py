@@ -81,6 +81,14 @@ class EngineConfig:
     max_loras: int = 0
     max_lora_rank: int = 16
     lora_modules: list = None
+    # Prefix caching by KV block copy (server/prefix_cache.py, csrc/kv_copy.hip). False (default):
+    # off — every step launches what it always did. True: a finished request keeps its block-table row and its blocks as a
+    # cache entry (reclaimed, least recently used first, whenever the scheduler needs the blocks, a row or an entry slot); a
+    # new prompt whose leading whole blocks equal an entry's gets private COPIES of those blocks (one launch) and prefills
+    # only the rest behind them, as a chunk behind a context — so it needs max_prefill_chunk > 0. Requests with a LoRA
+    # adapter or processed logits neither hit nor donate. prefix_cache_max_seqs: block-table rows the cache may hold.
+    enable_prefix_caching: bool = False
+    prefix_cache_max_seqs: int = 256
 
     # Internal switches (all on): set through `tuning`, read by the layer code as plain attributes.
     TUNING_DEFAULTS = dict(
@@ -154,6 +162,15 @@ class EngineConfig:
                 raise ValueError(f"lora_modules names an adapter twice: {names}")
             if len(names) > int(self.max_loras):
                 raise ValueError(f"lora_modules names {len(names)} adapters, max_loras is {self.max_loras}")
+        if self.enable_prefix_caching:
+            if int(self.max_prefill_chunk) == 0:
+                raise ValueError("enable_prefix_caching needs max_prefill_chunk > 0: a prompt that reuses a cached prefix "
+                                 "is a prompt chunk behind a context")
+            if not 1 <= int(self.prefix_cache_max_seqs) < int(self.max_seqs_in_block_table):
+                raise ValueError(f"prefix_cache_max_seqs must be in [1, max_seqs_in_block_table = "
+                                 f"{self.max_seqs_in_block_table}), got {self.prefix_cache_max_seqs}")
+        elif int(self.prefix_cache_max_seqs) < 1:
+            raise ValueError(f"prefix_cache_max_seqs must be >= 1, got {self.prefix_cache_max_seqs}")
         unknown = set(self.tuning or ()) - set(self.TUNING_DEFAULTS)
         if unknown:
             raise ValueError(f"unknown tuning switches {sorted(unknown)}; known: {sorted(self.TUNING_DEFAULTS)}")
@@ -171,6 +188,8 @@ class EngineConfig:
         if int(self.speculative_ngram) > 0 and self.kv_cache_dtype == "fp8_e4m3":
             raise ValueError("speculative_ngram > 0 cannot be combined with kv_cache_dtype='fp8_e4m3': the verify "
                              "attention kernel reads 16-bit KV pools only")
+        if self.enable_prefix_caching and self.decode_engine:
+            raise ValueError("enable_prefix_caching cannot be combined with tuning={'decode_engine': True}")
         if int(self.speculative_ngram) > 0 and self.decode_engine:
             raise ValueError("speculative_ngram > 0 cannot be combined with tuning={'decode_engine': True}: a verify step "
                              "is a multi-row forward the persistent one-sequence decode step does not run")
@@ -216,3 +235,8 @@ class EngineConfig:
                        help="A PEFT adapter directory to load at start-up under NAME (repeatable)")
         g.add_argument("--max-prefill-chunk", type=int, default=0,
                        help="Chunked prefill: prompt tokens per forward, at most (0 = off: a prompt is one forward)")
+        g.add_argument("--enable-prefix-caching", dest="enable_prefix_caching", action="store_true",
+                       help="Prefix caching by KV block copy: finished requests donate their whole blocks to later "
+                            "prompts with the same leading tokens (needs --max-prefill-chunk > 0)")
+        g.add_argument("--prefix-cache-max-seqs", type=int, default=256,
+                       help="Block-table rows the prefix cache may hold (below --max-seqs-in-block-table)")

@@ -50,6 +50,9 @@ class Engine:
         # initialize: capped by the model), verify steps run, drafts proposed and drafts accepted so far
         self.speculative_k = 0
         self.num_verify_steps = self.num_draft_tokens = self.num_accepted_tokens = 0
+        # prefix caching by block copy (EngineConfig.enable_prefix_caching): prompts that reused a cached prefix, the prompt
+        # tokens they did not prefill, and cache entries reclaimed so far
+        self.num_prefix_hits = self.num_prefix_hit_tokens = self.num_prefix_evictions = 0
         # asyncio thread -> model thread: lists of servable requests (the scheduler is touched by the model thread only)
         self._inbox: "queue.SimpleQueue[List[Request]]" = queue.SimpleQueue()
         # model thread only: (request, token, finished) of the last step, not fanned out yet
@@ -94,6 +97,11 @@ class Engine:
             self.speculative_k = max(0, min(want_k, int(getattr(self.model, "max_draft_tokens", 0) or 0)))
             print(f"[Engine] Prompt-lookup speculative decoding: {self.speculative_k} drafts per sequence per step "
                   f"(asked for {want_k}), decode batches of <= {self.engine_config.speculative_max_batch} greedy requests")
+        if self.scheduler.prefix_cache is not None:
+            if not hasattr(self.model, "copy_kv_prefix"):
+                raise RuntimeError("enable_prefix_caching needs a data plane with copy_kv_prefix")
+            print(f"[Engine] Prefix caching by KV block copy: up to {self.engine_config.prefix_cache_max_seqs} cached "
+                  f"sequences, reclaimed least recently used first")
         if hasattr(self.model, "after_launch_hook"):
             self.model.after_launch_hook = self._post_undelivered
         self.initialized = True
@@ -175,6 +183,28 @@ class Engine:
                 raise ValueError(f"LoRA adapter {name!r} is in use by a request that is waiting, running or swapped out")
             return self.model.unload_lora(name)
         return self._on_model_thread(unload)
+
+    # ---- prefix caching ------------------------------------------------------------------------------------------------
+    def drop_prefix_cache(self) -> int:
+        """Free every cached sequence (on the model thread): its KV blocks go back to the pool, its block-table row to the
+        id manager. Returns how many rows were freed. Needed before LlamaModel.set_kv_scales, which refuses while
+        sequences hold blocks; harmless with the option off."""
+        def drop():
+            ids = self.scheduler.drop_prefix_cache()
+            if ids:
+                self.model.free_seqs_resources(ids)
+            return len(ids)
+        return self._on_model_thread(drop)
+
+    def _retire(self, finished: List[Request]):
+        """Requests that finished in this step, before anyone is told: an eligible one's row becomes a prefix-cache entry
+        (it keeps its KV blocks), the others — and the entries that made room — are released as always."""
+        free = [r.request_id for r in finished if not self.scheduler.retire(r)]
+        evicted, _ = self.scheduler.take_cache_work()
+        self.num_prefix_evictions += len(evicted)
+        if free or evicted:
+            # release KV blocks before anyone is told: a caller that sees "finished" may tear us down
+            self.model.free_seqs_resources(free + evicted)
 
     # ---- asyncio side -------------------------------------------------------------------------------------------
     async def _tokenize_raw_request_event_loop(self):
@@ -280,16 +310,24 @@ class Engine:
         to do. Reference: engine.py:121-176."""
         self._drain_inbox()
         batch, swap_in, swap_out = self.scheduler.get_next_batch()
+        evicted, copies = self.scheduler.take_cache_work()      # (prefix caching; both empty with the option off)
         if not batch:
             self._post_undelivered()        # no launch to hide the fan-out behind
-            if not swap_in and not swap_out:
+            if not swap_in and not swap_out and not evicted:
                 return False
         if swap_out:
             self.model.swap_out_seqs([r.request_id for r in swap_out])
             self.num_swapped_out += len(swap_out)
+        if evicted:     # reclaimed cache entries: their blocks are what the swap-in, the copies and the forward were granted
+            self.model.free_seqs_resources(evicted)
+            self.num_prefix_evictions += len(evicted)
         if swap_in:
             self.model.swap_in_seqs([r.request_id for r in swap_in])
             self.num_swapped_in += len(swap_in)
+        if copies:      # the step's hits: private copies of the donors' blocks, one launch, before the forward that attends them
+            self.model.copy_kv_prefix([c[0] for c in copies], [c[1] for c in copies], [c[2] for c in copies])
+            self.num_prefix_hits += len(copies)
+            self.num_prefix_hit_tokens += sum(c[2] for c in copies)
         drafts = self._propose_drafts(batch) if batch and self.speculative_k > 0 else None
         if drafts is not None:
             self._verify_step(batch, drafts)
@@ -329,10 +367,9 @@ class Engine:
                 done = req.is_finished()
                 outputs.append((req, tok, done))
                 if done:
-                    finished.append(req.request_id)
+                    finished.append(req)
             if finished:
-                # release KV blocks before anyone is told: a caller that sees "finished" may tear us down
-                self.model.free_seqs_resources(finished)
+                self._retire(finished)
             self._undelivered = outputs
             self.scheduler.on_batch_finish(batch)
         return True
@@ -417,9 +454,9 @@ class Engine:
                 req.output_token_ids.append(tok)
                 outputs.append((req, tok, req.is_finished()))
             if req.is_finished():
-                finished.append(req.request_id)
+                finished.append(req)
         if finished:
-            self.model.free_seqs_resources(finished)
+            self._retire(finished)
         self._undelivered = outputs
         self.scheduler.on_batch_finish(batch)
 

@@ -20,6 +20,7 @@ from collections import deque
 from typing import Optional, Deque, List, Tuple
 
 from swiftllm_amd.utils import cdiv
+from .prefix_cache import PrefixCache
 from .structs import Request
 
 
@@ -41,6 +42,13 @@ class RequestIdManager:
     def free_ids(self, req_ids: List[int]):
         self._free.extend(req_ids)
 
+    def num_free(self) -> int:
+        return len(self._free)
+
+
+class _CacheConflict(Exception):
+    """Room (blocks, a row) could only be made by evicting an entry a prompt admitted in this step copies from."""
+
 
 class Scheduler:
     def __init__(self, model_config, engine_config, num_gpu_blocks: int, piggyback: bool = False):
@@ -58,6 +66,16 @@ class Scheduler:
         self.vocab_size: Optional[int] = getattr(model_config, "vocab_size", None)
         # ... and a callable returning the names of the LoRA adapters loaded right now (None: the data plane serves none)
         self.lora_names = None
+        # prefix caching by block copy (EngineConfig.enable_prefix_caching; chunked path only): finished requests' rows kept
+        # as cache entries, and the step's work for the engine — rows to free in the data plane (already back in the id
+        # manager here) and (donor row, new row, tokens) copies. None / always empty with the option off.
+        self.prefix_cache: Optional[PrefixCache] = None
+        if getattr(engine_config, "enable_prefix_caching", False):
+            self.prefix_cache = PrefixCache(engine_config.block_size, int(engine_config.prefix_cache_max_seqs))
+        self.cache_evictions: List[int] = []
+        self.cache_copies: List[Tuple[int, int, int]] = []
+        self._cache_pinned: set = set()     # rows a copy of this step reads: not evictable in this step
+        self._kept_ids: set = set()         # rows of finished requests that became entries (on_batch_finish keeps them)
 
     # ---- budgets -------------------------------------------------------------------------------------
     def _blocks(self, req: Request, extra_tokens: int = 0) -> int:
@@ -171,6 +189,12 @@ class Scheduler:
             used -= self._blocks(victim)
             swapped_out.append(victim)
         swapped_in: List[Request] = []
+        cache = self.prefix_cache
+        if cache is not None:
+            # cached blocks are reclaimable: every comparison below is made WITHOUT them, exactly as with the option off,
+            # and whatever it grants is made room for by evicting entries (least recently used first)
+            self._cache_pinned = set()
+            self._cache_make_room(used)
         if swapped_out:
             self.swapped_q.extendleft(swapped_out)
         else:
@@ -182,6 +206,8 @@ class Scheduler:
                 self.running_q.append(self.swapped_q.popleft())     # (it continues at its num_prefilled)
                 used += need
                 swapped_in.append(cand)
+                if cache is not None:
+                    self._cache_make_room(used)
 
         budget = self._chunk_cap()
         chunks: List[Request] = []
@@ -195,18 +221,12 @@ class Scheduler:
             chunks.append(req)
             budget -= take
         if not self.swapped_q:
-            while budget > 0 and self.waiting_q:
-                cand = self.waiting_q[0]
-                need = self._blocks(cand)
-                if len(self.running_q) + 1 > ecfg.max_batch_size or used + need > self.num_gpu_blocks:
-                    break       # strict FCFS: nothing may overtake the head of the queue
-                self.waiting_q.popleft()
-                cand.request_id = self.request_id_manager.get_id()
-                cand.prefill_take = min(budget, cand.prompt_len)
-                budget -= cand.prefill_take
-                used += need
-                self.running_q.append(cand)
-                chunks.append(cand)
+            try:
+                chunks += self._admit_waiting(budget, used, cache is not None)
+            except _CacheConflict:
+                # an entry this step copies from stood in the way of a later admission: the step is redone without hits,
+                # every entry evictable — what the scheduler without the cache admits
+                chunks += self._admit_waiting(budget, used, False)
         decoders = [r for r in self.running_q if r.is_prompt_resident()]
         if not chunks:
             return decoders, swapped_in, swapped_out[::-1]
@@ -219,6 +239,116 @@ class Scheduler:
             if sum(r.prefill_take for r in chunks) + len(decoders) <= ecfg.max_tokens_in_batch:
                 riders = decoders
         return chunks + riders, swapped_in, swapped_out[::-1]
+
+    # ---- prefix caching (EngineConfig.enable_prefix_caching) ----------------------------------------------------
+    @staticmethod
+    def cache_eligible(req: Request) -> bool:
+        """May hit and donate: no LoRA adapter (K/V depend on it) and no processed logits (the data plane's token history
+        starts at a context-0 prefill). Plain sampled requests are eligible: their draws depend on seed and position."""
+        sp = getattr(req, "sampling_params", None)
+        return getattr(req, "lora", None) is None and (sp is None or not sp.processes_logits)
+
+    def _cache_evict_one(self) -> bool:
+        entry = self.prefix_cache.evict_lru(self._cache_pinned)
+        if entry is None:
+            return False
+        self.cache_evictions.append(entry.seq_id)
+        self.request_id_manager.free_id(entry.seq_id)
+        return True
+
+    def _cache_make_room(self, used: int) -> bool:
+        """Evict until the running set's `used` blocks and the cache's fit the pool; False: only pinned entries are left."""
+        while used + self.prefix_cache.num_blocks_held > self.num_gpu_blocks:
+            if not self._cache_evict_one():
+                return False
+        return True
+
+    def _admit_waiting(self, budget: int, used: int, allow_hits: bool) -> List[Request]:
+        """New prompts from the head of the queue while the step's prompt-token budget, the batch and the pool take them
+        (the last part of _get_next_batch_chunked). With the prefix cache on, the comparisons are the same, on the same
+        numbers — the cache's blocks are not in `used` — and room is then made for what they granted. A prompt that
+        matches an entry (`allow_hits`) starts at num_prefilled = the matched tokens, so the budget counts only what is
+        fed; its block need is unchanged (private blocks for its whole length). Raises _CacheConflict — with every
+        admission of this call undone — when room could only be made by evicting an entry pinned by a hit of this call."""
+        ecfg, cache, ids = self.engine_config, self.prefix_cache, self.request_id_manager
+        admitted: List[Request] = []
+        copies: List[Tuple[int, int, int]] = []
+        while budget > 0 and self.waiting_q:
+            cand = self.waiting_q[0]
+            need = self._blocks(cand)
+            if len(self.running_q) + 1 > ecfg.max_batch_size or used + need > self.num_gpu_blocks:
+                break       # strict FCFS: nothing may overtake the head of the queue
+            entry, tokens = None, 0
+            if cache is not None:
+                if allow_hits and self.cache_eligible(cand):
+                    entry, tokens = cache.match(cand.prompt_token_ids)
+                fresh_pin = entry is not None and entry.seq_id not in self._cache_pinned
+                if entry is not None:
+                    self._cache_pinned.add(entry.seq_id)
+                ok = self._cache_make_room(used + need) and (ids.num_free() > 0 or self._cache_evict_one())
+                if not ok and fresh_pin:        # the donor itself stands in the way: no hit, the entry goes
+                    self._cache_pinned.discard(entry.seq_id)
+                    entry, tokens = None, 0
+                    ok = self._cache_make_room(used + need) and (ids.num_free() > 0 or self._cache_evict_one())
+                if not ok and len(cache) > 0:
+                    for r in reversed(admitted):
+                        self.running_q.pop()
+                        ids.free_id(r.request_id)
+                        r.request_id, r.num_prefilled, r.prefill_take = -1, 0, 0
+                        self.waiting_q.appendleft(r)
+                    self._cache_pinned = set()
+                    raise _CacheConflict()
+            self.waiting_q.popleft()
+            cand.request_id = ids.get_id()
+            if entry is not None:
+                cand.num_prefilled = tokens
+                copies.append((entry.seq_id, cand.request_id, tokens))
+            cand.prefill_take = min(budget, cand.prompt_len - cand.num_prefilled)
+            budget -= cand.prefill_take
+            used += need
+            self.running_q.append(cand)
+            admitted.append(cand)
+        self.cache_copies.extend(copies)
+        return admitted
+
+    def retire(self, req: Request) -> bool:
+        """A finished request, before on_batch_finish: True when its block-table row became a cache entry — the caller
+        then keeps the row's KV blocks — instead of going back to the id manager. The entry covers prompt + output[:-1]
+        (the last token's K/V was never stored), whole blocks only. An entry that had to go to make room for it is left in
+        `cache_evictions`."""
+        cache = self.prefix_cache
+        if cache is None or not self.cache_eligible(req) or req.request_id < 0:
+            return False
+        tokens = list(req.prompt_token_ids) + list(req.output_token_ids[:-1])
+        if len(tokens) < cache.block_size or cache.holds(tokens):
+            return False
+        self._cache_pinned = set()      # (the step's copies were issued before its forward)
+        while len(cache) >= cache.max_entries:
+            self._cache_evict_one()
+        if not cache.insert(req.request_id, tokens, self._blocks(req)):
+            return False
+        self._kept_ids.add(req.request_id)
+        return True
+
+    def take_cache_work(self) -> Tuple[List[int], List[Tuple[int, int, int]]]:
+        """(rows of evicted entries: the data plane frees them — they are back in the id manager already; copies of the
+        step as (donor row, new row, tokens)). Both empty with the option off."""
+        if not self.cache_evictions and not self.cache_copies:
+            return [], []
+        work = (self.cache_evictions, self.cache_copies)
+        self.cache_evictions, self.cache_copies = [], []
+        return work
+
+    def drop_prefix_cache(self) -> List[int]:
+        """Forget every entry; returns the rows the data plane must free (evictions not yet taken included). The rows go
+        back to the id manager here."""
+        if self.prefix_cache is None:
+            return []
+        ids = self.prefix_cache.clear()
+        self.request_id_manager.free_ids(ids)
+        self._cache_pinned = set()
+        evicted, _ = self.take_cache_work()
+        return evicted + ids
 
     def _admit_prefills(self) -> List[Request]:
         ecfg = self.engine_config
@@ -247,7 +377,10 @@ class Scheduler:
         return tokens <= ecfg.max_tokens_in_batch and blocks <= self.num_gpu_blocks
 
     def on_batch_finish(self, batch: List[Request]):
-        self.request_id_manager.free_ids([r.request_id for r in batch if r.is_finished()])
+        kept = self._kept_ids       # (rows that became prefix-cache entries stay out of the id manager; empty: option off)
+        self.request_id_manager.free_ids([r.request_id for r in batch if r.is_finished() and r.request_id not in kept])
+        if kept:
+            kept.difference_update(r.request_id for r in batch)
         self.running_q = [r for r in self.running_q if not r.is_finished()]
 
     def has_work(self) -> bool:

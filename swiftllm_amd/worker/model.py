@@ -24,6 +24,7 @@ import os
 import time
 from typing import List, Optional
 
+import numpy as np
 import torch
 
 from swiftllm_amd import _hip
@@ -37,6 +38,7 @@ from .block_manager import BlockManager
 from . import decode_engine as _decode_engine
 from .infer_state import LlamaInferState
 from .kernels.block_swapping import swap_blocks
+from .kernels.kv_copy import kv_copy_blocks
 from .kernels.linear import RawResidual
 from .kernels.paged_attn import verify_max_tokens
 from .kernels.rmsnorm import fused_add_rmsnorm_from_splitk, rmsnorm_inplace
@@ -1143,3 +1145,51 @@ class LlamaModel:
             self._histories.pop(sid, None)
         self.gpu_block_manager.free_blocks_for_seqs(seq_ids_list)
         self.cpu_block_manager.free_blocks_for_seqs(seq_ids_list)
+
+    # ---- prefix reuse by block copy --------------------------------------------------------------------------
+    @torch.inference_mode()
+    def copy_kv_prefix(self, src_seq_ids: List[int], dst_seq_ids: List[int], num_tokens: List[int]):
+        """The first num_tokens[i] tokens of sequence src_seq_ids[i] become the first num_tokens[i] tokens of sequence
+        dst_seq_ids[i]: the destination gets num_tokens[i] / block_size blocks of its own and the source's blocks are copied
+        into them, K and V, by ONE launch on the current stream (csrc/kv_copy.hip; one upload of the id lists, no host
+        sync). Whole blocks only; a destination owns nothing before the call. Afterwards
+        `forward([rest], [dst], [], prefill_ctx_lens=[num_tokens])` continues the destination behind the copied context.
+        Everything is refused on the host (ValueError / RuntimeError) before anything is allocated or launched. Stream
+        order makes reuse safe: a source freed by a later call is not overwritten before the copy has read it. Token
+        histories are not copied: a sequence whose logits are processed prefills whole (forward refuses it otherwise)."""
+        if self.gpu_block_manager is None or self.k_cache is None:
+            raise RuntimeError("copy_kv_prefix before init_kvcache_and_swap: there is no KV pool")
+        if not (len(src_seq_ids) == len(dst_seq_ids) == len(num_tokens)):
+            raise ValueError(f"copy_kv_prefix needs lists of one length, got {len(src_seq_ids)} sources, "
+                             f"{len(dst_seq_ids)} destinations and {len(num_tokens)} token counts")
+        if len(src_seq_ids) == 0:
+            return
+        bs = self.engine_config.block_size
+        mgr = self.gpu_block_manager
+        src_seq_ids, dst_seq_ids = [int(s) for s in src_seq_ids], [int(d) for d in dst_seq_ids]
+        num_tokens = [int(n) for n in num_tokens]
+        sources = set(src_seq_ids)
+        if len(set(dst_seq_ids)) != len(dst_seq_ids):
+            raise ValueError(f"copy_kv_prefix names a destination twice: {dst_seq_ids}")
+        for src, dst, n in zip(src_seq_ids, dst_seq_ids, num_tokens):
+            if n <= 0 or n % bs:
+                raise ValueError(f"copy_kv_prefix copies whole blocks: num_tokens must be a positive multiple of {bs}, "
+                                 f"got {n}")
+            if dst in sources:
+                raise ValueError(f"copy_kv_prefix: sequence {dst} is a destination and a source")
+            if not 0 <= dst < mgr.host.max_seqs:
+                raise RuntimeError(f"sequence id {dst} outside the block table (0..{mgr.host.max_seqs - 1})")
+            if mgr.host.num_allocated(src) < n // bs:
+                raise ValueError(f"copy_kv_prefix: source sequence {src} owns {mgr.host.num_allocated(src)} GPU blocks, "
+                                 f"{n} tokens need {n // bs}")
+            if mgr.host.num_allocated(dst):
+                raise ValueError(f"copy_kv_prefix: destination sequence {dst} already owns "
+                                 f"{mgr.host.num_allocated(dst)} blocks")
+        src_blocks = [b for src, n in zip(src_seq_ids, num_tokens) for b in mgr.get_block_ids_host(src)[:n // bs]]
+        self._lookahead = None
+        mgr.allocate_blocks_for_seqs(dst_seq_ids, num_tokens)      # (raises before it commits when the pool is short)
+        dst_blocks = [b for dst in dst_seq_ids for b in mgr.get_block_ids_host(dst)]
+        if len(dst_blocks) != len(src_blocks) or not sources.isdisjoint(dst_seq_ids) or set(dst_blocks) & set(src_blocks):
+            raise RuntimeError("copy_kv_prefix: the destinations' new blocks overlap the sources' (allocator state corrupt)")
+        d_src, d_dst = mgr._upload(np.asarray(src_blocks, dtype=np.int32), np.asarray(dst_blocks, dtype=np.int32))
+        kv_copy_blocks(self.k_cache, self.v_cache, d_src, d_dst)
