@@ -3,6 +3,7 @@ examples/offline.py against this implementation: build the model, size the KV po
 prefill a few prompts in one batch, then decode greedily step by step.
 
     python examples/offline.py --model-path /path/to/llama [--dtype bfloat16] [--steps 20] [--speculative-ngram 3]
+                               [--logprobs 3]
 
 With a HuggingFace tokenizer in the model directory the prompts are text; otherwise (e.g. the random-init
 checkpoints written by oracle/synth.py) random token ids are used and ids are printed.
@@ -33,6 +34,8 @@ def main():
     ap.add_argument("--lora", action="append", default=None, metavar="NAME=PATH",
                     help="a PEFT adapter directory (repeatable): prompt i runs with adapter i, the prompts beyond the "
                          "adapters with the base model")
+    ap.add_argument("--logprobs", type=int, default=None, metavar="N",
+                    help="report every generated token's log-probability, rank and N most likely alternatives (0..20)")
     args = ap.parse_args()
 
     cfg = swiftllm.EngineConfig(model_path=args.model_path, use_dummy=args.use_dummy, block_size=16,
@@ -65,17 +68,26 @@ def main():
     # one adapter per prompt, in the order of --lora; None (the base model) for the rest; no --lora: the call of always
     names = list(model.loras())
     kw = {"lora": [names[i] if i < len(names) else None for i in seq_ids]} if names else {}
+    if args.logprobs is not None:       # (no --logprobs: the call of always; last_logprobs is None then)
+        kw["sampling_params"] = [swiftllm.SamplingParams(logprobs=args.logprobs)] * len(seq_ids)
     outputs = [model.forward(input_ids, seq_ids, [], **kw)]
+    scores = [model.last_logprobs]
     lens = [len(x) for x in input_ids]
     t0 = time.perf_counter()
     for _ in range(args.steps):
         lens = [n + 1 for n in lens]
         outputs.append(model.forward([[t] for t in outputs[-1]], seq_ids, lens, **kw))
+        scores.append(model.last_logprobs)
     dt = time.perf_counter() - t0
     print(f"{args.steps} decode steps x {len(seq_ids)} sequences: {dt / args.steps * 1e3:.2f} ms/step")
     for i in seq_ids:
         toks = [step[i] for step in outputs]
         print(f"[{i}]", tokenizer.decode(toks, skip_special_tokens=True) if tokenizer else toks)
+        if args.logprobs is not None:
+            for step in scores:
+                lp = step[i]
+                top = ", ".join(f"{t}: {v:.3f}" for t, v in lp.top)
+                print(f"      {lp.token_id}: {lp.logprob:.3f} (rank {lp.rank})" + (f"  top: {top}" if top else ""))
     model.free_seqs_resources(seq_ids)
 
 

@@ -200,6 +200,24 @@ int swl_logits_adjust(void *x, int64_t num_rows, int32_t n, int64_t row_stride, 
                       const int32_t *edit_offsets, const int32_t *edit_ids, const int32_t *edit_meta,
                       const float *edit_bias, const float *row_params, swl_stream_t stream);
 
+/* ---- Log-probabilities of the picked token and the top-N alternatives, after swl_argmax / swl_sample -----------
+ * reference: none (post_layer.py:40 returns token ids only); this is an addition.
+ * Row r of x[num_rows, n] (row stride row_stride elements, any n >= 1) asks when top_n[r] >= 0; a row that does not
+ * ask writes nothing. With f_i = float(x_i), NaN elements ignored, lse = max f + log(sum exp(f_i - max f)) in fp32,
+ * logprob(i) = f_i - lse: the model's distribution at temperature 1 over the logits as they stand. Elements are ordered
+ * by (value descending, id ascending) on the stored 16-bit values, -0 == +0, NaN last. lp / ids are [num_rows, n_cap + 1]
+ * (contiguous), rank is [num_rows]. Column 0: the token chosen[r] — its logprob, its id, and rank[r] = 1 + the number of
+ * elements ahead of it in that order (exact). chosen[r] outside [0, n): logprob NaN, id -1, rank 0, nothing read outside
+ * the row. Columns 1..N, N = min(top_n[r], n_cap): the first N elements of that order (ids exact, ties included) with
+ * their logprobs; a row narrower than N fills the rest with id -1 / NaN. An asking row writes exactly columns 0..N and
+ * rank[r]. A row whose maximum is not finite reports NaN for every logprob; -inf elements of a healthy row report -inf.
+ * 0 <= n_cap <= 20. x needs 2-byte alignment (16-byte accesses are used when x is 16-byte aligned and
+ * row_stride % 8 == 0), the other arrays their natural alignment. No scratch, no atomics: bit-reproducible, and a row's
+ * outputs do not depend on the batch. The exact contract is in csrc/logprobs.hip. num_rows > 2^31 - 1:
+ * SWL_ERR_UNSUPPORTED. */
+int swl_logprobs(float *lp, int32_t *ids, int32_t *rank, const void *x, int64_t num_rows, int32_t n, int64_t row_stride,
+                 int32_t dtype, const int64_t *chosen, const int32_t *top_n, int32_t n_cap, swl_stream_t stream);
+
 /* ---- Paged attention, decode (flash-decoding, "paged attention v2") --------------------------
  * reference: paged_attn.py:9-108 (phase 1), :111-149 (phase 2), launcher :152-222
  * q[Bd, H, D] (token stride q_tok_stride), o[Bd, H, D] (token stride o_tok_stride).

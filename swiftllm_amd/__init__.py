@@ -2,14 +2,15 @@
 
 Public names match the reference package (swiftllm/__init__.py:1-9): `EngineConfig`,
 `LlamaModel`, and — imported lazily because they pull in the serving stack — `Engine`,
-`RawRequest`. `SamplingParams` is an addition (the reference samples greedily only).
+`RawRequest`. `SamplingParams` is an addition (the reference samples greedily only), and so is `TokenLogprob` (what a
+request that asks for logprobs learns about each generated token).
 """
 from swiftllm_amd.engine_config import EngineConfig
 from swiftllm_amd.model_config import LlamaModelConfig
-from swiftllm_amd.sampling_params import SamplingParams
+from swiftllm_amd.sampling_params import SamplingParams, TokenLogprob
 from swiftllm_amd.worker.model import LlamaModel
 
-__all__ = ["EngineConfig", "LlamaModelConfig", "LlamaModel", "SamplingParams", "Engine", "RawRequest"]
+__all__ = ["EngineConfig", "LlamaModelConfig", "LlamaModel", "SamplingParams", "TokenLogprob", "Engine", "RawRequest"]
 
 
 def __getattr__(name):

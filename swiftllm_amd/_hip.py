@@ -145,6 +145,9 @@ _SPECIAL = {
     # KV block copy inside the GPU pools (csrc/kv_copy.hip; prefix caching): an "int rc = f(...)" entry too, registered
     # here for the same reason (its own contract: tests/test_gpu_kv_copy.py).
     "swl_kv_copy_blocks": ([_P, _P, _P, _P, _I64, _I64, _I64, _P], _I32),
+    # Per-token logprobs (csrc/logprobs.hip): an "int rc = f(...)" entry too, registered here for the same reason (its own
+    # contract: tests/test_logprobs_abi.py, tests/test_gpu_logprobs.py).
+    "swl_logprobs": ([_P, _P, _P, _P, _I64, _I32, _I64, _I32, _P, _P, _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

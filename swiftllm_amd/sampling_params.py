@@ -11,11 +11,26 @@ and a frequency penalty (output tokens only), an additive `logit_bias` per token
 probability is below `min_p` times the largest one are removed before top-k / top-p act). `stop_token_ids` end the
 request at the first of them (delivered as its last token); while fewer than `min_tokens` tokens have been generated the
 stop tokens cannot be picked.
+
+`logprobs` = N (0..20) asks for the log-probability and the rank of every generated token and for the N most likely
+tokens at its position (csrc/logprobs.hip has the contract): the model's distribution at temperature 1 over the logits
+as they stand when the token is picked — after the edits above, before temperature / top-k / top-p, which do not
+renormalise it. It changes no token.
 """
 import dataclasses
 import math
 import secrets
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
+
+MAX_LOGPROBS = 20   # alternatives a token can report (the kernel's LDS-ordered survivors)
+
+
+class TokenLogprob(NamedTuple):
+    """What a request that asks for logprobs learns about one generated token."""
+    token_id: int
+    logprob: float      # NaN when the row's maximum is not finite
+    rank: int           # 1 = the most likely token (ties: the lowest id first)
+    top: Tuple[Tuple[int, float], ...] = ()     # the N most likely (id, logprob), in order
 
 
 @dataclasses.dataclass(frozen=True)
@@ -31,10 +46,14 @@ class SamplingParams:
     logit_bias: Optional[Tuple[Tuple[int, float], ...]] = None  # a mapping / pairs id -> bias; stored as sorted pairs
     stop_token_ids: Tuple[int, ...] = ()
     min_tokens: int = 0                 # stop tokens are banned while fewer output tokens exist
+    logprobs: Optional[int] = None      # None: off; N in 0..20: every generated token reports itself and its top N
 
     def __post_init__(self):
         self._check_sampling()
         self._check_processing()
+        n = self.logprobs
+        if n is not None and (isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= MAX_LOGPROBS):
+            raise ValueError(f"logprobs must be None or an integer in [0, {MAX_LOGPROBS}], got {n!r}")
 
     def _check_processing(self):
         def number(v):
@@ -111,7 +130,7 @@ class SamplingParams:
     @property
     def plain(self) -> bool:
         """Nothing to do beyond the argmax of the raw logits, run to output_len: what None means."""
-        return self.greedy and not self.processes_logits and not self.stop_token_ids
+        return self.greedy and not self.processes_logits and not self.stop_token_ids and self.logprobs is None
 
     def min_p_gap(self) -> float:
         """What the kernel compares x_i - max(x) with: T * ln(min_p), computed in double precision (the caller rounds it

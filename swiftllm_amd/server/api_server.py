@@ -8,11 +8,15 @@ top_k, top_p, seed; repetition_penalty, presence_penalty, frequency_penalty, min
 stop_token_ids, min_tokens; absent = greedy to output_len, as in the reference) and "lora": the name of a loaded LoRA
 adapter (--max-loras / --lora NAME=PATH; absent = the base model): non-streaming answers
 {"output_token_ids": [...]} (or {"output": text} with decode), streaming sends one line per token.
+"logprobs": N (0..20) asks for every generated token's log-probability, rank and N most likely alternatives: the
+non-streaming answer gains "logprobs": [{"token_id", "logprob", "rank", "top": [[id, logprob], ...]}, ...] and a stream
+sends one such JSON object per line (with "text" under decode); values that are not finite are sent as null.
 `GET /load` reports outstanding tokens (used by the replica router). Any engine failure takes the
 process down (reference api_server.py:114-119) so a supervisor can restart the replica.
 """
 import argparse
 import asyncio
+import json
 import math
 import os
 import traceback
@@ -22,7 +26,7 @@ import uvicorn
 from fastapi.responses import JSONResponse, StreamingResponse
 
 from swiftllm_amd.engine_config import EngineConfig
-from swiftllm_amd.sampling_params import SamplingParams
+from swiftllm_amd.sampling_params import MAX_LOGPROBS, SamplingParams
 from .engine import Engine
 from .structs import RawRequest
 
@@ -108,6 +112,9 @@ def _validate_sampling(body) -> "str | None":
     n = body.get("min_tokens")
     if n is not None and (not _is_int(n) or n < 0):
         return "min_tokens must be an integer >= 0"
+    lp = body.get("logprobs")
+    if lp is not None and (not _is_int(lp) or not 0 <= lp <= MAX_LOGPROBS):
+        return f"logprobs must be an integer in [0, {MAX_LOGPROBS}]"
     return None
 
 
@@ -117,7 +124,7 @@ _PROCESSING_FIELDS = ("repetition_penalty", "presence_penalty", "frequency_penal
 
 
 def _sampling_params(body) -> "SamplingParams | None":
-    if all(body.get(f) is None for f in _SAMPLING_FIELDS + _PROCESSING_FIELDS):
+    if all(body.get(f) is None for f in _SAMPLING_FIELDS + _PROCESSING_FIELDS + ("logprobs",)):
         return None
     kw = {}
     if any(body.get(f) is not None for f in _PROCESSING_FIELDS):       # (none of them: the params of always)
@@ -130,7 +137,18 @@ def _sampling_params(body) -> "SamplingParams | None":
                   stop_token_ids=tuple(body.get("stop_token_ids") or ()), min_tokens=int(body.get("min_tokens") or 0))
     return SamplingParams(temperature=float(body.get("temperature") or 0.0), top_k=int(body.get("top_k") or 0),
                           top_p=float(body.get("top_p") if body.get("top_p") is not None else 1.0),
-                          seed=body.get("seed"), **kw)
+                          seed=body.get("seed"), logprobs=body.get("logprobs"), **kw)
+
+
+def _finite_or_none(v: float) -> "float | None":
+    """JSON has no NaN / Infinity (JSONResponse refuses them): such a value is sent as null."""
+    return v if math.isfinite(v) else None
+
+
+def _logprob_json(lp) -> dict:
+    """A TokenLogprob as the object both answer forms carry."""
+    return {"token_id": lp.token_id, "logprob": _finite_or_none(lp.logprob), "rank": lp.rank,
+            "top": [[i, _finite_or_none(v)] for i, v in lp.top]}
 
 
 def build_app(engine: Engine) -> fastapi.FastAPI:
@@ -149,13 +167,19 @@ def build_app(engine: Engine) -> fastapi.FastAPI:
         raw = RawRequest(body.get("prompt", ""), body["output_len"], body.get("prompt_token_ids"),
                          sampling_params=_sampling_params(body), lora=body.get("lora"))
         want_text = bool(body.get("decode", False))
+        want_logprobs = body.get("logprobs") is not None
         cost = raw.output_len + len(raw.prompt_token_ids or raw.prompt.split())
         state["outstanding_tokens"] += cost
         if body.get("stream", False):
             async def lines():
                 try:
                     async for step in engine.add_request_and_stream(raw):
-                        if want_text:
+                        if want_logprobs and step.logprobs is not None:
+                            obj = _logprob_json(step.logprobs)
+                            if want_text:
+                                obj["text"] = await engine.tokenization_engine.decode([step.token_id])
+                            yield json.dumps(obj, allow_nan=False) + "\n"
+                        elif want_text:
                             yield await engine.tokenization_engine.decode([step.token_id]) + "\n"
                         else:
                             yield f"{step.token_id}\n"
@@ -171,9 +195,11 @@ def build_app(engine: Engine) -> fastapi.FastAPI:
             # the server's (503: a router in front retries on another replica)
             dead = getattr(engine, "_dead", None) is not None and request.error == engine._dead
             return JSONResponse({"error": request.error}, status_code=503 if dead else 400)
-        if want_text:
-            return JSONResponse({"output": await engine.tokenization_engine.decode(token_ids)})
-        return JSONResponse({"output_token_ids": token_ids})
+        answer = ({"output": await engine.tokenization_engine.decode(token_ids)} if want_text else
+                  {"output_token_ids": token_ids})
+        if want_logprobs:
+            answer["logprobs"] = [_logprob_json(lp) for lp in request.output_logprobs if lp is not None]
+        return JSONResponse(answer)
 
     @app.get("/load")
     async def load():

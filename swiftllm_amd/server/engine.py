@@ -55,8 +55,8 @@ class Engine:
         self.num_prefix_hits = self.num_prefix_hit_tokens = self.num_prefix_evictions = 0
         # asyncio thread -> model thread: lists of servable requests (the scheduler is touched by the model thread only)
         self._inbox: "queue.SimpleQueue[List[Request]]" = queue.SimpleQueue()
-        # model thread only: (request, token, finished) of the last step, not fanned out yet
-        self._undelivered: List[Tuple[Request, int, bool]] = []
+        # model thread only: (request, token, finished, its TokenLogprob or None) of the last step, not fanned out yet
+        self._undelivered: List[Tuple[Request, int, bool, object]] = []
         self._stop = threading.Event()
         self._model_thread: Optional[threading.Thread] = None
         # event-loop thread only: requests somebody may still be waiting on (woken with `error` set if the model thread dies)
@@ -232,10 +232,10 @@ class Engine:
                 self._inbox.put(servable)
             await asyncio.sleep(0.001)
 
-    def _deliver(self, outputs: List[Tuple[Request, int, bool]]):
+    def _deliver(self, outputs: List[Tuple[Request, int, bool, object]]):
         """Fan one step's tokens out to the per-request queues and events (event-loop thread)."""
-        for req, tok, finished in outputs:
-            req.output_q.put_nowait(StepOutput(tok, req))
+        for req, tok, finished, lp in outputs:
+            req.output_q.put_nowait(StepOutput(tok, req, lp))
             if finished:
                 self._live.discard(req)
                 req.finished_event.set()
@@ -356,16 +356,25 @@ class Engine:
             finally:
                 self._post_undelivered()    # (a data plane without the hook, or a forward that raised before launching)
             self.num_forwards += 1
+            # (a step in which some request asks for logprobs: what the data plane learnt about its tokens, aligned with
+            # the batch; a data plane that never scores is not asked)
+            scores = None
+            if any(sp is not None and sp.logprobs is not None for sp in sampling):
+                scores = getattr(self.model, "last_logprobs", None)
             outputs, finished = [], []
-            for req, tok in zip(batch, tokens):
+            for i, (req, tok) in enumerate(zip(batch, tokens)):
                 if id(req) in takes:
                     req.num_prefilled += takes[id(req)]
                     req.prefill_take = 0
                     if req.num_prefilled < req.prompt_len:
-                        continue        # not the last chunk: its token is discarded — nothing appended, nothing delivered
+                        continue        # not the last chunk: its token (and its logprobs) discarded — nothing appended, nothing delivered
                 req.output_token_ids.append(tok)
+                lp = None
+                if scores is not None and sampling[i] is not None and sampling[i].logprobs is not None:
+                    lp = scores[i]
+                    req.output_logprobs.append(lp)
                 done = req.is_finished()
-                outputs.append((req, tok, done))
+                outputs.append((req, tok, done, lp))
                 if done:
                     finished.append(req)
             if finished:
@@ -452,7 +461,7 @@ class Engine:
                 if req.is_finished():
                     break
                 req.output_token_ids.append(tok)
-                outputs.append((req, tok, req.is_finished()))
+                outputs.append((req, tok, req.is_finished(), None))
             if req.is_finished():
                 finished.append(req)
         if finished:

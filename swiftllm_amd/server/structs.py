@@ -4,14 +4,15 @@ import asyncio
 import dataclasses
 from typing import List, Optional
 
-from swiftllm_amd.sampling_params import SamplingParams
+from swiftllm_amd.sampling_params import SamplingParams, TokenLogprob
 
 
 @dataclasses.dataclass
 class StepOutput:
-    """One generated token of one request."""
+    """One generated token of one request; `logprobs`: what a request that asks for them learns about it."""
     token_id: int
     request: "Request"
+    logprobs: Optional[TokenLogprob] = None
 
 
 class RawRequest:
@@ -40,6 +41,8 @@ class Request:
         self.finished_event = asyncio.Event()                           # non-streaming consumers wait here
         self.request_id = -1            # row of the block table, assigned when the request is admitted
         self.output_token_ids: List[int] = []
+        # one TokenLogprob per output token, for a request whose sampling params ask for logprobs (empty otherwise)
+        self.output_logprobs: List[TokenLogprob] = []
         self.error: Optional[str] = None    # set instead of scheduling when the request can never be served
         # multi-LoRA serving: the adapter every step of this request runs with (None = the base model); such a request is
         # never speculated
@@ -47,7 +50,8 @@ class Request:
         # None = greedy. A None seed is resolved here, once: the stream depends on (seed, position) only, so the request
         # draws the same tokens through preemption, swap-out and swap-in, in any batch, on any replica
         # (None also stands for params that ask for nothing — `plain`; a greedy request with penalties, a bias, min_tokens
-        # or stop tokens keeps its params: the data plane processes its logits, and it is never speculated)
+        # or stop tokens keeps its params: the data plane processes its logits, and it is never speculated; so does one
+        # that asks for logprobs: the data plane scores its tokens)
         sp = getattr(raw_request, "sampling_params", None)
         self.sampling_params: Optional[SamplingParams] = (None if sp is None or sp.plain else
                                                           sp if sp.greedy else sp.with_seed())

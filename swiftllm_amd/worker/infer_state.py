@@ -51,6 +51,9 @@ class LlamaInferState:
     # A processed step (some row's params edit its logits): kernels/logits_process.AdjustArgs over the model's persistent
     # entry buffer; the post layer runs the adjustment between lm_head and the choice of the token. None: no such row.
     adjust: Optional[object] = None
+    # A scored step (some row asks for logprobs): kernels/logprobs.LogprobArgs over the model's persistent buffer; the post
+    # layer scores the picked tokens against the logits they were picked from. None: no such row, no launch.
+    logprobs: Optional[object] = None
     # Chunked prefill: tokens of each prefill sequence already resident in the pool (int32 [num_prefill_seqs]); its new
     # tokens take logical positions [ctx, ctx + len) and attend to the pool (kernels/prefill_attn.prefill_attention_paged).
     # None: every prompt starts at position 0 and attends to its fresh projections — the reference's prefill.

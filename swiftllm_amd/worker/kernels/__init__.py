@@ -3,7 +3,8 @@
 One module per module of the reference's swiftllm/worker/kernels, exporting functions with the same
 names and argument meaning; each one validates its tensors (the reference's asserts), then calls the
 gfx950 kernel through the C ABI (swiftllm_amd._hip). `swap_blocks` (reference: the swiftllm_c
-extension) lives in block_swapping.py; `kv_copy_blocks` (an addition: KV block copies inside the GPU pools) in kv_copy.py.
+extension) lives in block_swapping.py; `kv_copy_blocks` (an addition: KV block copies inside the GPU pools) in kv_copy.py;
+`token_logprobs` (an addition: log-probabilities of the picked tokens and their top-N alternatives) in logprobs.py.
 """
 from .linear import linear
 from .rmsnorm import rmsnorm_inplace, fused_add_rmsnorm_inplace
@@ -19,10 +20,11 @@ from .block_mgmt import (
 )
 from .block_swapping import swap_blocks
 from .kv_copy import kv_copy_blocks
+from .logprobs import token_logprobs
 
 __all__ = [
     "linear", "rmsnorm_inplace", "fused_add_rmsnorm_inplace", "rotary_embedding_inplace",
     "store_kvcache", "prefill_attention", "prefill_attention_paged", "paged_attention", "silu_and_mul_inplace",
     "set_block_table_and_num_seq_alloc_blocks", "unset_block_table_and_num_seq_alloc_blocks",
-    "gather_allocated_blocks_and_unset", "swap_blocks", "kv_copy_blocks",
+    "gather_allocated_blocks_and_unset", "swap_blocks", "kv_copy_blocks", "token_logprobs",
 ]

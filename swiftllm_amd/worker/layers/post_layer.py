@@ -5,6 +5,7 @@ import torch
 from ..kernels.rmsnorm import rmsnorm_inplace
 from ..kernels.linear import linear
 from ..kernels.logits_process import adjust_logits
+from ..kernels.logprobs import token_logprobs
 from ..kernels.sampling import argmax_rows, sample_rows
 
 
@@ -29,15 +30,18 @@ class LlamaPostLayer:
                              device=input_embds.device, dtype=torch.int32)))
         last_input = input_embds.index_select(0, idx)    # fresh [batch, hidden] copy
         rmsnorm_inplace(last_input, self.weights.final_norm, self.model_config.rms_norm_eps)
-        return self.forward_normed(last_input, sampling=infer_state.sampling, adjust=infer_state.adjust)
+        return self.forward_normed(last_input, sampling=infer_state.sampling, adjust=infer_state.adjust,
+                                   logprobs=infer_state.logprobs)
 
     def forward_normed(self, last_input: torch.Tensor, out: torch.Tensor = None, sampling=None,
-                       adjust=None) -> torch.Tensor:
+                       adjust=None, logprobs=None) -> torch.Tensor:
         """lm_head + sampling on rows that already went through the final norm (a pure-decode batch whose
         last add + norm ran fused on the split-K partials of the last down projection: every row is a last token).
         `sampling`: the step's kernels/sampling.SampleArgs, or None for an all-greedy step (argmax, as before).
         `adjust`: the step's kernels/logits_process.AdjustArgs — penalties, bias and min-p are applied to the logits in
-        place before the token is picked (the tap then shows what it was picked from) — or None: no launch."""
+        place before the token is picked (the tap then shows what it was picked from) — or None: no launch.
+        `logprobs`: the step's kernels/logprobs.LogprobArgs — once the tokens are picked, the asking rows' log-probability,
+        rank and top-N alternatives are written into its buffers, from the same logits — or None: no launch."""
         logits = linear(last_input, self.weights.lm_head, self.skinny)   # [batch, vocab]
         if adjust is not None:
             adjust_logits(logits, adjust)
@@ -45,5 +49,9 @@ class LlamaPostLayer:
         if self.logits_tap is not None:
             self.logits_tap.append(logits)
         if sampling is not None:
-            return sample_rows(logits, sampling, None, out)
-        return argmax_rows(logits, out)
+            tokens = sample_rows(logits, sampling, None, out)
+        else:
+            tokens = argmax_rows(logits, out)
+        if logprobs is not None:
+            token_logprobs(logits, tokens, logprobs)
+        return tokens

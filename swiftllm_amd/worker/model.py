@@ -43,6 +43,7 @@ from .kernels.linear import RawResidual
 from .kernels.paged_attn import verify_max_tokens
 from .kernels.rmsnorm import fused_add_rmsnorm_from_splitk, rmsnorm_inplace
 from .kernels import logits_process
+from .kernels import logprobs as token_scores
 from .kernels.sampling import device_args, pack_params
 from .lora import LoraBatch, LoraStaging, LoraStep, LoraStore, parse_lora_modules, rows_of_sequences
 from .layers.pre_layer import LlamaPreLayer
@@ -70,7 +71,7 @@ class _DecodeGraph:
 
 class _DecodeLookahead:
     """Everything the NEXT decode step of the same batch needs, prepared while the GPU was still busy with this one."""
-    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev", "sampling", "processed")
+    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev", "sampling", "processed", "scoring")
 
 
 class LlamaModel:
@@ -133,6 +134,16 @@ class LlamaModel:
         self._histories = {}
         self._edit_host = self._edit_host_np = self._edit_dev = self._edit_done = None
         self._edit_rows_cap = 0
+        # per-token logprobs (kernels/logprobs.py): one persistent device buffer — the rows' N, then what the kernel writes
+        # (rank, logprobs, ids; rows x 21) — at a fixed address (a scored hipGraph reads and writes it on every replay), the
+        # pinned staging of the N (one H2D copy per scored step that is not a look-ahead hit) and the pinned buffer the
+        # results come back through (one D2H copy per scored step, enqueued before the tokens' sync)
+        self._score_dev = self._score_host = self._score_host_np = self._score_done = None
+        self._score_out = self._score_out_np = None
+        self._score_rows_cap = 0
+        # what the last forward / forward_verify call learnt about its tokens: None when no row asked, else one
+        # TokenLogprob or None per sequence of the batch
+        self.last_logprobs = None
         # speculative decoding: drafts one verify step takes per sequence (forward_verify) = the verify attention kernel's
         # tokens per sequence (16 / G) minus the last accepted token that leads them; 0 with FP8 pools (no instantiation)
         self.max_draft_tokens = 0 if self.kv_fp8 else max(0, verify_max_tokens(self.model_config) - 1)
@@ -170,6 +181,7 @@ class LlamaModel:
         ecfg = self.engine_config
         self._ensure_sampling_rows(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
         self._ensure_edit_buffer(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)), 0)
+        self._ensure_score_rows(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
         # (... and so are the adapter slot stacks: the KV pool is sized with them)
         if int(getattr(ecfg, "max_loras", 0) or 0) > 0:
             self.lora_store = LoraStore(self.model_config, int(ecfg.max_loras), int(ecfg.max_lora_rank), self.dtype,
@@ -510,8 +522,34 @@ class LlamaModel:
                     self._edit_dev[lo:lo + used].copy_(self._edit_host[lo:lo + used], non_blocking=True)
         self._edit_done.record()
 
+    def _ensure_score_rows(self, rows: int):
+        """The persistent logprob buffer holds `rows` rows. Growing it moves it: the graphs captured against the old one are
+        dropped."""
+        if self._score_rows_cap >= rows:
+            return
+        cap = max(rows, 2 * self._score_rows_cap)
+        total = token_scores.buffer_len(cap)
+        self._score_host = torch.empty(cap, dtype=torch.int32, pin_memory=True)
+        self._score_host_np = self._score_host.numpy()
+        self._score_out = torch.empty(total - cap, dtype=torch.int32, pin_memory=True)
+        self._score_out_np = self._score_out.numpy()
+        self._score_dev = torch.zeros(total, dtype=torch.int32, device=self.device)
+        self._score_dev[:cap].fill_(-1)     # (no row asks)
+        self._score_done = torch.cuda.Event()
+        self._score_rows_cap = cap
+        self._drop_decode_graphs()     # captured scored graphs point into the old buffer
+
+    def _upload_scoring(self, scoring: List[Optional[int]], rows: int):
+        """One async H2D copy of the step's N per row (None rows, padded bucket rows and everything past them: -1)."""
+        self._ensure_score_rows(rows)
+        self._score_done.synchronize()     # (the previous step's copy out of the pinned buffer: long done)
+        token_scores.pack_top_n(scoring, self._score_host_np)
+        self._score_dev[:self._score_rows_cap].copy_(self._score_host, non_blocking=True)
+        self._score_done.record()
+
     def _make_infer_state(self, plan: BatchPlan, dev: dict, ignore_kvcache: bool,
-                          sampled: bool = False, processed: bool = False, scratch_rows: int = None) -> LlamaInferState:
+                          sampled: bool = False, processed: bool = False, scratch_rows: int = None,
+                          scored: bool = False) -> LlamaInferState:
         """`scratch_rows`: rows whose flash-decoding partials the persistent scratch must hold when the step splits its
         sequences — the decoding sequences (default); a verify step: every row."""
         nsb = plan.num_seq_blocks
@@ -537,6 +575,7 @@ class LlamaModel:
             paged_attn_scratch=self._scratch if nsb > 1 else None,
             sampling=device_args(self._sample_dev, dev["seq_lengths"]) if sampled else None,
             adjust=logits_process.device_args(self._edit_dev, self._edit_rows_cap) if processed else None,
+            logprobs=token_scores.device_args(self._score_dev, self._score_rows_cap) if scored else None,
             prefill_ctx_lens=dev.get("prefill_ctx_lens"), max_prefill_total_len=plan.max_prefill_total_len,
             kv_scales=self.kv_scales, kv_inv_scales=self.kv_inv_scales,
             verify=plan.verify_row_lens is not None, verify_row_lens=dev.get("verify_row_lens"))
@@ -552,7 +591,7 @@ class LlamaModel:
                                   self.engine_config.max_blocks_per_seq)
             rmsnorm_inplace(x, self.weight.final_norm, self.model_config.rms_norm_eps)
             return self.post_layer.forward_normed(x, out=self._engine.tok_err[:1], sampling=infer_state.sampling,
-                                                  adjust=infer_state.adjust)
+                                                  adjust=infer_state.adjust, logprobs=infer_state.logprobs)
         x = self.pre_layer.forward(input_ids)
         residual = torch.zeros_like(x)
         block_table = None if infer_state.ignore_kvcache else self.gpu_block_manager.block_table
@@ -561,12 +600,14 @@ class LlamaModel:
         if isinstance(x, RawResidual):          # the last down projection added itself into the residual (rows_decode):
             x = residual.clone()                # pure decode, every row a last token — final norm of the residual rows
             rmsnorm_inplace(x, self.weight.final_norm, self.model_config.rms_norm_eps)
-            return self.post_layer.forward_normed(x, sampling=infer_state.sampling, adjust=infer_state.adjust)
+            return self.post_layer.forward_normed(x, sampling=infer_state.sampling, adjust=infer_state.adjust,
+                                                  logprobs=infer_state.logprobs)
         if not isinstance(x, torch.Tensor):     # the last down projection left as split-K partials
             if infer_state.num_prefill_seqs == 0:
                 # pure decode: every row is a last token — reduce + residual add + final norm in one launch
                 x = fused_add_rmsnorm_from_splitk(x, residual, self.weight.final_norm, self.model_config.rms_norm_eps)
-                return self.post_layer.forward_normed(x, sampling=infer_state.sampling, adjust=infer_state.adjust)
+                return self.post_layer.forward_normed(x, sampling=infer_state.sampling, adjust=infer_state.adjust,
+                                                      logprobs=infer_state.logprobs)
             x = x.materialize()
         x += residual
         return self.post_layer.forward(x, infer_state)
@@ -660,7 +701,7 @@ class LlamaModel:
         return plan
 
     def _forward_decode_graph(self, plan: BatchPlan, dev: dict, sampled: bool = False,
-                              processed: bool = False) -> torch.Tensor:
+                              processed: bool = False, scored: bool = False) -> torch.Tensor:
         sbs, nsb_cap = self._graph_bucket(plan)
         use_engine = self._engine is not None and plan.batch_size == 1
         tap = self.post_layer.logits_tap
@@ -668,18 +709,19 @@ class LlamaModel:
         # (the engine has one launch geometry; a graph captured while a test taps the logits keeps its [B, vocab] tensor
         # alive in the shared pool, one captured without the tap does not — up to 65 MB per graph at 256 sequences)
         # (a sampled step is a graph of its own: its sampler reads the persistent parameter buffer; greedy graphs are as
-        # they were; so is a processed step: its adjustment kernel reads the persistent entry buffer)
-        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None, sampled, processed)
+        # they were; so is a processed step: its adjustment kernel reads the persistent entry buffer; and a scored step: its
+        # logprob kernel reads the rows' N from, and writes its results into, the persistent logprob buffer)
+        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None, sampled, processed, scored)
         entry = self._decode_graphs.pop(key, None)
         plan.seq_block_size, plan.num_seq_blocks = sbs, nsb_cap
         if entry is None:
             self.graph_captures += 1
             t_cap = time.perf_counter()
-            state = self._make_infer_state(plan, dev, False, sampled, processed)
+            state = self._make_infer_state(plan, dev, False, sampled, processed, scored=scored)
             # one eager run on a side stream first (library handles, workspaces, allocator pools): nothing may be lazily
             # initialised while the stream is capturing. Once per BATCH BUCKET (r06b): a new split geometry at a batch size
             # that has been captured before launches the same kernels on the same shapes — only the attention grid moves.
-            warm_key = (key[0], use_engine, tap is not None, sampled, processed)
+            warm_key = (key[0], use_engine, tap is not None, sampled, processed, scored)
             if warm_key not in self._warmed_buckets:
                 warm = torch.cuda.Stream()
                 warm.wait_stream(torch.cuda.current_stream())
@@ -714,7 +756,7 @@ class LlamaModel:
 
     # ---- decode look-ahead: the host side of step k+1 runs while the GPU executes step k ---------------------------------
     def _prepare_next_decode(self, plan: BatchPlan, seq_ids_list: List[int], tokens_dev: torch.Tensor, sampling=None,
-                             processed: bool = False):
+                             processed: bool = False, scoring=None):
         """Called right after the graph of a pure-decode step was launched, before the host blocks on its tokens. A
         generation loop calls forward again with the same sequences, every length + 1 and the tokens just sampled: plan
         that step now (numpy) and enqueue — behind the running graph, on the same stream — the H2D copy of its metadata and
@@ -744,18 +786,20 @@ class LlamaModel:
         la.seq_ids, la.lens, la.plan, la.dev, la.tokens = list(seq_ids_list), next_lens, nxt, dev, None
         la.sampling = sampling      # (the parameter buffer keeps this step's rows: the next step may reuse it as it is)
         la.processed = processed    # (the entry buffer does NOT keep: a processed step uploads its entries on a hit too)
+        la.scoring = scoring        # (the logprob buffer keeps this step's N: the next step may reuse them as they are)
         return la
 
     def _take_lookahead(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
-                        processed: bool = False):
+                        processed: bool = False, scoring=None):
         """The prepared step, if this call is it (any other call drops the preparation). A sampled step hits only with
-        the per-row parameters (seeds resolved) of the step it was prepared after: those are still on the device."""
+        the per-row parameters (seeds resolved) of the step it was prepared after: those are still on the device. So does
+        a scored step: only with the rows' N of the step it was prepared after."""
         la, self._lookahead = self._lookahead, None
         if (la is None or la.tokens is None or ignore_kvcache or not self._decode_lookahead
                 or not getattr(self.engine_config, "use_hip_graph", False)
                 or len(input_ids_list) != len(la.lens) or list(decoding_seq_lens_list) != la.lens
                 or list(seq_ids_list) != la.seq_ids or sampling != getattr(la, "sampling", None)
-                or processed != getattr(la, "processed", False)):
+                or processed != getattr(la, "processed", False) or scoring != getattr(la, "scoring", None)):
             return None
         for ids, tok in zip(input_ids_list, la.tokens):
             if len(ids) != 1 or ids[0] != tok:
@@ -763,9 +807,18 @@ class LlamaModel:
         return la
 
     # ------------------------------------------------------------------------------------------------
-    def _tokens_to_host(self, tokens: torch.Tensor) -> List[int]:
+    def _tokens_to_host(self, tokens: torch.Tensor, scoring=None) -> List[int]:
         """The step's one D2H copy (and its one sync). A step of the persistent decode engine brings its error word back in
-        the same copy (DecodeEngine.tok_err = [token, error])."""
+        the same copy (DecodeEngine.tok_err = [token, error]). A scored step's results are copied into their pinned buffer
+        first, on the same stream: the tokens' sync covers them, and `last_logprobs` is read off that buffer afterwards."""
+        if scoring is None:
+            return self._sync_tokens(tokens)
+        self._score_out.copy_(self._score_dev[self._score_rows_cap:], non_blocking=True)
+        out = self._sync_tokens(tokens)
+        self.last_logprobs = token_scores.unpack(self._score_out_np, self._score_rows_cap, scoring)
+        return out
+
+    def _sync_tokens(self, tokens: torch.Tensor) -> List[int]:
         eng = self._engine
         if eng is not None and tokens.data_ptr() == eng.tok_err.data_ptr():
             vals = eng.tok_err.tolist()
@@ -784,6 +837,10 @@ class LlamaModel:
         sequence: greedy (the reference, model.py:252-359), or — for the entries of `sampling_params`
         (aligned with `input_ids_list`) that are not greedy — a seeded draw at the position the token
         takes (a None seed draws a fresh one for this call). All-greedy steps launch what they always did.
+        Entries whose `logprobs` is set make the step a scored one: `last_logprobs` then holds, aligned with the batch, a
+        TokenLogprob for each of them (the returned token's log-probability and rank, and its top-N alternatives, over
+        the logits the token was picked from) and None for the others; after any other step it is None. The tokens are
+        those of the same call without the field.
 
         `prefill_ctx_lens` (chunked prefill; one entry per prefill sequence): tokens of that sequence already resident
         in the KV pool from earlier calls. Its `input_ids` are then the next chunk of its prompt: the chunk is stored
@@ -794,18 +851,22 @@ class LlamaModel:
         `lora` (multi-LoRA serving; aligned with `input_ids_list`): the name of a loaded adapter, or None, per sequence.
         None or all None: today's call, launch for launch. Otherwise the step runs the LoRA layer path eagerly (no
         hipGraph, no look-ahead): every row of a named sequence gets its adapter's low-rank update on every projection."""
+        self.last_logprobs = None
         if len(input_ids_list) == 0:
             return []   # the reference's idle engine calls forward([], [], []) in a loop
         lora_slots = self._resolve_lora(lora, len(input_ids_list))
         _require_hip_device()
         prefill_ctx_lens = self._check_prefill_ctx(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache,
                                                    prefill_ctx_lens)
-        sampling = None
+        sampling = scoring = None
         if sampling_params is not None:
             if len(sampling_params) != len(input_ids_list):
                 raise ValueError("sampling_params must be aligned with input_ids_list")
             if not all(is_greedy(p) for p in sampling_params):
                 sampling = [None if is_greedy(p) else p.with_seed() for p in sampling_params]
+            # a scored step: the N of every row that asks for logprobs (SamplingParams.logprobs), None for the others
+            if not ignore_kvcache and any(p is not None and p.logprobs is not None for p in sampling_params):
+                scoring = [None if p is None else p.logprobs for p in sampling_params]
         # logits processing: the histories move ONCE per call, here (the engine fallback below runs the step twice)
         # (a step that raises — block allocation, the rotary table — takes its history updates back: the caller may repeat
         # the call, and the other sequences of the batch stay in step)
@@ -817,13 +878,13 @@ class LlamaModel:
         try:
             try:
                 return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                          prefill_ctx_lens, edits, lora_slots)
+                                          prefill_ctx_lens, edits, lora_slots, scoring)
             except _decode_engine.DecodeEngineError as exc:
                 # bounded hand-off timed out inside the persistent one-sequence step: its KV writes are re-done below with
                 # the same values by the multi-launch HIP path, which serves one-sequence steps from here on
                 self._engine_failed(int(str(exc)))
                 return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                          prefill_ctx_lens, edits, lora_slots)
+                                          prefill_ctx_lens, edits, lora_slots, scoring)
         except BaseException:
             self._rollback_histories(undo)
             raise
@@ -932,9 +993,10 @@ class LlamaModel:
                                    f"({rope_rows} positions)")
         return ctx
 
-    def _begin_step(self, plan: BatchPlan, seq_ids_list, ignore_kvcache: bool = False, sampling=None, edits=None):
+    def _begin_step(self, plan: BatchPlan, seq_ids_list, ignore_kvcache: bool = False, sampling=None, edits=None,
+                    scoring=None):
         """What every step does between its plan and its launches: the rotary-table check, KV blocks for the caller's
-        sequences, the plan's upload and — a sampled / processed step — its parameters' and entries'. Returns the plan's
+        sequences, the plan's upload and — a sampled / processed / scored step — its parameters', entries' and N's. Returns the plan's
         device views and the host times at which the checked plan and the blocks were ready (host_profile's sections)."""
         num_real = plan.num_real_seqs = len(seq_ids_list)
         longest = max(plan.seq_lengths_list)
@@ -952,28 +1014,32 @@ class LlamaModel:
             self._upload_sampling(sampling, plan.batch_size)
         if edits is not None:
             self._upload_edits(edits, plan.batch_size)
+        if scoring is not None:
+            self._upload_scoring(scoring, plan.batch_size)
         return dev, t_plan, t_blocks
 
     def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
-                      prefill_ctx_lens=None, edits=None, lora_slots=None):
+                      prefill_ctx_lens=None, edits=None, lora_slots=None, scoring=None):
         prof = self._host_prof
         t0 = time.perf_counter() if prof is not None else 0.0
         sampled = sampling is not None
         processed = edits is not None
+        scored = scoring is not None
         if lora_slots is not None:
             return self._forward_step_lora(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                           prefill_ctx_lens, edits, lora_slots)
-        la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling, processed)
+                                           prefill_ctx_lens, edits, lora_slots, scoring)
+        la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling, processed,
+                                  scoring)
         if la is not None:      # the step that was prepared while the previous one ran: blocks, then the launch
             self.gpu_block_manager.allocate_blocks_for_seqs(la.seq_ids, la.lens)   # (the real sequences only)
             if processed:       # (the entries change every step: they go up before every replay)
                 self._upload_edits(edits, la.plan.batch_size)
-            tokens = self._forward_decode_graph(la.plan, la.dev, sampled, processed)
-            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens, sampling, processed)
+            tokens = self._forward_decode_graph(la.plan, la.dev, sampled, processed, scored)
+            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens, sampling, processed, scoring)
             if self.after_launch_hook is not None:
                 self.after_launch_hook()
             t4 = time.perf_counter() if prof is not None else 0.0
-            out = self._tokens_to_host(tokens)
+            out = self._tokens_to_host(tokens, scoring)
             if nxt is not None:
                 nxt.tokens = out
             self._lookahead = nxt
@@ -991,32 +1057,33 @@ class LlamaModel:
         else:
             plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                               self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
-        dev, t1, t2 = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits)
+        dev, t1, t2 = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits, scoring)
         t3 = time.perf_counter() if prof is not None else 0.0
         pure_decode = plan.num_prefill_seqs == 0
         nxt = None
         if (pure_decode and not ignore_kvcache and getattr(self.engine_config, "use_hip_graph", False)):
-            tokens = self._forward_decode_graph(plan, dev, sampled, processed)
+            tokens = self._forward_decode_graph(plan, dev, sampled, processed, scored)
             if self._decode_lookahead:
-                nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens, sampling, processed)
+                nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens, sampling, processed, scoring)
         else:
             if pure_decode and not ignore_kvcache and self._eager_uses_graph_buckets:
                 plan.seq_block_size, plan.num_seq_blocks = self._graph_bucket(plan)
             tokens = self._forward(dev["input_ids"],
-                                   self._make_infer_state(plan, dev, ignore_kvcache, sampled, processed))[:num_real]
+                                   self._make_infer_state(plan, dev, ignore_kvcache, sampled, processed,
+                                                          scored=scored))[:num_real]
             tap = self.post_layer.logits_tap
             if tap and plan.batch_size > num_real:      # (tests) a padded eager step: the real rows only, as on replay
                 tap[-1] = tap[-1][:num_real]
         if self.after_launch_hook is not None:
             self.after_launch_hook()
         if prof is None:
-            out = self._tokens_to_host(tokens)
+            out = self._tokens_to_host(tokens, scoring)
             if nxt is not None:
                 nxt.tokens = out
             self._lookahead = nxt
             return out
         t4 = time.perf_counter()
-        out = self._tokens_to_host(tokens)
+        out = self._tokens_to_host(tokens, scoring)
         t5 = time.perf_counter()
         if nxt is not None:
             nxt.tokens = out
@@ -1027,17 +1094,18 @@ class LlamaModel:
         return out
 
     def _forward_step_lora(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                           prefill_ctx_lens, edits, lora_slots):
+                           prefill_ctx_lens, edits, lora_slots, scoring=None):
         """A step with at least one adapter row: the plain plan of the batch (never padded to a replay bucket), eager
         launches, the prepared look-ahead dropped; the row -> slot tiles go up in a buffer of their own."""
         self._lookahead = None
         num_real = len(input_ids_list)
         plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                           self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
-        dev = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits)[0]
+        dev = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits, scoring)[0]
         num_prefill = num_real - len(decoding_seq_lens_list)
         row_slots = rows_of_sequences(lora_slots, [len(ids) for ids in input_ids_list[:num_prefill]])
-        state = self._make_infer_state(plan, dev, ignore_kvcache, sampling is not None, edits is not None)
+        state = self._make_infer_state(plan, dev, ignore_kvcache, sampling is not None, edits is not None,
+                                       scored=scoring is not None)
         state.lora = LoraStep(LoraBatch(row_slots, self.lora_store.max_loras, self.device, self._lora_staging),
                               self.lora_store.layers)
         tokens = self._forward(dev["input_ids"], state)[:num_real]
@@ -1045,7 +1113,7 @@ class LlamaModel:
             self.after_launch_hook()
         if self._host_prof is not None:
             self._host_prof["calls"] = self._host_prof.get("calls", 0.0) + 1.0
-        return self._tokens_to_host(tokens)
+        return self._tokens_to_host(tokens, scoring)
 
     @torch.inference_mode()
     def forward_verify(self, input_ids_list: List[List[int]], seq_ids_list: List[int],
@@ -1059,7 +1127,9 @@ class LlamaModel:
 
         It is the chunked-prefill forward of the same arguments with three differences: the infer state is marked
         `verify`, attention is kernels/paged_attn.paged_attention_verify (the decode kernel's geometry, split over the
-        total lengths), and every row is a last token. Eager launches, no hipGraph."""
+        total lengths), and every row is a last token. Eager launches, no hipGraph. A verify step scores nothing:
+        `last_logprobs` is None afterwards."""
+        self.last_logprobs = None
         if len(input_ids_list) == 0:
             return []
         _require_hip_device()
