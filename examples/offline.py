@@ -3,7 +3,7 @@ examples/offline.py against this implementation: build the model, size the KV po
 prefill a few prompts in one batch, then decode greedily step by step.
 
     python examples/offline.py --model-path /path/to/llama [--dtype bfloat16] [--steps 20] [--speculative-ngram 3]
-                               [--logprobs 3]
+                               [--logprobs 3] [--guided-regex '[0-9]{4}-[0-9]{2}-[0-9]{2}']
 
 With a HuggingFace tokenizer in the model directory the prompts are text; otherwise (e.g. the random-init
 checkpoints written by oracle/synth.py) random token ids are used and ids are printed.
@@ -36,6 +36,10 @@ def main():
                          "adapters with the base model")
     ap.add_argument("--logprobs", type=int, default=None, metavar="N",
                     help="report every generated token's log-probability, rank and N most likely alternatives (0..20)")
+    ap.add_argument("--guided-regex", default=None, metavar="PATTERN",
+                    help="guided decoding: the bytes every prompt's output spells fullmatch this pattern (the byte-level "
+                         "subset of swiftllm_amd/guided/regex.py; needs tokenizer.json in --model-path); a sequence is "
+                         "printed up to the token that completes the pattern")
     args = ap.parse_args()
 
     cfg = swiftllm.EngineConfig(model_path=args.model_path, use_dummy=args.use_dummy, block_size=16,
@@ -43,7 +47,8 @@ def main():
                                 max_blocks_per_seq=2048, max_batch_size=16, max_tokens_in_batch=2048 * 16,
                                 dtype=args.dtype, use_hip_graph=True, kv_cache_dtype=args.kv_cache_dtype,
                                 speculative_ngram=args.speculative_ngram, max_loras=args.max_loras,
-                                max_lora_rank=args.max_lora_rank, lora_modules=args.lora)
+                                max_lora_rank=args.max_lora_rank, lora_modules=args.lora,
+                                guided_max_states=1024 if args.guided_regex is not None else 0)
     t0 = time.perf_counter()
     model = swiftllm.LlamaModel(cfg)
     model.load_weights()
@@ -70,24 +75,46 @@ def main():
     kw = {"lora": [names[i] if i < len(names) else None for i in seq_ids]} if names else {}
     if args.logprobs is not None:       # (no --logprobs: the call of always; last_logprobs is None then)
         kw["sampling_params"] = [swiftllm.SamplingParams(logprobs=args.logprobs)] * len(seq_ids)
-    outputs = [model.forward(input_ids, seq_ids, [], **kw)]
+    # --guided-regex: one cursor per sequence through one shared guide; the caller advances them with the returned tokens
+    # (no --guided-regex: the call of always). A sequence whose pattern is complete rides on unguided and is cut below.
+    cursors, done_at = None, {}
+    if args.guided_regex is not None:
+        from swiftllm_amd.guided import GuideCursor, guide_key
+        key = guide_key("regex", args.guided_regex)
+        cursors = [GuideCursor(model.guide_store.acquire(key)) for _ in seq_ids]
+
+    def step(ids, lens):
+        if cursors is None:
+            return model.forward(ids, seq_ids, lens, **kw)
+        guides = [None if i in done_at else c for i, c in enumerate(cursors)]
+        toks = model.forward(ids, seq_ids, lens, guides=guides, **kw)
+        for i, (c, t) in enumerate(zip(guides, toks)):
+            if c is not None:
+                c.advance(t)
+                if c.complete:
+                    done_at[i] = len(outputs) + 1
+        return toks
+    outputs = []
+    outputs.append(step(input_ids, []))
     scores = [model.last_logprobs]
     lens = [len(x) for x in input_ids]
     t0 = time.perf_counter()
     for _ in range(args.steps):
         lens = [n + 1 for n in lens]
-        outputs.append(model.forward([[t] for t in outputs[-1]], seq_ids, lens, **kw))
+        outputs.append(step([[t] for t in outputs[-1]], lens))
         scores.append(model.last_logprobs)
     dt = time.perf_counter() - t0
     print(f"{args.steps} decode steps x {len(seq_ids)} sequences: {dt / args.steps * 1e3:.2f} ms/step")
     for i in seq_ids:
-        toks = [step[i] for step in outputs]
+        toks = [out[i] for out in outputs][:done_at.get(i)]
         print(f"[{i}]", tokenizer.decode(toks, skip_special_tokens=True) if tokenizer else toks)
         if args.logprobs is not None:
-            for step in scores:
-                lp = step[i]
+            for scored in scores[:done_at.get(i)]:
+                lp = scored[i]
                 top = ", ".join(f"{t}: {v:.3f}" for t, v in lp.top)
                 print(f"      {lp.token_id}: {lp.logprob:.3f} (rank {lp.rank})" + (f"  top: {top}" if top else ""))
+    for c in cursors or ():
+        model.guide_store.release(c.guide)
     model.free_seqs_resources(seq_ids)
 
 

@@ -218,6 +218,31 @@ int swl_logits_adjust(void *x, int64_t num_rows, int32_t n, int64_t row_stride, 
 int swl_logprobs(float *lp, int32_t *ids, int32_t *rank, const void *x, int64_t num_rows, int32_t n, int64_t row_stride,
                  int32_t dtype, const int64_t *chosen, const int32_t *top_n, int32_t n_cap, swl_stream_t stream);
 
+/* ---- Guided decoding: per-state token bitmasks, built on the device and applied to the logits ------------------
+ * reference: none (post_layer.py:40 takes the argmax of the raw logits); this is an addition.
+ * masks is a pool [rows, words_per_row] int32: bit (t & 31) of word (t >> 5) of row row_base + s says whether token t
+ * may be picked in state s of a byte-level DFA trans[num_states, 256] (int32, -1 = dead; a value outside
+ * [0, num_states) counts as dead), accepting[num_states] (bytes, 0 / 1). Token t spells the bytes
+ * tok_bytes[tok_offsets[t] .. tok_offsets[t + 1]). Its bit is set when it is an end id (end_ids[num_end_ids]) and
+ * accepting[s], or when it is no end id, has at least one byte, and the walk from s over its bytes never meets a dead
+ * entry. Bits [vocab, 32 * words_per_row) are 0. Every word of rows [row_base, row_base + num_states) is written
+ * whatever the pool held, no word outside them; the caller owns the pool's size. words_per_row >= ceil(vocab / 32).
+ * No atomics: bit-reproducible. num_states == 0: SWL_OK, nothing read. num_states > 2^23 - 1, row_base + num_states
+ * > 2^31 - 1 or words_per_row > 2^26 - 9: SWL_ERR_UNSUPPORTED. The exact contract is in csrc/guided.hip. */
+int swl_guide_build_masks(int32_t *masks, int64_t row_base, int64_t num_states, int32_t words_per_row,
+                          const int32_t *trans, const uint8_t *accepting, const uint8_t *tok_bytes,
+                          const int32_t *tok_offsets, int32_t vocab, const int32_t *end_ids, int32_t num_end_ids,
+                          swl_stream_t stream);
+
+/* Row r of x[num_rows, n] (fp16 / bf16, row stride row_stride elements) with k = row_index[r]: k outside
+ * [0, num_mask_rows) leaves the row untouched; otherwise every element whose bit in row k of masks[num_mask_rows,
+ * words_per_row] is clear becomes -inf (0xfc00 / 0xff80), whatever it held, and every other element keeps its bits.
+ * In place, before swl_logits_adjust and the pickers. words_per_row * 32 >= n. x needs 2-byte alignment (16-byte accesses
+ * when x is 16-byte aligned and row_stride % 8 == 0). No scratch, no atomics. num_rows or num_mask_rows > 2^31 - 1:
+ * SWL_ERR_UNSUPPORTED. */
+int swl_logits_mask(void *x, int64_t num_rows, int32_t n, int64_t row_stride, int32_t dtype, const int32_t *masks,
+                    int64_t num_mask_rows, int32_t words_per_row, const int32_t *row_index, swl_stream_t stream);
+
 /* ---- Paged attention, decode (flash-decoding, "paged attention v2") --------------------------
  * reference: paged_attn.py:9-108 (phase 1), :111-149 (phase 2), launcher :152-222
  * q[Bd, H, D] (token stride q_tok_stride), o[Bd, H, D] (token stride o_tok_stride).

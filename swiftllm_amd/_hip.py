@@ -148,6 +148,10 @@ _SPECIAL = {
     # Per-token logprobs (csrc/logprobs.hip): an "int rc = f(...)" entry too, registered here for the same reason (its own
     # contract: tests/test_logprobs_abi.py, tests/test_gpu_logprobs.py).
     "swl_logprobs": ([_P, _P, _P, _P, _I64, _I32, _I64, _I32, _P, _P, _I32, _P], _I32),
+    # Guided decoding (csrc/guided.hip): the mask builder and the mask application, "int rc = f(...)" entries too,
+    # registered here for the same reason (their own contract: tests/test_guided_abi.py, tests/test_gpu_guided.py).
+    "swl_guide_build_masks": ([_P, _I64, _I64, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P], _I32),
+    "swl_logits_mask": ([_P, _I64, _I32, _I64, _I32, _P, _I64, _I32, _P, _P], _I32),
 }
 
 _lock = threading.Lock()

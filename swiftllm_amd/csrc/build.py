@@ -35,10 +35,11 @@ SOURCES = [
     "sampling.hip",
     "logits_adjust.hip",
     "logprobs.hip",
+    "guided.hip",
     "lora.hip",
     "decode_engine.hip",
 ]
-HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "decode_attn.h", "prefill_tile.h", "fp8_kv.h", "kv_store.h", "gemm_host.h", "logits_keys.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
+HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "decode_attn.h", "prefill_tile.h", "fp8_kv.h", "kv_store.h", "gemm_host.h", "logits_keys.h", "logits_bits.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
 LIB = os.path.join(HERE, "libswiftllm_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 ARCH = "gfx950"

@@ -26,27 +26,17 @@
 // the order anyway): no atomics, two launches on the same input agree bit for bit. VEC: 16-byte accesses (base 16-byte
 // aligned and row_stride % 8 == 0); otherwise 2-byte accesses. The row is read twice in phase 2; the second read comes
 // from L2 (256 KB per row at n = 128256).
+//
+// An element that is -inf when the kernel starts (a token the guide mask of csrc/guided.hip removed) is -inf when it ends:
+// every fp32 step above maps -inf to -inf (rep is finite and > 0, freq * count and pres are finite, bias is finite or
+// -inf), T(-inf) is -inf, and in phase 2 -inf - m < gap holds for any finite m.
 #include "swl_common.h"
+#include "logits_bits.h"
 
 namespace swl {
 
 constexpr int kAdjustThreads = 1024;
 constexpr int kAdjustWaves = kAdjustThreads / kWave;
-
-typedef uint16_t bits8_t __attribute__((ext_vector_type(8)));
-
-template <typename T>
-__device__ __forceinline__ float bits_to_f(uint16_t b) {
-    if constexpr (std::is_same<T, f16>::value)
-        return static_cast<float>(__builtin_bit_cast(f16, b));
-    else
-        return __uint_as_float(static_cast<uint32_t>(b) << 16);
-}
-
-template <typename T>
-__device__ __forceinline__ constexpr uint16_t neg_inf_bits() {
-    return std::is_same<T, f16>::value ? 0xfc00u : 0xff80u;
-}
 
 template <typename T, bool VEC>
 __global__ __launch_bounds__(kAdjustThreads) void logits_adjust_kernel(

@@ -81,6 +81,13 @@ class EngineConfig:
     max_loras: int = 0
     max_lora_rank: int = 16
     lora_modules: list = None
+    # Guided decoding (swiftllm_amd/guided, csrc/guided.hip): rows of the device pool of per-state
+    # token bitmasks, one row (ceil(vocab / 32) int32 words: 16 KiB at Llama-3's vocabulary) per DFA state of a resident
+    # guide. 0 (default): off — no pool, no new code path, and a guided request is answered with an error. > 0: load_weights
+    # allocates the pool and the vocabulary's flat device form (from model_path/tokenizer.json, or
+    # LlamaModel.set_guide_vocab) before the KV pool is sized; a request may then be held to a regex, a choice or a set of
+    # token ids (SamplingParams.guided_regex / guided_choice / allowed_token_ids).
+    guided_max_states: int = 0
     # Prefix caching by KV block copy (server/prefix_cache.py, csrc/kv_copy.hip). False (default):
     # off — every step launches what it always did. True: a finished request keeps its block-table row and its blocks as a
     # cache entry (reclaimed, least recently used first, whenever the scheduler needs the blocks, a row or an entry slot); a
@@ -162,6 +169,8 @@ class EngineConfig:
                 raise ValueError(f"lora_modules names an adapter twice: {names}")
             if len(names) > int(self.max_loras):
                 raise ValueError(f"lora_modules names {len(names)} adapters, max_loras is {self.max_loras}")
+        if isinstance(self.guided_max_states, bool) or int(self.guided_max_states) < 0:
+            raise ValueError(f"guided_max_states must be an integer >= 0 (0 = off), got {self.guided_max_states!r}")
         if self.enable_prefix_caching:
             if int(self.max_prefill_chunk) == 0:
                 raise ValueError("enable_prefix_caching needs max_prefill_chunk > 0: a prompt that reuses a cached prefix "
@@ -240,3 +249,6 @@ class EngineConfig:
                             "prompts with the same leading tokens (needs --max-prefill-chunk > 0)")
         g.add_argument("--prefix-cache-max-seqs", type=int, default=256,
                        help="Block-table rows the prefix cache may hold (below --max-seqs-in-block-table)")
+        g.add_argument("--guided-max-states", type=int, default=0,
+                       help="Guided decoding: rows of the device pool of per-state token bitmasks (0 = off); needs "
+                            "tokenizer.json in --model-path")

@@ -16,6 +16,16 @@ stop tokens cannot be picked.
 tokens at its position (csrc/logprobs.hip has the contract): the model's distribution at temperature 1 over the logits
 as they stand when the token is picked — after the edits above, before temperature / top-k / top-p, which do not
 renormalise it. It changes no token.
+
+`guided_regex`, `guided_choice` and `allowed_token_ids` (at most one of them) hold the output to a shape: the bytes the
+generated tokens spell fullmatch the regex (the byte-level subset of swiftllm_amd/guided/regex.py), are one of the choices,
+or every token is one of the ids. Before anything else reads the logits, the tokens the request's state does not allow
+become -inf (csrc/guided.hip), so min-p, the pickers and logprobs see the allowed tokens only. The request's
+`stop_token_ids` are its end ids: allowed exactly where the text so far is a full match. A regex / choice request ends at
+such a stop token, or — without one — as soon as nothing can follow (its last token is delivered); one that reaches
+`output_len` first is cut where it stands, mid-pattern; one whose guide reaches a state in which the vocabulary offers no
+token (no token spells the bytes needed there, or only a stop id does) ends there with an error. `min_tokens` cannot be combined with a guide: a state in which
+only the end ids are left would have nothing to pick.
 """
 import dataclasses
 import math
@@ -47,6 +57,9 @@ class SamplingParams:
     stop_token_ids: Tuple[int, ...] = ()
     min_tokens: int = 0                 # stop tokens are banned while fewer output tokens exist
     logprobs: Optional[int] = None      # None: off; N in 0..20: every generated token reports itself and its top N
+    guided_regex: Optional[str] = None                  # the output's bytes fullmatch this pattern
+    guided_choice: Optional[Tuple[str, ...]] = None     # ... or are one of these strings
+    allowed_token_ids: Optional[Tuple[int, ...]] = None     # ... or every token is one of these ids; stored sorted, unique
 
     def __post_init__(self):
         self._check_sampling()
@@ -54,6 +67,34 @@ class SamplingParams:
         n = self.logprobs
         if n is not None and (isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= MAX_LOGPROBS):
             raise ValueError(f"logprobs must be None or an integer in [0, {MAX_LOGPROBS}], got {n!r}")
+        self._check_guided()
+
+    def _check_guided(self):
+        """Shapes only: the pattern itself is compiled when the request is submitted (swiftllm_amd/guided)."""
+        r, c, a = self.guided_regex, self.guided_choice, self.allowed_token_ids
+        if sum(v is not None for v in (r, c, a)) > 1:
+            raise ValueError("at most one of guided_regex, guided_choice and allowed_token_ids may be set")
+        if r is not None and not isinstance(r, str):
+            raise ValueError(f"guided_regex must be a string, got {r!r}")
+        if c is not None:
+            if isinstance(c, (str, bytes)) or not hasattr(c, "__iter__"):
+                raise ValueError(f"guided_choice must be a sequence of strings, got {c!r}")
+            c = tuple(c)
+            if not c or any(not isinstance(s, str) or s == "" for s in c):
+                raise ValueError(f"guided_choice must name at least one choice, each a non-empty string, got {c!r}")
+            if len(set(c)) != len(c):
+                raise ValueError(f"guided_choice names a choice twice: {c!r}")
+            object.__setattr__(self, "guided_choice", c)
+        if a is not None:
+            if isinstance(a, (str, bytes)) or not hasattr(a, "__iter__"):
+                raise ValueError(f"allowed_token_ids must be a sequence of integers, got {a!r}")
+            a = tuple(a)
+            if not a or any(isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < 2 ** 31 for t in a):
+                raise ValueError(f"allowed_token_ids must name at least one integer in [0, 2**31), got {a!r}")
+            object.__setattr__(self, "allowed_token_ids", tuple(sorted(set(a))))
+        if self.guided and self.min_tokens > 0:
+            raise ValueError("min_tokens > 0 cannot be combined with a guide: a state in which only the end ids are allowed "
+                             "would have nothing left to pick")
 
     def _check_processing(self):
         def number(v):
@@ -128,9 +169,26 @@ class SamplingParams:
                 or (self.min_tokens > 0 and bool(self.stop_token_ids)))
 
     @property
+    def guided(self) -> bool:
+        """The output is held to a regex, a choice or a set of token ids (it needs no token history: `processes_logits`
+        does not depend on it)."""
+        return self.guided_regex is not None or self.guided_choice is not None or self.allowed_token_ids is not None
+
+    def guide_spec(self):
+        """(kind, spec) for swiftllm_amd.guided.guide_key, or None."""
+        if self.guided_regex is not None:
+            return "regex", self.guided_regex
+        if self.guided_choice is not None:
+            return "choice", self.guided_choice
+        if self.allowed_token_ids is not None:
+            return "tokens", self.allowed_token_ids
+        return None
+
+    @property
     def plain(self) -> bool:
         """Nothing to do beyond the argmax of the raw logits, run to output_len: what None means."""
-        return self.greedy and not self.processes_logits and not self.stop_token_ids and self.logprobs is None
+        return (self.greedy and not self.processes_logits and not self.stop_token_ids and self.logprobs is None
+                and not self.guided)
 
     def min_p_gap(self) -> float:
         """What the kernel compares x_i - max(x) with: T * ln(min_p), computed in double precision (the caller rounds it

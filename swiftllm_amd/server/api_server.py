@@ -8,6 +8,11 @@ top_k, top_p, seed; repetition_penalty, presence_penalty, frequency_penalty, min
 stop_token_ids, min_tokens; absent = greedy to output_len, as in the reference) and "lora": the name of a loaded LoRA
 adapter (--max-loras / --lora NAME=PATH; absent = the base model): non-streaming answers
 {"output_token_ids": [...]} (or {"output": text} with decode), streaming sends one line per token.
+"guided_regex": pattern, "guided_choice": [strings] or "allowed_token_ids": [ids] (at most one; --guided-max-states > 0)
+hold the output to a shape: its bytes fullmatch the pattern (the byte-level subset of swiftllm_amd/guided/regex.py), are one
+of the choices, or every token is one of the ids; "stop_token_ids" are the guide's end ids. A pattern outside the subset is
+answered with 400, a guide store whose rows are all held by live requests with 503; a request whose guide reaches a state
+in which no token is allowed ends with {"error": ...} (400) as well.
 "logprobs": N (0..20) asks for every generated token's log-probability, rank and N most likely alternatives: the
 non-streaming answer gains "logprobs": [{"token_id", "logprob", "rank", "top": [[id, logprob], ...]}, ...] and a stream
 sends one such JSON object per line (with "text" under decode); values that are not finite are sent as null.
@@ -115,23 +120,43 @@ def _validate_sampling(body) -> "str | None":
     lp = body.get("logprobs")
     if lp is not None and (not _is_int(lp) or not 0 <= lp <= MAX_LOGPROBS):
         return f"logprobs must be an integer in [0, {MAX_LOGPROBS}]"
+    if sum(body.get(f) is not None for f in _GUIDED_FIELDS) > 1:
+        return "at most one of guided_regex, guided_choice and allowed_token_ids may be set"
+    g = body.get("guided_regex")
+    if g is not None and not isinstance(g, str):
+        return "guided_regex must be a string"
+    g = body.get("guided_choice")
+    if g is not None and (not isinstance(g, list) or not g or not all(isinstance(c, str) and c for c in g)
+                          or len(set(g)) != len(g)):
+        return "guided_choice must be a non-empty list of distinct non-empty strings"
+    g = body.get("allowed_token_ids")
+    if g is not None and (not isinstance(g, list) or not g or not all(_is_int(t) and 0 <= t < 2 ** 31 for t in g)):
+        return "allowed_token_ids must be a non-empty list of integers >= 0"
+    if any(body.get(f) is not None for f in _GUIDED_FIELDS) and (n or 0) > 0:
+        return "min_tokens cannot be combined with guided_regex, guided_choice or allowed_token_ids"
     return None
 
 
 _SAMPLING_FIELDS = ("temperature", "top_k", "top_p", "seed")
+_GUIDED_FIELDS = ("guided_regex", "guided_choice", "allowed_token_ids")
 _PROCESSING_FIELDS = ("repetition_penalty", "presence_penalty", "frequency_penalty", "min_p", "logit_bias",
                       "stop_token_ids", "min_tokens")
 
 
 def _sampling_params(body) -> "SamplingParams | None":
-    if all(body.get(f) is None for f in _SAMPLING_FIELDS + _PROCESSING_FIELDS + ("logprobs",)):
+    if all(body.get(f) is None for f in _SAMPLING_FIELDS + _PROCESSING_FIELDS + ("logprobs",) + _GUIDED_FIELDS):
         return None
     kw = {}
+    if any(body.get(f) is not None for f in _GUIDED_FIELDS):            # (none of them: the params of always)
+        choice, allowed = body.get("guided_choice"), body.get("allowed_token_ids")
+        kw = dict(guided_regex=body.get("guided_regex"), guided_choice=tuple(choice) if choice is not None else None,
+                  allowed_token_ids=tuple(allowed) if allowed is not None else None,
+                  stop_token_ids=tuple(body.get("stop_token_ids") or ()))
     if any(body.get(f) is not None for f in _PROCESSING_FIELDS):       # (none of them: the params of always)
         def num(name, default):
             return float(body[name]) if body.get(name) is not None else default
         bias = body.get("logit_bias")
-        kw = dict(repetition_penalty=num("repetition_penalty", 1.0), presence_penalty=num("presence_penalty", 0.0),
+        kw.update(repetition_penalty=num("repetition_penalty", 1.0), presence_penalty=num("presence_penalty", 0.0),
                   frequency_penalty=num("frequency_penalty", 0.0), min_p=num("min_p", 0.0),
                   logit_bias={int(k): float(v) for k, v in bias.items()} if bias else None,
                   stop_token_ids=tuple(body.get("stop_token_ids") or ()), min_tokens=int(body.get("min_tokens") or 0))
@@ -194,7 +219,8 @@ def build_app(engine: Engine) -> fastapi.FastAPI:
             # a request the engine can never serve is the client's error (400); an engine whose model thread is gone is
             # the server's (503: a router in front retries on another replica)
             dead = getattr(engine, "_dead", None) is not None and request.error == engine._dead
-            return JSONResponse({"error": request.error}, status_code=503 if dead else 400)
+            retry = dead or getattr(request, "error_retryable", False)      # (a full guide store passes: try again later)
+            return JSONResponse({"error": request.error}, status_code=503 if retry else 400)
         answer = ({"output": await engine.tokenization_engine.decode(token_ids)} if want_text else
                   {"output_token_ids": token_ids})
         if want_logprobs:

@@ -22,6 +22,7 @@ import threading
 from typing import AsyncGenerator, List, Optional, Tuple
 
 from swiftllm_amd.engine_config import EngineConfig
+from swiftllm_amd.guided import GuideCursor, GuideStoreFull, GuideViolation, guide_key
 from swiftllm_amd.model_config import LlamaModelConfig
 from swiftllm_amd.utils import GB
 
@@ -199,12 +200,47 @@ class Engine:
     def _retire(self, finished: List[Request]):
         """Requests that finished in this step, before anyone is told: an eligible one's row becomes a prefix-cache entry
         (it keeps its KV blocks), the others — and the entries that made room — are released as always."""
+        for r in finished:
+            self._release_guide(r)
         free = [r.request_id for r in finished if not self.scheduler.retire(r)]
         evicted, _ = self.scheduler.take_cache_work()
         self.num_prefix_evictions += len(evicted)
         if free or evicted:
             # release KV blocks before anyone is told: a caller that sees "finished" may tear us down
             self.model.free_seqs_resources(free + evicted)
+
+    # ---- guided decoding ------------------------------------------------------------------------------------------------
+    def _acquire_guide(self, req: Request):
+        """Compile (cached) and make resident the guide of a guided request, and give the request its cursor. Runs in an
+        executor of the event loop, like tokenisation, never on the model thread; whatever is wrong with the guide is the
+        request's `error` (a full store: a retryable one), never an exception."""
+        sp = req.sampling_params
+        store = getattr(self.model, "guide_store", None)
+        if store is None:
+            req.error = "guided decoding is off: the engine was started with guided_max_states = 0"
+            return
+        try:
+            kind, spec = sp.guide_spec()
+            req.guide_cursor = GuideCursor(store.acquire(guide_key(kind, spec, sp.stop_token_ids)))
+        except GuideStoreFull as exc:
+            req.error, req.error_retryable = f"guided decoding: {exc}", True
+        except Exception as exc:     # noqa: BLE001 — GuideSyntaxError, an oversized NFA / DFA, ids outside the vocabulary,
+            # a pattern nested too deeply to parse ... whatever it is, it is this request's answer: the submission loop
+            # serves every other request and must survive it
+            what = str(exc) if isinstance(exc, ValueError) else f"{type(exc).__name__}: {exc}"
+            req.error = f"guided decoding: {what}"
+
+    def _acquire_guides(self, requests: List[Request]):
+        """One executor job for the guided requests of one batch of arrivals, in arrival order."""
+        for req in requests:
+            self._acquire_guide(req)
+
+    def _release_guide(self, req: Request):
+        """Drop the request's reference on its guide (finished, failed or refused after it was acquired); once only."""
+        cur = req.guide_cursor
+        if cur is not None and not cur.released:
+            cur.released = True
+            self.model.guide_store.release(cur.guide)
 
     # ---- asyncio side -------------------------------------------------------------------------------------------
     async def _tokenize_raw_request_event_loop(self):
@@ -219,23 +255,30 @@ class Engine:
                 for (req, _), token_ids in zip(texts, ids):
                     req.prompt_token_ids = list(token_ids)
                     req.prompt_len = len(token_ids)
-            servable = []
+            servable, guided = [], []
             for req, _ in pending:
                 req.error = self._dead or self.scheduler.why_unservable(req)      # (reads the engine's limits only)
-                if req.error is None:
+                if req.error is None and req.sampling_params is not None and req.sampling_params.guided:
+                    guided.append(req)      # (its guide is compiled and acquired below, off the event loop)
+                elif req.error is None:
                     servable.append(req)
                 else:           # answer at once: waiters wake up with no tokens, streams end
-                    self._live.discard(req)
-                    req.finished_event.set()
-                    req.output_q.put_nowait(None)
-            if servable:
+                    self._reject([req])
+            if servable:        # the requests without a guide do not wait for anybody's compile
                 self._inbox.put(servable)
+            if guided:
+                await self.event_loop.run_in_executor(None, self._acquire_guides, guided)
+                self._reject([r for r in guided if r.error is not None])
+                servable = [r for r in guided if r.error is None]
+                if servable:
+                    self._inbox.put(servable)
             await asyncio.sleep(0.001)
 
     def _deliver(self, outputs: List[Tuple[Request, int, bool, object]]):
         """Fan one step's tokens out to the per-request queues and events (event-loop thread)."""
         for req, tok, finished, lp in outputs:
-            req.output_q.put_nowait(StepOutput(tok, req, lp))
+            if tok is not None:         # (None: a request the engine ended with an error — no token, only the end)
+                req.output_q.put_nowait(StepOutput(tok, req, lp))
             if finished:
                 self._live.discard(req)
                 req.finished_event.set()
@@ -249,6 +292,7 @@ class Engine:
         live, self._live = list(self._live), set()
         pending, self.untokenized_raw_requests = self.untokenized_raw_requests, []
         for req in live + [r for r, _ in pending]:
+            self._release_guide(req)
             req.error = req.error or why
             req.finished_event.set()
             req.output_q.put_nowait(None)
@@ -292,6 +336,7 @@ class Engine:
             item = [r for r in item if r not in gone]
             for r in gone:
                 r.error = f"LoRA adapter {r.lora!r} is not loaded"
+                self._release_guide(r)
             try:
                 self.event_loop.call_soon_threadsafe(self._reject, gone)
             except RuntimeError:        # the event loop is gone (shutdown)
@@ -351,6 +396,8 @@ class Engine:
                 kwargs["prefill_ctx_lens"] = [r.num_prefilled for r in prefills]
             if any(r.lora is not None for r in batch):      # (no adapter in the batch: the call of always)
                 kwargs["lora"] = [r.lora for r in batch]
+            if any(r.guide_cursor is not None for r in batch):      # (no guided request in the batch: the call of always)
+                kwargs["guides"] = [r.guide_cursor for r in batch]
             try:
                 tokens = self.model.forward(input_ids, seq_ids, decoding_lens, **kwargs)
             finally:
@@ -368,6 +415,19 @@ class Engine:
                     req.prefill_take = 0
                     if req.num_prefilled < req.prompt_len:
                         continue        # not the last chunk: its token (and its logprobs) discarded — nothing appended, nothing delivered
+                                        # (and a guided request's cursor stays where it is)
+                if req.guide_cursor is not None:
+                    try:
+                        req.guide_cursor.advance(tok)       # (is_finished below reads the state the token led to)
+                    except GuideViolation as exc:
+                        # the state allows no token at all (the picker's answer to an all -inf row is not allowed either):
+                        # the vocabulary cannot spell what the guide needs here. This request ends with an error; the
+                        # others of the batch go on. Its token is not delivered.
+                        req.error = f"guided decoding: no token is allowed after {bytes(req.guide_cursor.text)!r}: {exc}"
+                        req.aborted = True
+                        outputs.append((req, None, True, None))
+                        finished.append(req)
+                        continue
                 req.output_token_ids.append(tok)
                 lp = None
                 if scores is not None and sampling[i] is not None and sampling[i].logprobs is not None:

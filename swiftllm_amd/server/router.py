@@ -142,7 +142,15 @@ def main():
     ap.add_argument("--max-lora-rank", type=int, default=None, choices=[8, 16, 32, 64])
     ap.add_argument("--lora", action="append", default=None, metavar="NAME=PATH",
                     help="a PEFT adapter directory every replica loads at start-up (repeatable)")
+    # guided decoding: every replica keeps a mask pool of this many rows (a request's "guided_regex", "guided_choice" and
+    # "allowed_token_ids" fields are relayed like every field)
+    ap.add_argument("--guided-max-states", type=int, default=None,
+                    help="rows of every replica's guide mask pool (api_server --guided-max-states; 0 = off)")
     args, passthrough = ap.parse_known_args()
+    if args.guided_max_states is not None:
+        if args.guided_max_states < 0:
+            raise SystemExit("--guided-max-states must be >= 0")
+        passthrough = list(passthrough) + ["--guided-max-states", str(args.guided_max_states)]
     if args.kv_cache_dtype is not None:
         passthrough = list(passthrough) + ["--kv-cache-dtype", args.kv_cache_dtype]
     passthrough = list(passthrough) + lora_passthrough(args.max_loras, args.max_lora_rank, args.lora)

@@ -44,6 +44,13 @@ class Request:
         # one TokenLogprob per output token, for a request whose sampling params ask for logprobs (empty otherwise)
         self.output_logprobs: List[TokenLogprob] = []
         self.error: Optional[str] = None    # set instead of scheduling when the request can never be served
+        self.error_retryable = False        # ... for a reason that passes (a full guide store): HTTP 503 instead of 400
+        self.aborted = False                # ended by the engine with `error` set after it had started: finished, whatever
+                                            # it has generated (a guide that ran into a state in which no token is allowed)
+        # guided decoding: the request's cursor through its guide (swiftllm_amd.guided.GuideCursor over a guide acquired when
+        # the request was submitted; the engine advances it with every delivered token and releases the guide when the
+        # request retires); None = not guided. Such a request is never speculated (its sampling params are not None)
+        self.guide_cursor = None
         # multi-LoRA serving: the adapter every step of this request runs with (None = the base model); such a request is
         # never speculated
         self.lora: Optional[str] = getattr(raw_request, "lora", None)
@@ -74,9 +81,14 @@ class Request:
 
     def is_finished(self) -> bool:
         out = self.output_token_ids
-        if len(out) >= self.output_len:
+        if self.aborted or len(out) >= self.output_len:
             return True
-        return bool(self._stop_ids) and len(out) > self._min_tokens and out[-1] in self._stop_ids
+        if bool(self._stop_ids) and len(out) > self._min_tokens and out[-1] in self._stop_ids:
+            return True
+        # a guided request also ends once nothing can follow what it has generated (its last token was delivered); one that
+        # reaches output_len first is cut where it stands
+        cur = self.guide_cursor
+        return cur is not None and bool(out) and cur.complete
 
     def get_cur_output_len(self) -> int:
         return len(self.output_token_ids)

@@ -54,6 +54,10 @@ class LlamaInferState:
     # A scored step (some row asks for logprobs): kernels/logprobs.LogprobArgs over the model's persistent buffer; the post
     # layer scores the picked tokens against the logits they were picked from. None: no such row, no launch.
     logprobs: Optional[object] = None
+    # A guided step (some row's request is held to a regex, a choice or a token set): kernels/guided.GuideArgs over the
+    # model's mask pool and its persistent row-index buffer; the post layer masks the logits before anything else reads
+    # them. None: no such row, no launch.
+    guide: Optional[object] = None
     # Chunked prefill: tokens of each prefill sequence already resident in the pool (int32 [num_prefill_seqs]); its new
     # tokens take logical positions [ctx, ctx + len) and attend to the pool (kernels/prefill_attn.prefill_attention_paged).
     # None: every prompt starts at position 0 and attends to its fresh projections — the reference's prefill.

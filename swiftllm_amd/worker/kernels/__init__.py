@@ -4,7 +4,8 @@ One module per module of the reference's swiftllm/worker/kernels, exporting func
 names and argument meaning; each one validates its tensors (the reference's asserts), then calls the
 gfx950 kernel through the C ABI (swiftllm_amd._hip). `swap_blocks` (reference: the swiftllm_c
 extension) lives in block_swapping.py; `kv_copy_blocks` (an addition: KV block copies inside the GPU pools) in kv_copy.py;
-`token_logprobs` (an addition: log-probabilities of the picked tokens and their top-N alternatives) in logprobs.py.
+`token_logprobs` (an addition: log-probabilities of the picked tokens and their top-N alternatives) in logprobs.py;
+`build_guide_masks` / `mask_logits` (an addition: guided decoding's token bitmasks) in guided.py.
 """
 from .linear import linear
 from .rmsnorm import rmsnorm_inplace, fused_add_rmsnorm_inplace
@@ -21,10 +22,12 @@ from .block_mgmt import (
 from .block_swapping import swap_blocks
 from .kv_copy import kv_copy_blocks
 from .logprobs import token_logprobs
+from .guided import build_guide_masks, mask_logits
 
 __all__ = [
     "linear", "rmsnorm_inplace", "fused_add_rmsnorm_inplace", "rotary_embedding_inplace",
     "store_kvcache", "prefill_attention", "prefill_attention_paged", "paged_attention", "silu_and_mul_inplace",
     "set_block_table_and_num_seq_alloc_blocks", "unset_block_table_and_num_seq_alloc_blocks",
     "gather_allocated_blocks_and_unset", "swap_blocks", "kv_copy_blocks", "token_logprobs",
+    "build_guide_masks", "mask_logits",
 ]

@@ -29,6 +29,7 @@ import torch
 
 from swiftllm_amd import _hip
 from swiftllm_amd.engine_config import EngineConfig
+from swiftllm_amd.guided import GuideStore, TokenVocab
 from swiftllm_amd.model_config import LlamaModelConfig
 from swiftllm_amd.sampling_params import SamplingParams, is_greedy
 from swiftllm_amd.utils import GB
@@ -44,6 +45,7 @@ from .kernels.paged_attn import verify_max_tokens
 from .kernels.rmsnorm import fused_add_rmsnorm_from_splitk, rmsnorm_inplace
 from .kernels import logits_process
 from .kernels import logprobs as token_scores
+from .kernels import guided as guide_kernels
 from .kernels.sampling import device_args, pack_params
 from .lora import LoraBatch, LoraStaging, LoraStep, LoraStore, parse_lora_modules, rows_of_sequences
 from .layers.pre_layer import LlamaPreLayer
@@ -71,7 +73,7 @@ class _DecodeGraph:
 
 class _DecodeLookahead:
     """Everything the NEXT decode step of the same batch needs, prepared while the GPU was still busy with this one."""
-    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev", "sampling", "processed", "scoring")
+    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev", "sampling", "processed", "scoring", "guided")
 
 
 class LlamaModel:
@@ -144,6 +146,15 @@ class LlamaModel:
         # what the last forward / forward_verify call learnt about its tokens: None when no row asked, else one
         # TokenLogprob or None per sequence of the batch
         self.last_logprobs = None
+        # guided decoding (swiftllm_amd/guided, kernels/guided.py; EngineConfig.guided_max_states > 0): the host bookkeeping
+        # of the mask pool (GuideStore; None = off), the pool itself (int32 [guided_max_states, ceil(vocab / 32)]), the
+        # vocabulary's flat device form the build kernel walks, and the step's mask row per row of logits: pinned staging +
+        # its device twin (fixed address: a guided hipGraph reads it on every replay; uploaded before every guided step,
+        # look-ahead hits included — the rows move with every token)
+        self.guide_store = None
+        self._guide_vocab = self._guide_vocab_dev = self._guide_masks = None
+        self._guide_host = self._guide_host_np = self._guide_dev = self._guide_done = None
+        self._guide_rows_cap = 0
         # speculative decoding: drafts one verify step takes per sequence (forward_verify) = the verify attention kernel's
         # tokens per sequence (16 / G) minus the last accepted token that leads them; 0 with FP8 pools (no instantiation)
         self.max_draft_tokens = 0 if self.kv_fp8 else max(0, verify_max_tokens(self.model_config) - 1)
@@ -182,6 +193,9 @@ class LlamaModel:
         self._ensure_sampling_rows(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
         self._ensure_edit_buffer(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)), 0)
         self._ensure_score_rows(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
+        # (... and so are the guide mask pool and the vocabulary's device form, when guided decoding is on)
+        if int(getattr(ecfg, "guided_max_states", 0) or 0) > 0:
+            self._init_guided(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
         # (... and so are the adapter slot stacks: the KV pool is sized with them)
         if int(getattr(ecfg, "max_loras", 0) or 0) > 0:
             self.lora_store = LoraStore(self.model_config, int(ecfg.max_loras), int(ecfg.max_lora_rank), self.dtype,
@@ -190,6 +204,103 @@ class LlamaModel:
                   f"{self.lora_store.nbytes() / 2**20:.1f} MiB", flush=True)
             for name, path in parse_lora_modules(getattr(ecfg, "lora_modules", None)).items():
                 self.load_lora(name, path)
+
+    # ---- guided decoding ---------------------------------------------------------------------------------------------
+    def set_guide_vocab(self, vocab: TokenVocab):
+        """The bytes every token id spells, for models without a tokenizer.json (dummy checkpoints, tests): call it before
+        load_weights, or afterwards while no guide is resident. It must spell exactly the model's vocab_size ids."""
+        if not isinstance(vocab, TokenVocab):
+            raise TypeError("set_guide_vocab takes a swiftllm_amd.guided.TokenVocab")
+        if len(vocab) != self.model_config.vocab_size:
+            raise ValueError(f"the guide vocabulary spells {len(vocab)} ids, the model's vocabulary has "
+                             f"{self.model_config.vocab_size}")
+        if self.guide_store is not None:
+            if self.guide_store.resident():
+                raise RuntimeError("set_guide_vocab while guides are resident: their masks were built from the old vocabulary")
+            self._guide_vocab_dev = guide_kernels.upload_vocab(vocab, self.model_config.vocab_size, self.device)
+            self.guide_store.vocab = vocab
+        self._guide_vocab = vocab
+
+    def _init_guided(self, rows: int):
+        """The mask pool, the vocabulary's device form and the row-index buffer. A missing vocabulary is an error here, at
+        start-up, not at the first guided request."""
+        ecfg, vocab_size = self.engine_config, self.model_config.vocab_size
+        if self._guide_vocab is None:
+            path = os.path.join(str(ecfg.model_path), "tokenizer.json")
+            if not os.path.exists(path):
+                raise RuntimeError(f"guided_max_states = {ecfg.guided_max_states} but there is no vocabulary: {path} does not "
+                                   "exist and LlamaModel.set_guide_vocab was not called")
+            self._guide_vocab = TokenVocab.from_tokenizer_json(path, vocab_size)
+        self._guide_vocab_dev = guide_kernels.upload_vocab(self._guide_vocab, vocab_size, self.device)
+        self.guide_store = GuideStore(int(ecfg.guided_max_states), vocab_size, self._guide_vocab)
+        self._guide_masks = torch.zeros((self.guide_store.max_states, self.guide_store.words), dtype=torch.int32,
+                                        device=self.device)
+        self._ensure_guide_rows(rows)
+        print(f"[Model] guided decoding: {self.guide_store.max_states} mask rows, "
+              f"{self._guide_masks.numel() * 4 / 2**20:.1f} MiB", flush=True)
+
+    def _ensure_guide_rows(self, rows: int):
+        """The persistent row-index buffer holds `rows` rows. Growing it moves it: the graphs captured against the old one
+        are dropped."""
+        if self._guide_rows_cap >= rows:
+            return
+        cap = max(rows, 2 * self._guide_rows_cap)
+        self._guide_host = torch.empty(cap, dtype=torch.int32, pin_memory=True)
+        self._guide_host_np = self._guide_host.numpy()
+        self._guide_dev = torch.full((cap,), -1, dtype=torch.int32, device=self.device)     # (no row is guided)
+        self._guide_done = torch.cuda.Event()
+        self._guide_rows_cap = cap
+        self._drop_decode_graphs()     # captured guided graphs point into the old buffer
+
+    def _build_guide(self, guide):
+        """Fill the guide's rows of the pool, on the current stream: behind every earlier step that may still read the rows
+        of a guide evicted for it. A DFA guide: one launch of the build kernel; an allowed-token guide: its one row, written
+        by the host."""
+        if guide.dfa is None:
+            self._guide_masks[guide.base].copy_(torch.from_numpy(guide.host_mask_row(self.guide_store.words)))
+        else:
+            vocab_size = self.model_config.vocab_size
+            ends = [t for t in guide.end_ids if t < vocab_size]
+            guide_kernels.build_guide_masks(
+                self._guide_masks, guide.base, torch.from_numpy(guide.dfa.trans).to(self.device),
+                torch.from_numpy(guide.dfa.accepting.view(np.uint8)).to(self.device), self._guide_vocab_dev,
+                torch.tensor(ends, dtype=torch.int32, device=self.device) if ends else None)
+        guide.built = True
+
+    def _upload_guides(self, guides, rows: int):
+        """Build what is not built yet, then one async H2D copy of the step's mask row per row (unguided rows, padded
+        bucket rows and everything past them: -1)."""
+        for c in guides:
+            if c is not None and not c.guide.built:
+                self._build_guide(c.guide)
+        self._ensure_guide_rows(rows)
+        self._guide_done.synchronize()     # (the previous step's copy out of the pinned buffer: long done)
+        guide_kernels.pack_rows(guides, self._guide_host_np)
+        self._guide_dev.copy_(self._guide_host, non_blocking=True)
+        self._guide_done.record()
+
+    def _check_guides(self, guides, num_seqs: int, ignore_kvcache: bool):
+        """The step's cursors, or None when no sequence is guided. Host only: everything is refused before anything is
+        allocated or launched."""
+        if guides is None:
+            return None
+        if len(guides) != num_seqs:
+            raise ValueError("guides must be aligned with input_ids_list")
+        if all(c is None for c in guides):
+            return None
+        if self.guide_store is None:
+            raise ValueError("this model serves no guided requests: EngineConfig.guided_max_states is 0 (or load_weights "
+                             "has not run)")
+        if ignore_kvcache:
+            raise ValueError("guides cannot be combined with ignore_kvcache")
+        for c in guides:
+            if c is None:
+                continue
+            g = c.guide
+            if g.evicted or g.refs <= 0 or not 0 <= g.base <= c.mask_row < g.base + g.num_states <= self.guide_store.max_states:
+                raise ValueError("a guide cursor whose guide is not held in this model's store (acquire it, and release it "
+                                 "only when the sequence is done)")
+        return list(guides)
 
     # ---- multi-LoRA serving ------------------------------------------------------------------------------------------
     def _require_lora_store(self) -> LoraStore:
@@ -549,7 +660,7 @@ class LlamaModel:
 
     def _make_infer_state(self, plan: BatchPlan, dev: dict, ignore_kvcache: bool,
                           sampled: bool = False, processed: bool = False, scratch_rows: int = None,
-                          scored: bool = False) -> LlamaInferState:
+                          scored: bool = False, guided: bool = False) -> LlamaInferState:
         """`scratch_rows`: rows whose flash-decoding partials the persistent scratch must hold when the step splits its
         sequences — the decoding sequences (default); a verify step: every row."""
         nsb = plan.num_seq_blocks
@@ -576,6 +687,7 @@ class LlamaModel:
             sampling=device_args(self._sample_dev, dev["seq_lengths"]) if sampled else None,
             adjust=logits_process.device_args(self._edit_dev, self._edit_rows_cap) if processed else None,
             logprobs=token_scores.device_args(self._score_dev, self._score_rows_cap) if scored else None,
+            guide=guide_kernels.GuideArgs(self._guide_masks, self._guide_dev) if guided else None,
             prefill_ctx_lens=dev.get("prefill_ctx_lens"), max_prefill_total_len=plan.max_prefill_total_len,
             kv_scales=self.kv_scales, kv_inv_scales=self.kv_inv_scales,
             verify=plan.verify_row_lens is not None, verify_row_lens=dev.get("verify_row_lens"))
@@ -591,7 +703,8 @@ class LlamaModel:
                                   self.engine_config.max_blocks_per_seq)
             rmsnorm_inplace(x, self.weight.final_norm, self.model_config.rms_norm_eps)
             return self.post_layer.forward_normed(x, out=self._engine.tok_err[:1], sampling=infer_state.sampling,
-                                                  adjust=infer_state.adjust, logprobs=infer_state.logprobs)
+                                                  adjust=infer_state.adjust, logprobs=infer_state.logprobs,
+                                                  guide=infer_state.guide)
         x = self.pre_layer.forward(input_ids)
         residual = torch.zeros_like(x)
         block_table = None if infer_state.ignore_kvcache else self.gpu_block_manager.block_table
@@ -601,13 +714,13 @@ class LlamaModel:
             x = residual.clone()                # pure decode, every row a last token — final norm of the residual rows
             rmsnorm_inplace(x, self.weight.final_norm, self.model_config.rms_norm_eps)
             return self.post_layer.forward_normed(x, sampling=infer_state.sampling, adjust=infer_state.adjust,
-                                                  logprobs=infer_state.logprobs)
+                                                  logprobs=infer_state.logprobs, guide=infer_state.guide)
         if not isinstance(x, torch.Tensor):     # the last down projection left as split-K partials
             if infer_state.num_prefill_seqs == 0:
                 # pure decode: every row is a last token — reduce + residual add + final norm in one launch
                 x = fused_add_rmsnorm_from_splitk(x, residual, self.weight.final_norm, self.model_config.rms_norm_eps)
                 return self.post_layer.forward_normed(x, sampling=infer_state.sampling, adjust=infer_state.adjust,
-                                                      logprobs=infer_state.logprobs)
+                                                      logprobs=infer_state.logprobs, guide=infer_state.guide)
             x = x.materialize()
         x += residual
         return self.post_layer.forward(x, infer_state)
@@ -701,7 +814,7 @@ class LlamaModel:
         return plan
 
     def _forward_decode_graph(self, plan: BatchPlan, dev: dict, sampled: bool = False,
-                              processed: bool = False, scored: bool = False) -> torch.Tensor:
+                              processed: bool = False, scored: bool = False, guided: bool = False) -> torch.Tensor:
         sbs, nsb_cap = self._graph_bucket(plan)
         use_engine = self._engine is not None and plan.batch_size == 1
         tap = self.post_layer.logits_tap
@@ -710,18 +823,20 @@ class LlamaModel:
         # alive in the shared pool, one captured without the tap does not — up to 65 MB per graph at 256 sequences)
         # (a sampled step is a graph of its own: its sampler reads the persistent parameter buffer; greedy graphs are as
         # they were; so is a processed step: its adjustment kernel reads the persistent entry buffer; and a scored step: its
-        # logprob kernel reads the rows' N from, and writes its results into, the persistent logprob buffer)
-        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None, sampled, processed, scored)
+        # logprob kernel reads the rows' N from, and writes its results into, the persistent logprob buffer; and a guided
+        # step: its mask kernel reads the rows' mask rows from the persistent row-index buffer)
+        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None, sampled, processed, scored,
+                                                                                 guided)
         entry = self._decode_graphs.pop(key, None)
         plan.seq_block_size, plan.num_seq_blocks = sbs, nsb_cap
         if entry is None:
             self.graph_captures += 1
             t_cap = time.perf_counter()
-            state = self._make_infer_state(plan, dev, False, sampled, processed, scored=scored)
+            state = self._make_infer_state(plan, dev, False, sampled, processed, scored=scored, guided=guided)
             # one eager run on a side stream first (library handles, workspaces, allocator pools): nothing may be lazily
             # initialised while the stream is capturing. Once per BATCH BUCKET (r06b): a new split geometry at a batch size
             # that has been captured before launches the same kernels on the same shapes — only the attention grid moves.
-            warm_key = (key[0], use_engine, tap is not None, sampled, processed, scored)
+            warm_key = (key[0], use_engine, tap is not None, sampled, processed, scored, guided)
             if warm_key not in self._warmed_buckets:
                 warm = torch.cuda.Stream()
                 warm.wait_stream(torch.cuda.current_stream())
@@ -756,7 +871,7 @@ class LlamaModel:
 
     # ---- decode look-ahead: the host side of step k+1 runs while the GPU executes step k ---------------------------------
     def _prepare_next_decode(self, plan: BatchPlan, seq_ids_list: List[int], tokens_dev: torch.Tensor, sampling=None,
-                             processed: bool = False, scoring=None):
+                             processed: bool = False, scoring=None, guided: bool = False):
         """Called right after the graph of a pure-decode step was launched, before the host blocks on its tokens. A
         generation loop calls forward again with the same sequences, every length + 1 and the tokens just sampled: plan
         that step now (numpy) and enqueue — behind the running graph, on the same stream — the H2D copy of its metadata and
@@ -787,19 +902,23 @@ class LlamaModel:
         la.sampling = sampling      # (the parameter buffer keeps this step's rows: the next step may reuse it as it is)
         la.processed = processed    # (the entry buffer does NOT keep: a processed step uploads its entries on a hit too)
         la.scoring = scoring        # (the logprob buffer keeps this step's N: the next step may reuse them as they are)
+        la.guided = guided          # (the row-index buffer does NOT keep: a guided step's mask rows depend on the token the
+                                    # host has not seen yet, so it uploads its rows on a hit too)
         return la
 
     def _take_lookahead(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
-                        processed: bool = False, scoring=None):
+                        processed: bool = False, scoring=None, guided: bool = False):
         """The prepared step, if this call is it (any other call drops the preparation). A sampled step hits only with
         the per-row parameters (seeds resolved) of the step it was prepared after: those are still on the device. So does
-        a scored step: only with the rows' N of the step it was prepared after."""
+        a scored step: only with the rows' N of the step it was prepared after. A guided step hits only a preparation made
+        after a guided step (as a processed one)."""
         la, self._lookahead = self._lookahead, None
         if (la is None or la.tokens is None or ignore_kvcache or not self._decode_lookahead
                 or not getattr(self.engine_config, "use_hip_graph", False)
                 or len(input_ids_list) != len(la.lens) or list(decoding_seq_lens_list) != la.lens
                 or list(seq_ids_list) != la.seq_ids or sampling != getattr(la, "sampling", None)
-                or processed != getattr(la, "processed", False) or scoring != getattr(la, "scoring", None)):
+                or processed != getattr(la, "processed", False) or scoring != getattr(la, "scoring", None)
+                or guided != getattr(la, "guided", False)):
             return None
         for ids, tok in zip(input_ids_list, la.tokens):
             if len(ids) != 1 or ids[0] != tok:
@@ -831,7 +950,8 @@ class LlamaModel:
     def forward(self, input_ids_list: List[List[int]], seq_ids_list: List[int],
                 decoding_seq_lens_list: List[int], ignore_kvcache: bool = False,
                 sampling_params: Optional[List[Optional[SamplingParams]]] = None,
-                prefill_ctx_lens: Optional[List[int]] = None, lora: Optional[List[Optional[str]]] = None) -> List[int]:
+                prefill_ctx_lens: Optional[List[int]] = None, lora: Optional[List[Optional[str]]] = None,
+                guides: Optional[List[Optional[object]]] = None) -> List[int]:
         """One iteration: prefill sequences first, then decoding sequences (one token each, their
         lengths in `decoding_seq_lens_list` INCLUDE that token). Returns the next token of every
         sequence: greedy (the reference, model.py:252-359), or — for the entries of `sampling_params`
@@ -850,10 +970,18 @@ class LlamaModel:
 
         `lora` (multi-LoRA serving; aligned with `input_ids_list`): the name of a loaded adapter, or None, per sequence.
         None or all None: today's call, launch for launch. Otherwise the step runs the LoRA layer path eagerly (no
-        hipGraph, no look-ahead): every row of a named sequence gets its adapter's low-rank update on every projection."""
+        hipGraph, no look-ahead): every row of a named sequence gets its adapter's low-rank update on every projection.
+
+        `guides` (guided decoding; aligned with `input_ids_list`): a swiftllm_amd.guided.GuideCursor over a guide held in
+        `guide_store`, or None, per sequence. None or all None: today's call, launch for launch. Otherwise the logits of a
+        guided row are masked to the tokens its cursor's state allows before anything else reads them (csrc/guided.hip);
+        a guide that is not built yet is built first, on the step's stream. The model does NOT advance the cursors: the
+        caller does, with the returned tokens (and not with the token of a prompt chunk that is not the last). Refused with
+        ignore_kvcache and when EngineConfig.guided_max_states is 0; forward_verify takes no guides."""
         self.last_logprobs = None
         if len(input_ids_list) == 0:
             return []   # the reference's idle engine calls forward([], [], []) in a loop
+        guides = self._check_guides(guides, len(input_ids_list), ignore_kvcache)
         lora_slots = self._resolve_lora(lora, len(input_ids_list))
         _require_hip_device()
         prefill_ctx_lens = self._check_prefill_ctx(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache,
@@ -878,13 +1006,13 @@ class LlamaModel:
         try:
             try:
                 return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                          prefill_ctx_lens, edits, lora_slots, scoring)
+                                          prefill_ctx_lens, edits, lora_slots, scoring, guides)
             except _decode_engine.DecodeEngineError as exc:
                 # bounded hand-off timed out inside the persistent one-sequence step: its KV writes are re-done below with
                 # the same values by the multi-launch HIP path, which serves one-sequence steps from here on
                 self._engine_failed(int(str(exc)))
                 return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                          prefill_ctx_lens, edits, lora_slots, scoring)
+                                          prefill_ctx_lens, edits, lora_slots, scoring, guides)
         except BaseException:
             self._rollback_histories(undo)
             raise
@@ -994,7 +1122,7 @@ class LlamaModel:
         return ctx
 
     def _begin_step(self, plan: BatchPlan, seq_ids_list, ignore_kvcache: bool = False, sampling=None, edits=None,
-                    scoring=None):
+                    scoring=None, guides=None):
         """What every step does between its plan and its launches: the rotary-table check, KV blocks for the caller's
         sequences, the plan's upload and — a sampled / processed / scored step — its parameters', entries' and N's. Returns the plan's
         device views and the host times at which the checked plan and the blocks were ready (host_profile's sections)."""
@@ -1016,26 +1144,31 @@ class LlamaModel:
             self._upload_edits(edits, plan.batch_size)
         if scoring is not None:
             self._upload_scoring(scoring, plan.batch_size)
+        if guides is not None:      # (a guided step: unbuilt guides are built, then the rows' mask rows go up)
+            self._upload_guides(guides, plan.batch_size)
         return dev, t_plan, t_blocks
 
     def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
-                      prefill_ctx_lens=None, edits=None, lora_slots=None, scoring=None):
+                      prefill_ctx_lens=None, edits=None, lora_slots=None, scoring=None, guides=None):
         prof = self._host_prof
         t0 = time.perf_counter() if prof is not None else 0.0
         sampled = sampling is not None
         processed = edits is not None
         scored = scoring is not None
+        guided = guides is not None
         if lora_slots is not None:
             return self._forward_step_lora(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                           prefill_ctx_lens, edits, lora_slots, scoring)
+                                           prefill_ctx_lens, edits, lora_slots, scoring, guides)
         la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling, processed,
-                                  scoring)
+                                  scoring, guided)
         if la is not None:      # the step that was prepared while the previous one ran: blocks, then the launch
             self.gpu_block_manager.allocate_blocks_for_seqs(la.seq_ids, la.lens)   # (the real sequences only)
             if processed:       # (the entries change every step: they go up before every replay)
                 self._upload_edits(edits, la.plan.batch_size)
-            tokens = self._forward_decode_graph(la.plan, la.dev, sampled, processed, scored)
-            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens, sampling, processed, scoring)
+            if guided:          # (so do the mask rows)
+                self._upload_guides(guides, la.plan.batch_size)
+            tokens = self._forward_decode_graph(la.plan, la.dev, sampled, processed, scored, guided)
+            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens, sampling, processed, scoring, guided)
             if self.after_launch_hook is not None:
                 self.after_launch_hook()
             t4 = time.perf_counter() if prof is not None else 0.0
@@ -1057,20 +1190,20 @@ class LlamaModel:
         else:
             plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                               self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
-        dev, t1, t2 = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits, scoring)
+        dev, t1, t2 = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits, scoring, guides)
         t3 = time.perf_counter() if prof is not None else 0.0
         pure_decode = plan.num_prefill_seqs == 0
         nxt = None
         if (pure_decode and not ignore_kvcache and getattr(self.engine_config, "use_hip_graph", False)):
-            tokens = self._forward_decode_graph(plan, dev, sampled, processed, scored)
+            tokens = self._forward_decode_graph(plan, dev, sampled, processed, scored, guided)
             if self._decode_lookahead:
-                nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens, sampling, processed, scoring)
+                nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens, sampling, processed, scoring, guided)
         else:
             if pure_decode and not ignore_kvcache and self._eager_uses_graph_buckets:
                 plan.seq_block_size, plan.num_seq_blocks = self._graph_bucket(plan)
             tokens = self._forward(dev["input_ids"],
                                    self._make_infer_state(plan, dev, ignore_kvcache, sampled, processed,
-                                                          scored=scored))[:num_real]
+                                                          scored=scored, guided=guided))[:num_real]
             tap = self.post_layer.logits_tap
             if tap and plan.batch_size > num_real:      # (tests) a padded eager step: the real rows only, as on replay
                 tap[-1] = tap[-1][:num_real]
@@ -1094,18 +1227,18 @@ class LlamaModel:
         return out
 
     def _forward_step_lora(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                           prefill_ctx_lens, edits, lora_slots, scoring=None):
+                           prefill_ctx_lens, edits, lora_slots, scoring=None, guides=None):
         """A step with at least one adapter row: the plain plan of the batch (never padded to a replay bucket), eager
         launches, the prepared look-ahead dropped; the row -> slot tiles go up in a buffer of their own."""
         self._lookahead = None
         num_real = len(input_ids_list)
         plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                           self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
-        dev = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits, scoring)[0]
+        dev = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits, scoring, guides)[0]
         num_prefill = num_real - len(decoding_seq_lens_list)
         row_slots = rows_of_sequences(lora_slots, [len(ids) for ids in input_ids_list[:num_prefill]])
         state = self._make_infer_state(plan, dev, ignore_kvcache, sampling is not None, edits is not None,
-                                       scored=scoring is not None)
+                                       scored=scoring is not None, guided=guides is not None)
         state.lora = LoraStep(LoraBatch(row_slots, self.lora_store.max_loras, self.device, self._lora_staging),
                               self.lora_store.layers)
         tokens = self._forward(dev["input_ids"], state)[:num_real]
@@ -1117,7 +1250,7 @@ class LlamaModel:
 
     @torch.inference_mode()
     def forward_verify(self, input_ids_list: List[List[int]], seq_ids_list: List[int],
-                       ctx_lens: List[int]) -> List[List[int]]:
+                       ctx_lens: List[int], guides: Optional[List[Optional[object]]] = None) -> List[List[int]]:
         """One speculative-decoding verify step (greedy; no reference counterpart). Sequence s has `ctx_lens[s]` tokens
         resident in the KV pool and brings `input_ids_list[s]`: its last accepted token followed by its drafts,
         1 .. max_draft_tokens + 1 tokens. Returns, per sequence, the greedy token after EVERY one of its inputs: the
@@ -1128,8 +1261,11 @@ class LlamaModel:
         It is the chunked-prefill forward of the same arguments with three differences: the infer state is marked
         `verify`, attention is kernels/paged_attn.paged_attention_verify (the decode kernel's geometry, split over the
         total lengths), and every row is a last token. Eager launches, no hipGraph. A verify step scores nothing:
-        `last_logprobs` is None afterwards."""
+        `last_logprobs` is None afterwards. It takes no guides either (a verify step picks the argmax of the raw logits):
+        `guides` with a cursor in it is refused."""
         self.last_logprobs = None
+        if guides is not None and any(c is not None for c in guides):
+            raise ValueError("forward_verify takes no guides: a guided sequence is never speculated")
         if len(input_ids_list) == 0:
             return []
         _require_hip_device()
