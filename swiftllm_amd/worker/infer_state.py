@@ -45,19 +45,10 @@ class LlamaInferState:
     last_token_indices: Optional[torch.Tensor] = None   # [batch_size] int32
     # Preallocated fp32 scratch for the flash-decoding partials.
     paged_attn_scratch: Optional[torch.Tensor] = None
-    # A sampled step (some row not greedy): the per-row parameters and `pos` (= the plan's seq_lengths view, the index
-    # the sampled token takes) as kernels/sampling.SampleArgs. None: every row is greedy (argmax).
-    sampling: Optional[object] = None
-    # A processed step (some row's params edit its logits): kernels/logits_process.AdjustArgs over the model's persistent
-    # entry buffer; the post layer runs the adjustment between lm_head and the choice of the token. None: no such row.
-    adjust: Optional[object] = None
-    # A scored step (some row asks for logprobs): kernels/logprobs.LogprobArgs over the model's persistent buffer; the post
-    # layer scores the picked tokens against the logits they were picked from. None: no such row, no launch.
-    logprobs: Optional[object] = None
-    # A guided step (some row's request is held to a regex, a choice or a token set): kernels/guided.GuideArgs over the
-    # model's mask pool and its persistent row-index buffer; the post layer masks the logits before anything else reads
-    # them. None: no such row, no launch.
-    guide: Optional[object] = None
+    # A step with logits options (some row guided, processed, sampled or asking for logprobs): worker/step_logits.LogitsArgs,
+    # one set of device views over the model's persistent buffers per option in use — the post layer masks, adjusts, draws
+    # and scores with them. None: a plain step, argmax of the raw logits and no further launch.
+    logits: Optional[object] = None
     # Chunked prefill: tokens of each prefill sequence already resident in the pool (int32 [num_prefill_seqs]); its new
     # tokens take logical positions [ctx, ctx + len) and attend to the pool (kernels/prefill_attn.prefill_attention_paged).
     # None: every prompt starts at position 0 and attends to its fresh projections — the reference's prefill.

@@ -31,21 +31,17 @@ class LlamaPostLayer:
                              device=input_embds.device, dtype=torch.int32)))
         last_input = input_embds.index_select(0, idx)    # fresh [batch, hidden] copy
         rmsnorm_inplace(last_input, self.weights.final_norm, self.model_config.rms_norm_eps)
-        return self.forward_normed(last_input, sampling=infer_state.sampling, adjust=infer_state.adjust,
-                                   logprobs=infer_state.logprobs, guide=infer_state.guide)
+        return self.forward_normed(last_input, logits=infer_state.logits)
 
-    def forward_normed(self, last_input: torch.Tensor, out: torch.Tensor = None, sampling=None,
-                       adjust=None, logprobs=None, guide=None) -> torch.Tensor:
+    def forward_normed(self, last_input: torch.Tensor, out: torch.Tensor = None, logits=None) -> torch.Tensor:
         """lm_head + sampling on rows that already went through the final norm (a pure-decode batch whose
         last add + norm ran fused on the split-K partials of the last down projection: every row is a last token).
-        `sampling`: the step's kernels/sampling.SampleArgs, or None for an all-greedy step (argmax, as before).
-        `adjust`: the step's kernels/logits_process.AdjustArgs — penalties, bias and min-p are applied to the logits in
-        place before the token is picked (the tap then shows what it was picked from) — or None: no launch.
-        `logprobs`: the step's kernels/logprobs.LogprobArgs — once the tokens are picked, the asking rows' log-probability,
-        rank and top-N alternatives are written into its buffers, from the same logits — or None: no launch.
-        `guide`: the step's kernels/guided.GuideArgs — every guided row's disallowed tokens become -inf before anything
-        else reads the logits (mask -> adjust -> pick -> logprobs: min-p takes its maximum over the allowed tokens, the tap
-        shows what the token was picked from, logprobs are the distribution over the allowed tokens) — or None: no launch."""
+        `logits`: the step's worker/step_logits.LogitsArgs, each field None for no launch, or None for a plain step (argmax
+        of the raw logits). mask -> adjust -> pick -> logprobs: `guide` turns every guided row's disallowed tokens into -inf
+        before anything else reads the logits (so min-p takes its maximum over the allowed tokens and logprobs are the
+        distribution over them); `adjust` applies penalties, bias and min-p in place (the tap shows what the token was
+        picked from); `sampling` draws where a row is not greedy; `logprobs` scores the picked tokens on the same logits."""
+        guide, adjust, sampling, logprobs = logits or (None,) * 4
         logits = linear(last_input, self.weights.lm_head, self.skinny)   # [batch, vocab]
         if guide is not None:
             mask_logits(logits, guide)

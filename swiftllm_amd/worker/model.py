@@ -22,6 +22,7 @@ The compute backend is libswiftllm_hip.so only; without a HIP device this class 
 import math
 import os
 import time
+import weakref
 from typing import List, Optional
 
 import numpy as np
@@ -44,13 +45,11 @@ from .kernels.linear import RawResidual
 from .kernels.paged_attn import verify_max_tokens
 from .kernels.rmsnorm import fused_add_rmsnorm_from_splitk, rmsnorm_inplace
 from .kernels import logits_process
-from .kernels import logprobs as token_scores
-from .kernels import guided as guide_kernels
-from .kernels.sampling import device_args, pack_params
 from .lora import LoraBatch, LoraStaging, LoraStep, LoraStore, parse_lora_modules, rows_of_sequences
 from .layers.pre_layer import LlamaPreLayer
 from .layers.transformer_layer import LlamaTransformerLayer
 from .layers.post_layer import LlamaPostLayer
+from .step_logits import PLAIN, LogitsStage, StepLogits
 from .token_history import TokenHistory, row_entries
 from .weight import load_weights, pack_decode_weights
 
@@ -73,7 +72,10 @@ class _DecodeGraph:
 
 class _DecodeLookahead:
     """Everything the NEXT decode step of the same batch needs, prepared while the GPU was still busy with this one."""
-    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev", "sampling", "processed", "scoring", "guided")
+    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev", "logits")
+
+    def __init__(self):
+        self.logits = PLAIN     # the StepLogits of the step it was prepared behind
 
 
 class LlamaModel:
@@ -107,7 +109,7 @@ class LlamaModel:
         self._meta_dev = None       # its device twin (fixed address: hipGraph replays read it)
         self._meta_done = None
         self._num_slots = 256        # CUs: one 8-wave paged-attention workgroup each
-        self._decode_graphs = {}     # (batch, split width, split count, logits kept) -> _DecodeGraph, in LRU order
+        self._decode_graphs = {}     # (batch, split width, split count, logits kept) + StepLogits.flags -> _DecodeGraph, LRU order
         self._lookahead = None       # _DecodeLookahead of the step that is expected next (graph replay only)
         self._decode_lookahead = True    # (tests switch it off to hold the fast path to the plain one)
         # optional callable, invoked by forward() in the calling thread once the step's kernels are enqueued and before
@@ -126,35 +128,20 @@ class LlamaModel:
         self.graph_captures = 0      # hipGraph captures so far (the first at a batch bucket = one warm-up forward + one capture)
         self.graph_capture_s = 0.0   # host seconds spent in them: serving reports both
         self._warmed_buckets = set()
-        # per-row sampling parameters of a sampled step: pinned staging + its device twin (fixed address: a sampled
-        # hipGraph reads it on every replay), laid out by kernels/sampling.pack_params; one H2D copy per sampled step
-        self._sample_host = self._sample_host_np = self._sample_dev = self._sample_done = None
-        # logits processing (penalties / logit bias / min-p / min_tokens bans; kernels/logits_process.py): the token history
-        # of every sequence whose request asks for it (worker/token_history.py; started by its prefill, dropped by
-        # free_seqs_resources), and the step's entries: pinned staging + its device twin (fixed address: a processed
-        # hipGraph reads it on every replay; uploaded before every processed step, look-ahead hits included)
+        # a step's logits options (seeded sampling, logits processing, per-token logprobs, guided decoding): their persistent
+        # device buffers and pinned staging (worker/step_logits.py); one that grows moves, and the captured graphs go (bound
+        # weakly — a dropped model frees its HBM at once — and looked up at the call: tests wrap _drop_decode_graphs)
+        me = weakref.ref(self)
+        self._logits = LogitsStage(lambda: me()._drop_decode_graphs())
+        # logits processing: the token history of every sequence that asks for it (worker/token_history.py; started by its
+        # prefill, dropped by free_seqs_resources)
         self._histories = {}
-        self._edit_host = self._edit_host_np = self._edit_dev = self._edit_done = None
-        self._edit_rows_cap = 0
-        # per-token logprobs (kernels/logprobs.py): one persistent device buffer — the rows' N, then what the kernel writes
-        # (rank, logprobs, ids; rows x 21) — at a fixed address (a scored hipGraph reads and writes it on every replay), the
-        # pinned staging of the N (one H2D copy per scored step that is not a look-ahead hit) and the pinned buffer the
-        # results come back through (one D2H copy per scored step, enqueued before the tokens' sync)
-        self._score_dev = self._score_host = self._score_host_np = self._score_done = None
-        self._score_out = self._score_out_np = None
-        self._score_rows_cap = 0
         # what the last forward / forward_verify call learnt about its tokens: None when no row asked, else one
         # TokenLogprob or None per sequence of the batch
         self.last_logprobs = None
         # guided decoding (swiftllm_amd/guided, kernels/guided.py; EngineConfig.guided_max_states > 0): the host bookkeeping
-        # of the mask pool (GuideStore; None = off), the pool itself (int32 [guided_max_states, ceil(vocab / 32)]), the
-        # vocabulary's flat device form the build kernel walks, and the step's mask row per row of logits: pinned staging +
-        # its device twin (fixed address: a guided hipGraph reads it on every replay; uploaded before every guided step,
-        # look-ahead hits included — the rows move with every token)
-        self.guide_store = None
-        self._guide_vocab = self._guide_vocab_dev = self._guide_masks = None
-        self._guide_host = self._guide_host_np = self._guide_dev = self._guide_done = None
-        self._guide_rows_cap = 0
+        # of the mask pool (GuideStore; None = off) and the vocabulary its guides are compiled against
+        self.guide_store = self._guide_vocab = None
         # speculative decoding: drafts one verify step takes per sequence (forward_verify) = the verify attention kernel's
         # tokens per sequence (16 / G) minus the last accepted token that leads them; 0 with FP8 pools (no instantiation)
         self.max_draft_tokens = 0 if self.kv_fp8 else max(0, verify_max_tokens(self.model_config) - 1)
@@ -190,12 +177,10 @@ class LlamaModel:
             self.kv_inv_scales = torch.ones_like(self.kv_scales)
         # (allocated before profile_num_blocks measures: the largest replay bucket's rows)
         ecfg = self.engine_config
-        self._ensure_sampling_rows(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
-        self._ensure_edit_buffer(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)), 0)
-        self._ensure_score_rows(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
-        # (... and so are the guide mask pool and the vocabulary's device form, when guided decoding is on)
+        # (... as are the guide mask pool and the vocabulary's device form, when guided decoding is on)
         if int(getattr(ecfg, "guided_max_states", 0) or 0) > 0:
-            self._init_guided(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
+            self._init_guided()
+        self._logits.reserve(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
         # (... and so are the adapter slot stacks: the KV pool is sized with them)
         if int(getattr(ecfg, "max_loras", 0) or 0) > 0:
             self.lora_store = LoraStore(self.model_config, int(ecfg.max_loras), int(ecfg.max_lora_rank), self.dtype,
@@ -206,6 +191,8 @@ class LlamaModel:
                 self.load_lora(name, path)
 
     # ---- guided decoding ---------------------------------------------------------------------------------------------
+    _guide_masks = property(lambda self: self._logits.guide_masks)      # (the pool, read only: tests hold it to their reference)
+
     def set_guide_vocab(self, vocab: TokenVocab):
         """The bytes every token id spells, for models without a tokenizer.json (dummy checkpoints, tests): call it before
         load_weights, or afterwards while no guide is resident. It must spell exactly the model's vocab_size ids."""
@@ -217,13 +204,12 @@ class LlamaModel:
         if self.guide_store is not None:
             if self.guide_store.resident():
                 raise RuntimeError("set_guide_vocab while guides are resident: their masks were built from the old vocabulary")
-            self._guide_vocab_dev = guide_kernels.upload_vocab(vocab, self.model_config.vocab_size, self.device)
+            self._logits.set_vocab(vocab, self.model_config.vocab_size, self.device)
             self.guide_store.vocab = vocab
         self._guide_vocab = vocab
 
-    def _init_guided(self, rows: int):
-        """The mask pool, the vocabulary's device form and the row-index buffer. A missing vocabulary is an error here, at
-        start-up, not at the first guided request."""
+    def _init_guided(self):
+        """The mask pool and the device vocabulary. No vocabulary: an error here, at start-up, not at the first guided request."""
         ecfg, vocab_size = self.engine_config, self.model_config.vocab_size
         if self._guide_vocab is None:
             path = os.path.join(str(ecfg.model_path), "tokenizer.json")
@@ -231,53 +217,9 @@ class LlamaModel:
                 raise RuntimeError(f"guided_max_states = {ecfg.guided_max_states} but there is no vocabulary: {path} does not "
                                    "exist and LlamaModel.set_guide_vocab was not called")
             self._guide_vocab = TokenVocab.from_tokenizer_json(path, vocab_size)
-        self._guide_vocab_dev = guide_kernels.upload_vocab(self._guide_vocab, vocab_size, self.device)
-        self.guide_store = GuideStore(int(ecfg.guided_max_states), vocab_size, self._guide_vocab)
-        self._guide_masks = torch.zeros((self.guide_store.max_states, self.guide_store.words), dtype=torch.int32,
-                                        device=self.device)
-        self._ensure_guide_rows(rows)
-        print(f"[Model] guided decoding: {self.guide_store.max_states} mask rows, "
-              f"{self._guide_masks.numel() * 4 / 2**20:.1f} MiB", flush=True)
-
-    def _ensure_guide_rows(self, rows: int):
-        """The persistent row-index buffer holds `rows` rows. Growing it moves it: the graphs captured against the old one
-        are dropped."""
-        if self._guide_rows_cap >= rows:
-            return
-        cap = max(rows, 2 * self._guide_rows_cap)
-        self._guide_host = torch.empty(cap, dtype=torch.int32, pin_memory=True)
-        self._guide_host_np = self._guide_host.numpy()
-        self._guide_dev = torch.full((cap,), -1, dtype=torch.int32, device=self.device)     # (no row is guided)
-        self._guide_done = torch.cuda.Event()
-        self._guide_rows_cap = cap
-        self._drop_decode_graphs()     # captured guided graphs point into the old buffer
-
-    def _build_guide(self, guide):
-        """Fill the guide's rows of the pool, on the current stream: behind every earlier step that may still read the rows
-        of a guide evicted for it. A DFA guide: one launch of the build kernel; an allowed-token guide: its one row, written
-        by the host."""
-        if guide.dfa is None:
-            self._guide_masks[guide.base].copy_(torch.from_numpy(guide.host_mask_row(self.guide_store.words)))
-        else:
-            vocab_size = self.model_config.vocab_size
-            ends = [t for t in guide.end_ids if t < vocab_size]
-            guide_kernels.build_guide_masks(
-                self._guide_masks, guide.base, torch.from_numpy(guide.dfa.trans).to(self.device),
-                torch.from_numpy(guide.dfa.accepting.view(np.uint8)).to(self.device), self._guide_vocab_dev,
-                torch.tensor(ends, dtype=torch.int32, device=self.device) if ends else None)
-        guide.built = True
-
-    def _upload_guides(self, guides, rows: int):
-        """Build what is not built yet, then one async H2D copy of the step's mask row per row (unguided rows, padded
-        bucket rows and everything past them: -1)."""
-        for c in guides:
-            if c is not None and not c.guide.built:
-                self._build_guide(c.guide)
-        self._ensure_guide_rows(rows)
-        self._guide_done.synchronize()     # (the previous step's copy out of the pinned buffer: long done)
-        guide_kernels.pack_rows(guides, self._guide_host_np)
-        self._guide_dev.copy_(self._guide_host, non_blocking=True)
-        self._guide_done.record()
+        self.guide_store = store = GuideStore(int(ecfg.guided_max_states), vocab_size, self._guide_vocab)
+        self._logits.set_vocab(self._guide_vocab, vocab_size, self.device, mask_shape=(store.max_states, store.words))
+        print(f"[Model] guided decoding: {store.max_states} mask rows, {self._guide_masks.numel() * 4 / 2**20:.1f} MiB", flush=True)
 
     def _check_guides(self, guides, num_seqs: int, ignore_kvcache: bool):
         """The step's cursors, or None when no sequence is guided. Host only: everything is refused before anything is
@@ -413,7 +355,7 @@ class LlamaModel:
         # its share): a max_batch_size decode forward's activations, [B, vocab] logits (+ fp32 argmax candidates) and
         # split-K scratch. The eager prefill peak above does not contain it.
         graph_bytes = 0
-        if getattr(ecfg, "use_hip_graph", False):
+        if self._use_hip_graph:
             graph_bytes = self._measure_decode_graph_bytes()
             free_memory, _ = torch.cuda.mem_get_info()      # (the measurement may have grown the regular pool as well)
             peak_memory = max(peak_memory, total_memory - free_memory)
@@ -571,96 +513,8 @@ class LlamaModel:
         self._meta_done.record()
         return {name: self._meta_dev[off:off + n] for name, off, n in layout}
 
-    def _ensure_sampling_rows(self, rows: int):
-        cap = 0 if self._sample_dev is None else self._sample_dev.numel() // 5
-        if cap >= rows:
-            return
-        cap = max(rows, 2 * cap)
-        self._sample_host = torch.empty(5 * cap, dtype=torch.int32, pin_memory=True)
-        self._sample_host_np = self._sample_host.numpy()
-        self._sample_dev = torch.zeros(5 * cap, dtype=torch.int32, device=self.device)
-        self._sample_done = torch.cuda.Event()
-        self._drop_decode_graphs()     # captured sampled graphs point into the old buffer
-
-    def _upload_sampling(self, params: List[Optional[SamplingParams]], rows: int):
-        """One async H2D copy of the step's per-row parameters (seeds resolved; rows past the caller's batch: greedy)."""
-        self._ensure_sampling_rows(rows)
-        self._sample_done.synchronize()     # (the previous step's copy out of the pinned buffer: long done)
-        pack_params(params, self._sample_host_np)
-        self._sample_dev.copy_(self._sample_host, non_blocking=True)
-        self._sample_done.record()
-
-    _MIN_EDIT_CAP = 1024     # entries the edit buffer starts with
-    _ONE_COPY_WORDS = 16384  # up to this many int32 words the whole edit buffer goes up in one H2D copy
-
-    def _ensure_edit_buffer(self, rows: int, edits: int):
-        """The persistent entry buffer holds `rows` rows and `edits` entries (kernels/logits_process.buffer_len). Growing
-        it moves it: the graphs captured against the old one are dropped. The entry capacity grows in powers of two (a
-        penalised sequence adds at most one entry per step)."""
-        cap = 0 if self._edit_dev is None else logits_process.edit_capacity(self._edit_dev.numel(), self._edit_rows_cap)
-        if self._edit_dev is not None and self._edit_rows_cap >= rows and cap >= edits:
-            return
-        rows = max(rows, self._edit_rows_cap)
-        cap = max(cap, self._MIN_EDIT_CAP)
-        while cap < edits:
-            cap *= 2
-        total = logits_process.buffer_len(rows, cap)
-        self._edit_host = torch.empty(total, dtype=torch.int32, pin_memory=True)
-        self._edit_host_np = self._edit_host.numpy()
-        self._edit_dev = torch.zeros(total, dtype=torch.int32, device=self.device)
-        self._edit_done = torch.cuda.Event()
-        self._edit_rows_cap = rows
-        self._drop_decode_graphs()     # captured processed graphs point into the old buffer
-
-    def _upload_edits(self, edits, rows: int):
-        """Pack the step's entries (one RowEdits or None per real row; rows past them: inert) and ship them: one async
-        H2D copy while the buffer is small, else the row header and the used part of each of the three arrays."""
-        need = sum(len(r.ids) for r in edits if r is not None)
-        self._ensure_edit_buffer(rows, need)
-        self._edit_done.synchronize()     # (the previous step's copy out of the pinned buffer: long done)
-        rows_cap = self._edit_rows_cap
-        used = logits_process.pack_edits(edits, self._edit_host_np, rows_cap)
-        total = self._edit_dev.numel()
-        if total <= self._ONE_COPY_WORDS:
-            self._edit_dev.copy_(self._edit_host, non_blocking=True)
-        else:
-            base = 5 * rows_cap + 1
-            cap = logits_process.edit_capacity(total, rows_cap)
-            self._edit_dev[:base].copy_(self._edit_host[:base], non_blocking=True)
-            if used:
-                for a in range(3):
-                    lo = base + a * cap
-                    self._edit_dev[lo:lo + used].copy_(self._edit_host[lo:lo + used], non_blocking=True)
-        self._edit_done.record()
-
-    def _ensure_score_rows(self, rows: int):
-        """The persistent logprob buffer holds `rows` rows. Growing it moves it: the graphs captured against the old one are
-        dropped."""
-        if self._score_rows_cap >= rows:
-            return
-        cap = max(rows, 2 * self._score_rows_cap)
-        total = token_scores.buffer_len(cap)
-        self._score_host = torch.empty(cap, dtype=torch.int32, pin_memory=True)
-        self._score_host_np = self._score_host.numpy()
-        self._score_out = torch.empty(total - cap, dtype=torch.int32, pin_memory=True)
-        self._score_out_np = self._score_out.numpy()
-        self._score_dev = torch.zeros(total, dtype=torch.int32, device=self.device)
-        self._score_dev[:cap].fill_(-1)     # (no row asks)
-        self._score_done = torch.cuda.Event()
-        self._score_rows_cap = cap
-        self._drop_decode_graphs()     # captured scored graphs point into the old buffer
-
-    def _upload_scoring(self, scoring: List[Optional[int]], rows: int):
-        """One async H2D copy of the step's N per row (None rows, padded bucket rows and everything past them: -1)."""
-        self._ensure_score_rows(rows)
-        self._score_done.synchronize()     # (the previous step's copy out of the pinned buffer: long done)
-        token_scores.pack_top_n(scoring, self._score_host_np)
-        self._score_dev[:self._score_rows_cap].copy_(self._score_host, non_blocking=True)
-        self._score_done.record()
-
-    def _make_infer_state(self, plan: BatchPlan, dev: dict, ignore_kvcache: bool,
-                          sampled: bool = False, processed: bool = False, scratch_rows: int = None,
-                          scored: bool = False, guided: bool = False) -> LlamaInferState:
+    def _make_infer_state(self, plan: BatchPlan, dev: dict, ignore_kvcache: bool, opts: StepLogits = PLAIN,
+                          scratch_rows: int = None) -> LlamaInferState:
         """`scratch_rows`: rows whose flash-decoding partials the persistent scratch must hold when the step splits its
         sequences — the decoding sequences (default); a verify step: every row."""
         nsb = plan.num_seq_blocks
@@ -684,10 +538,7 @@ class LlamaModel:
             ignore_kvcache=ignore_kvcache,
             position_indices=dev["position_indices"], last_token_indices=dev["last_token_indices"],
             paged_attn_scratch=self._scratch if nsb > 1 else None,
-            sampling=device_args(self._sample_dev, dev["seq_lengths"]) if sampled else None,
-            adjust=logits_process.device_args(self._edit_dev, self._edit_rows_cap) if processed else None,
-            logprobs=token_scores.device_args(self._score_dev, self._score_rows_cap) if scored else None,
-            guide=guide_kernels.GuideArgs(self._guide_masks, self._guide_dev) if guided else None,
+            logits=self._logits.args(opts, dev["seq_lengths"]),
             prefill_ctx_lens=dev.get("prefill_ctx_lens"), max_prefill_total_len=plan.max_prefill_total_len,
             kv_scales=self.kv_scales, kv_inv_scales=self.kv_inv_scales,
             verify=plan.verify_row_lens is not None, verify_row_lens=dev.get("verify_row_lens"))
@@ -702,9 +553,7 @@ class LlamaModel:
                                   infer_state.seq_ids, infer_state.decoding_seq_lens, self._cos_cached, self._sin_cached,
                                   self.engine_config.max_blocks_per_seq)
             rmsnorm_inplace(x, self.weight.final_norm, self.model_config.rms_norm_eps)
-            return self.post_layer.forward_normed(x, out=self._engine.tok_err[:1], sampling=infer_state.sampling,
-                                                  adjust=infer_state.adjust, logprobs=infer_state.logprobs,
-                                                  guide=infer_state.guide)
+            return self.post_layer.forward_normed(x, self._engine.tok_err[:1], infer_state.logits)
         x = self.pre_layer.forward(input_ids)
         residual = torch.zeros_like(x)
         block_table = None if infer_state.ignore_kvcache else self.gpu_block_manager.block_table
@@ -713,17 +562,16 @@ class LlamaModel:
         if isinstance(x, RawResidual):          # the last down projection added itself into the residual (rows_decode):
             x = residual.clone()                # pure decode, every row a last token — final norm of the residual rows
             rmsnorm_inplace(x, self.weight.final_norm, self.model_config.rms_norm_eps)
-            return self.post_layer.forward_normed(x, sampling=infer_state.sampling, adjust=infer_state.adjust,
-                                                  logprobs=infer_state.logprobs, guide=infer_state.guide)
-        if not isinstance(x, torch.Tensor):     # the last down projection left as split-K partials
-            if infer_state.num_prefill_seqs == 0:
-                # pure decode: every row is a last token — reduce + residual add + final norm in one launch
-                x = fused_add_rmsnorm_from_splitk(x, residual, self.weight.final_norm, self.model_config.rms_norm_eps)
-                return self.post_layer.forward_normed(x, sampling=infer_state.sampling, adjust=infer_state.adjust,
-                                                      logprobs=infer_state.logprobs, guide=infer_state.guide)
-            x = x.materialize()
-        x += residual
-        return self.post_layer.forward(x, infer_state)
+        elif not isinstance(x, torch.Tensor) and infer_state.num_prefill_seqs == 0:
+            # the last down projection left as split-K partials, pure decode: every row is a last token — reduce +
+            # residual add + final norm in one launch
+            x = fused_add_rmsnorm_from_splitk(x, residual, self.weight.final_norm, self.model_config.rms_norm_eps)
+        else:
+            if not isinstance(x, torch.Tensor):     # split-K partials of a step with prompt rows
+                x = x.materialize()
+            x += residual
+            return self.post_layer.forward(x, infer_state)
+        return self.post_layer.forward_normed(x, logits=infer_state.logits)
 
     def _engine_applies(self, st) -> bool:
         return (self._engine is not None and getattr(st, "lora", None) is None and st.num_prefill_seqs == 0 and st.batch_size == 1
@@ -742,6 +590,10 @@ class LlamaModel:
         self.engine_fallbacks += 1
 
     # ---- hipGraph replay of pure-decode steps ------------------------------------------------------------
+    @property
+    def _use_hip_graph(self) -> bool:       # (read at every use: tools flip it on a live model)
+        return getattr(self.engine_config, "use_hip_graph", False)
+
     def _drop_decode_graphs(self):
         """Forget every captured decode graph (their buffers moved, or the pool / engine they were captured against is gone)
         AND the private memory pool they shared. The pool handle must go with them: once its last graph is destroyed the
@@ -813,30 +665,25 @@ class LlamaModel:
         plan.num_real_seqs = b
         return plan
 
-    def _forward_decode_graph(self, plan: BatchPlan, dev: dict, sampled: bool = False,
-                              processed: bool = False, scored: bool = False, guided: bool = False) -> torch.Tensor:
+    def _forward_decode_graph(self, plan: BatchPlan, dev: dict, opts: StepLogits = PLAIN) -> torch.Tensor:
         sbs, nsb_cap = self._graph_bucket(plan)
         use_engine = self._engine is not None and plan.batch_size == 1
         tap = self.post_layer.logits_tap
         tap_len = len(tap) if tap is not None else 0
         # (the engine has one launch geometry; a graph captured while a test taps the logits keeps its [B, vocab] tensor
         # alive in the shared pool, one captured without the tap does not — up to 65 MB per graph at 256 sequences)
-        # (a sampled step is a graph of its own: its sampler reads the persistent parameter buffer; greedy graphs are as
-        # they were; so is a processed step: its adjustment kernel reads the persistent entry buffer; and a scored step: its
-        # logprob kernel reads the rows' N from, and writes its results into, the persistent logprob buffer; and a guided
-        # step: its mask kernel reads the rows' mask rows from the persistent row-index buffer)
-        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None, sampled, processed, scored,
-                                                                                 guided)
+        # (each logits option in use makes the step a graph of its own: StepLogits.flags; plain graphs are as they were)
+        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None,) + opts.flags
         entry = self._decode_graphs.pop(key, None)
         plan.seq_block_size, plan.num_seq_blocks = sbs, nsb_cap
         if entry is None:
             self.graph_captures += 1
             t_cap = time.perf_counter()
-            state = self._make_infer_state(plan, dev, False, sampled, processed, scored=scored, guided=guided)
+            state = self._make_infer_state(plan, dev, False, opts)
             # one eager run on a side stream first (library handles, workspaces, allocator pools): nothing may be lazily
             # initialised while the stream is capturing. Once per BATCH BUCKET (r06b): a new split geometry at a batch size
             # that has been captured before launches the same kernels on the same shapes — only the attention grid moves.
-            warm_key = (key[0], use_engine, tap is not None, sampled, processed, scored, guided)
+            warm_key = (key[0], use_engine, tap is not None) + opts.flags
             if warm_key not in self._warmed_buckets:
                 warm = torch.cuda.Stream()
                 warm.wait_stream(torch.cuda.current_stream())
@@ -870,8 +717,7 @@ class LlamaModel:
         return entry.out_tokens[:n]
 
     # ---- decode look-ahead: the host side of step k+1 runs while the GPU executes step k ---------------------------------
-    def _prepare_next_decode(self, plan: BatchPlan, seq_ids_list: List[int], tokens_dev: torch.Tensor, sampling=None,
-                             processed: bool = False, scoring=None, guided: bool = False):
+    def _prepare_next_decode(self, plan: BatchPlan, seq_ids_list: List[int], tokens_dev: torch.Tensor, opts: StepLogits = PLAIN):
         """Called right after the graph of a pure-decode step was launched, before the host blocks on its tokens. A
         generation loop calls forward again with the same sequences, every length + 1 and the tokens just sampled: plan
         that step now (numpy) and enqueue — behind the running graph, on the same stream — the H2D copy of its metadata and
@@ -897,28 +743,17 @@ class LlamaModel:
         self._la_done.record()
         dev = {name: self._meta_dev[off:off + n] for name, off, n in layout}
         dev["input_ids"][:b].copy_(tokens_dev)  # int64 -> int32 on the device: the host has not seen them yet (inert rows: 0)
-        la = _DecodeLookahead()
-        la.seq_ids, la.lens, la.plan, la.dev, la.tokens = list(seq_ids_list), next_lens, nxt, dev, None
-        la.sampling = sampling      # (the parameter buffer keeps this step's rows: the next step may reuse it as it is)
-        la.processed = processed    # (the entry buffer does NOT keep: a processed step uploads its entries on a hit too)
-        la.scoring = scoring        # (the logprob buffer keeps this step's N: the next step may reuse them as they are)
-        la.guided = guided          # (the row-index buffer does NOT keep: a guided step's mask rows depend on the token the
-                                    # host has not seen yet, so it uploads its rows on a hit too)
+        la = _DecodeLookahead()     # (`logits`: what the next step must continue, StepLogits.continues)
+        la.seq_ids, la.lens, la.plan, la.dev, la.tokens, la.logits = list(seq_ids_list), next_lens, nxt, dev, None, opts
         return la
 
-    def _take_lookahead(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
-                        processed: bool = False, scoring=None, guided: bool = False):
-        """The prepared step, if this call is it (any other call drops the preparation). A sampled step hits only with
-        the per-row parameters (seeds resolved) of the step it was prepared after: those are still on the device. So does
-        a scored step: only with the rows' N of the step it was prepared after. A guided step hits only a preparation made
-        after a guided step (as a processed one)."""
+    def _take_lookahead(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts: StepLogits = PLAIN):
+        """The prepared step, if this call is it (any other call drops the preparation): the same sequences, every length
+        + 1, the tokens just returned, and logits options that continue those of the step it was prepared behind."""
         la, self._lookahead = self._lookahead, None
-        if (la is None or la.tokens is None or ignore_kvcache or not self._decode_lookahead
-                or not getattr(self.engine_config, "use_hip_graph", False)
+        if (la is None or la.tokens is None or ignore_kvcache or not self._decode_lookahead or not self._use_hip_graph
                 or len(input_ids_list) != len(la.lens) or list(decoding_seq_lens_list) != la.lens
-                or list(seq_ids_list) != la.seq_ids or sampling != getattr(la, "sampling", None)
-                or processed != getattr(la, "processed", False) or scoring != getattr(la, "scoring", None)
-                or guided != getattr(la, "guided", False)):
+                or list(seq_ids_list) != la.seq_ids or not opts.continues(la.logits)):
             return None
         for ids, tok in zip(input_ids_list, la.tokens):
             if len(ids) != 1 or ids[0] != tok:
@@ -930,21 +765,18 @@ class LlamaModel:
         """The step's one D2H copy (and its one sync). A step of the persistent decode engine brings its error word back in
         the same copy (DecodeEngine.tok_err = [token, error]). A scored step's results are copied into their pinned buffer
         first, on the same stream: the tokens' sync covers them, and `last_logprobs` is read off that buffer afterwards."""
-        if scoring is None:
-            return self._sync_tokens(tokens)
-        self._score_out.copy_(self._score_dev[self._score_rows_cap:], non_blocking=True)
-        out = self._sync_tokens(tokens)
-        self.last_logprobs = token_scores.unpack(self._score_out_np, self._score_rows_cap, scoring)
-        return out
-
-    def _sync_tokens(self, tokens: torch.Tensor) -> List[int]:
+        read_scores = None if scoring is None else self._logits.fetch_scores(scoring)
         eng = self._engine
         if eng is not None and tokens.data_ptr() == eng.tok_err.data_ptr():
-            vals = eng.tok_err.tolist()
-            if vals[1] != 0:
-                raise _decode_engine.DecodeEngineError(str(vals[1]))
-            return vals[:1]
-        return tokens.tolist()
+            out, err = eng.tok_err.tolist()
+            if err != 0:
+                raise _decode_engine.DecodeEngineError(str(err))
+            out = [out]
+        else:
+            out = tokens.tolist()
+        if read_scores is not None:
+            self.last_logprobs = read_scores()
+        return out
 
     @torch.inference_mode()
     def forward(self, input_ids_list: List[List[int]], seq_ids_list: List[int],
@@ -1003,16 +835,17 @@ class LlamaModel:
                 p is not None and p.processes_logits for p in sampling_params))):
             edits = self._track_histories(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                                           sampling_params or [None] * len(input_ids_list), prefill_ctx_lens, undo)
+        opts = StepLogits.of(sampling, edits, scoring, guides)
         try:
             try:
-                return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                          prefill_ctx_lens, edits, lora_slots, scoring, guides)
+                return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts,
+                                          prefill_ctx_lens, lora_slots)
             except _decode_engine.DecodeEngineError as exc:
                 # bounded hand-off timed out inside the persistent one-sequence step: its KV writes are re-done below with
                 # the same values by the multi-launch HIP path, which serves one-sequence steps from here on
                 self._engine_failed(int(str(exc)))
-                return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                          prefill_ctx_lens, edits, lora_slots, scoring, guides)
+                return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts,
+                                          prefill_ctx_lens, lora_slots)
         except BaseException:
             self._rollback_histories(undo)
             raise
@@ -1121,11 +954,10 @@ class LlamaModel:
                                    f"({rope_rows} positions)")
         return ctx
 
-    def _begin_step(self, plan: BatchPlan, seq_ids_list, ignore_kvcache: bool = False, sampling=None, edits=None,
-                    scoring=None, guides=None):
+    def _begin_step(self, plan: BatchPlan, seq_ids_list, ignore_kvcache: bool = False, opts: StepLogits = PLAIN):
         """What every step does between its plan and its launches: the rotary-table check, KV blocks for the caller's
-        sequences, the plan's upload and — a sampled / processed / scored step — its parameters', entries' and N's. Returns the plan's
-        device views and the host times at which the checked plan and the blocks were ready (host_profile's sections)."""
+        sequences, the plan's upload and what the step's logits options read. Returns the plan's device views and the
+        host times at which the checked plan and the blocks were ready (host_profile's sections)."""
         num_real = plan.num_real_seqs = len(seq_ids_list)
         longest = max(plan.seq_lengths_list)
         if longest > self._cos_cached.shape[0]:
@@ -1138,107 +970,73 @@ class LlamaModel:
             self.gpu_block_manager.allocate_blocks_for_seqs(seq_ids_list, plan.seq_lengths_list[:num_real])
         t_blocks = time.perf_counter()
         dev = self._upload_plan(plan)
-        if sampling is not None:
-            self._upload_sampling(sampling, plan.batch_size)
-        if edits is not None:
-            self._upload_edits(edits, plan.batch_size)
-        if scoring is not None:
-            self._upload_scoring(scoring, plan.batch_size)
-        if guides is not None:      # (a guided step: unbuilt guides are built, then the rows' mask rows go up)
-            self._upload_guides(guides, plan.batch_size)
+        self._logits.upload(opts, plan.batch_size)
         return dev, t_plan, t_blocks
 
-    def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling=None,
-                      prefill_ctx_lens=None, edits=None, lora_slots=None, scoring=None, guides=None):
+    def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts: StepLogits = PLAIN,
+                      prefill_ctx_lens=None, lora_slots=None):
         prof = self._host_prof
         t0 = time.perf_counter() if prof is not None else 0.0
-        sampled = sampling is not None
-        processed = edits is not None
-        scored = scoring is not None
-        guided = guides is not None
         if lora_slots is not None:
-            return self._forward_step_lora(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                                           prefill_ctx_lens, edits, lora_slots, scoring, guides)
-        la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling, processed,
-                                  scoring, guided)
+            return self._forward_step_lora(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts,
+                                           prefill_ctx_lens, lora_slots)
+        la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts)
         if la is not None:      # the step that was prepared while the previous one ran: blocks, then the launch
             self.gpu_block_manager.allocate_blocks_for_seqs(la.seq_ids, la.lens)   # (the real sequences only)
-            if processed:       # (the entries change every step: they go up before every replay)
-                self._upload_edits(edits, la.plan.batch_size)
-            if guided:          # (so do the mask rows)
-                self._upload_guides(guides, la.plan.batch_size)
-            tokens = self._forward_decode_graph(la.plan, la.dev, sampled, processed, scored, guided)
-            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens, sampling, processed, scoring, guided)
-            if self.after_launch_hook is not None:
-                self.after_launch_hook()
-            t4 = time.perf_counter() if prof is not None else 0.0
-            out = self._tokens_to_host(tokens, scoring)
-            if nxt is not None:
-                nxt.tokens = out
-            self._lookahead = nxt
-            if prof is not None:
-                for name, dt in (("launch", t4 - t0), ("wait_tokens", time.perf_counter() - t4), ("calls", 1.0),
-                                 ("lookahead_hits", 1.0)):
-                    prof[name] = prof.get(name, 0.0) + dt
-            return out
-        num_real = len(input_ids_list)
-        graph_step = (len(decoding_seq_lens_list) == num_real and not ignore_kvcache
-                      and getattr(self.engine_config, "use_hip_graph", False))
-        if graph_step or (self._eager_uses_graph_buckets and len(decoding_seq_lens_list) == num_real and not ignore_kvcache):
-            # pure decode on the replay path: the batch is rounded up to its bucket with inert rows (_decode_batch_bucket)
-            plan = self._plan_decode(seq_ids_list, list(decoding_seq_lens_list), input_ids_list, True)
+            self._logits.upload(opts, la.plan.batch_size, hit=True)
+            tokens = self._forward_decode_graph(la.plan, la.dev, opts)
+            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens, opts)
         else:
-            plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
-                              self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
-        dev, t1, t2 = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits, scoring, guides)
-        t3 = time.perf_counter() if prof is not None else 0.0
-        pure_decode = plan.num_prefill_seqs == 0
-        nxt = None
-        if (pure_decode and not ignore_kvcache and getattr(self.engine_config, "use_hip_graph", False)):
-            tokens = self._forward_decode_graph(plan, dev, sampled, processed, scored, guided)
-            if self._decode_lookahead:
-                nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens, sampling, processed, scoring, guided)
-        else:
-            if pure_decode and not ignore_kvcache and self._eager_uses_graph_buckets:
-                plan.seq_block_size, plan.num_seq_blocks = self._graph_bucket(plan)
-            tokens = self._forward(dev["input_ids"],
-                                   self._make_infer_state(plan, dev, ignore_kvcache, sampled, processed,
-                                                          scored=scored, guided=guided))[:num_real]
-            tap = self.post_layer.logits_tap
-            if tap and plan.batch_size > num_real:      # (tests) a padded eager step: the real rows only, as on replay
-                tap[-1] = tap[-1][:num_real]
+            num_real = len(input_ids_list)
+            pure_decode = len(decoding_seq_lens_list) == num_real and not ignore_kvcache
+            graph_step = pure_decode and self._use_hip_graph
+            if graph_step or (pure_decode and self._eager_uses_graph_buckets):
+                # pure decode on the replay path: the batch is rounded up to its bucket with inert rows (_decode_batch_bucket)
+                plan = self._plan_decode(seq_ids_list, list(decoding_seq_lens_list), input_ids_list, True)
+            else:
+                plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
+                                  self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
+            dev, t1, t2 = self._begin_step(plan, seq_ids_list, ignore_kvcache, opts)
+            t3 = time.perf_counter() if prof is not None else 0.0
+            nxt = None
+            if graph_step:
+                tokens = self._forward_decode_graph(plan, dev, opts)
+                if self._decode_lookahead:
+                    nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens, opts)
+            else:
+                if pure_decode and self._eager_uses_graph_buckets:
+                    plan.seq_block_size, plan.num_seq_blocks = self._graph_bucket(plan)
+                tokens = self._forward(dev["input_ids"], self._make_infer_state(plan, dev, ignore_kvcache, opts))[:num_real]
+                tap = self.post_layer.logits_tap
+                if tap and plan.batch_size > num_real:      # (tests) a padded eager step: the real rows only, as on replay
+                    tap[-1] = tap[-1][:num_real]
         if self.after_launch_hook is not None:
             self.after_launch_hook()
-        if prof is None:
-            out = self._tokens_to_host(tokens, scoring)
-            if nxt is not None:
-                nxt.tokens = out
-            self._lookahead = nxt
-            return out
-        t4 = time.perf_counter()
-        out = self._tokens_to_host(tokens, scoring)
-        t5 = time.perf_counter()
+        t4 = time.perf_counter() if prof is not None else 0.0
+        out = self._tokens_to_host(tokens, opts.scoring)
         if nxt is not None:
             nxt.tokens = out
         self._lookahead = nxt
-        for name, dt in (("plan", t1 - t0), ("blocks", t2 - t1), ("upload", t3 - t2), ("launch", t4 - t3),
-                         ("wait_tokens", t5 - t4), ("calls", 1.0)):
-            prof[name] = prof.get(name, 0.0) + dt
+        if prof is not None:
+            t5 = time.perf_counter()
+            sections = ((("launch", t4 - t0), ("lookahead_hits", 1.0)) if la is not None else      # (a hit: all of it is launch)
+                        (("plan", t1 - t0), ("blocks", t2 - t1), ("upload", t3 - t2), ("launch", t4 - t3)))
+            for name, dt in sections + (("wait_tokens", t5 - t4), ("calls", 1.0)):
+                prof[name] = prof.get(name, 0.0) + dt
         return out
 
-    def _forward_step_lora(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, sampling,
-                           prefill_ctx_lens, edits, lora_slots, scoring=None, guides=None):
+    def _forward_step_lora(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts,
+                           prefill_ctx_lens, lora_slots):
         """A step with at least one adapter row: the plain plan of the batch (never padded to a replay bucket), eager
         launches, the prepared look-ahead dropped; the row -> slot tiles go up in a buffer of their own."""
         self._lookahead = None
         num_real = len(input_ids_list)
         plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                           self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
-        dev = self._begin_step(plan, seq_ids_list, ignore_kvcache, sampling, edits, scoring, guides)[0]
+        dev = self._begin_step(plan, seq_ids_list, ignore_kvcache, opts)[0]
         num_prefill = num_real - len(decoding_seq_lens_list)
         row_slots = rows_of_sequences(lora_slots, [len(ids) for ids in input_ids_list[:num_prefill]])
-        state = self._make_infer_state(plan, dev, ignore_kvcache, sampling is not None, edits is not None,
-                                       scored=scoring is not None, guided=guides is not None)
+        state = self._make_infer_state(plan, dev, ignore_kvcache, opts)
         state.lora = LoraStep(LoraBatch(row_slots, self.lora_store.max_loras, self.device, self._lora_staging),
                               self.lora_store.layers)
         tokens = self._forward(dev["input_ids"], state)[:num_real]
@@ -1246,7 +1044,7 @@ class LlamaModel:
             self.after_launch_hook()
         if self._host_prof is not None:
             self._host_prof["calls"] = self._host_prof.get("calls", 0.0) + 1.0
-        return self._tokens_to_host(tokens, scoring)
+        return self._tokens_to_host(tokens, opts.scoring)
 
     @torch.inference_mode()
     def forward_verify(self, input_ids_list: List[List[int]], seq_ids_list: List[int],
@@ -1294,7 +1092,7 @@ class LlamaModel:
         self.gpu_block_manager.host.surplus_ok.update(seq_ids_list)     # rejected drafts leave their block with the sequence
         plan = plan_verify(input_ids_list, seq_ids_list, ctx, self.model_config.num_kv_heads, self._num_slots)
         dev = self._begin_step(plan, seq_ids_list)[0]
-        tokens = self._forward(dev["input_ids"], self._make_infer_state(plan, dev, False, scratch_rows=plan.num_tokens))
+        tokens = self._forward(dev["input_ids"], self._make_infer_state(plan, dev, False, PLAIN, plan.num_tokens))
         if self.after_launch_hook is not None:
             self.after_launch_hook()
         flat = tokens.tolist()

@@ -218,7 +218,7 @@ STEPS = 24
 SEQS = [3, 0, 5, 1]
 
 
-def _model(tmp_path, dtype, graph=False, **kw):
+def _model(tmp_path, dtype, graph=False, guide_vocab=None, **kw):
     from swiftllm_amd import EngineConfig, LlamaModel
     cfg = synth.make_config()           # TINY
     path = tmp_path / f"tiny_{dtype}"
@@ -230,6 +230,8 @@ def _model(tmp_path, dtype, graph=False, **kw):
                 use_hip_graph=graph)
     base.update(kw)
     model = LlamaModel(EngineConfig(**base))
+    if guide_vocab is not None:
+        model.set_guide_vocab(guide_vocab(cfg["vocab_size"]))
     model.load_weights()
     model.init_kvcache_and_swap(40)
     model._eager_uses_graph_buckets = True      # eager steps at the replay path's batch bucket and split geometry
@@ -381,9 +383,11 @@ def test_entry_buffer_growth_drops_the_graphs_and_the_stream_goes_on(tmp_path, d
     want, _ = _generate(eager, prompts, sps)
     del eager
     graph, _ = _model(tmp_path, dtype, graph=True)
-    graph._MIN_EDIT_CAP, graph._ONE_COPY_WORDS = 8, 16
-    graph._edit_dev = graph._edit_host = graph._edit_host_np = None     # (allocated at load with the class's capacity)
-    graph._edit_rows_cap = 0
+    from swiftllm_amd.worker.step_logits import StagedInts
+    stage = graph._logits
+    stage.min_edit_cap, stage.one_copy_words = 8, 16
+    stage.edits = StagedInts(graph._drop_decode_graphs)     # (allocated at load with the class's capacity)
+    stage.edit_rows = 0
     hits = _count_lookahead_hits(graph)
     log = []            # per forward: (buffer words, captures so far, look-ahead hits so far, graphs cached before the call)
     inner = graph.forward
@@ -391,7 +395,7 @@ def test_entry_buffer_growth_drops_the_graphs_and_the_stream_goes_on(tmp_path, d
     def spy(*a, **kw):
         cached = len(graph._decode_graphs)
         out = inner(*a, **kw)
-        log.append((graph._edit_dev.numel(), graph.graph_captures, hits[0], cached))
+        log.append((stage.edits.dev.numel(), graph.graph_captures, hits[0], cached))
         return out
     graph.forward = spy
     assert _generate(graph, prompts, sps)[0] == want
@@ -401,6 +405,70 @@ def test_entry_buffer_growth_drops_the_graphs_and_the_stream_goes_on(tmp_path, d
     k = grown[0]
     assert log[k][2] == log[k - 1][2] + 1                               # ... on a look-ahead hit
     assert log[k][3] >= 1 and log[k][1] == log[k - 1][1] + 1            # a graph was cached; the step was captured again
+
+
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
+def test_every_staged_buffer_can_move_under_captured_graphs(tmp_path, dtype):
+    """All four logits options across one batch — a plain row, a penalised greedy row that asks for logprobs, a guided row
+    and a seeded sampled row with min-p — on a replay model whose four staged buffers start over at ONE row (the edit
+    buffer at 8 entries, in pieces beyond 16 words): every buffer outgrows itself under captured graphs, and the stream and
+    its logprobs are the eager model's."""
+    from _guided_ref import synthetic_vocab
+    from swiftllm_amd.guided import GuideCursor, guide_key
+    from swiftllm_amd.worker.step_logits import StagedInts
+    allowed = [3, 40, 41, 97, 200, 251]
+    # (the penalised row is the 5-token prompt: one entry per token it has seen, so 8 entries and then 16 are outgrown
+    # within the first dozen decode steps)
+    sps = [_sp(repetition_penalty=1.3, presence_penalty=0.4, frequency_penalty=0.1, logprobs=5), None,
+           _sp(allowed_token_ids=allowed), _sp(0.9, seed=1234, min_p=0.1)]
+
+    def stream(model, watch=None):
+        cur = GuideCursor(model.guide_store.acquire(guide_key("tokens", allowed, ())))
+        guides, lens = [None, None, cur, None], list(LENS)
+        toks = [model.forward(prompts, SEQS, [], sampling_params=sps, guides=guides)]
+        scores = [model.last_logprobs]
+        for _ in range(STEPS):
+            cur.advance(toks[-1][2])
+            lens = [n + 1 for n in lens]
+            toks.append(model.forward([[t] for t in toks[-1]], SEQS, lens, sampling_params=sps, guides=guides))
+            scores.append(model.last_logprobs)
+            if watch is not None:
+                watch()
+        model.free_seqs_resources(SEQS)
+        model.guide_store.release(cur.guide)
+        return toks, scores
+
+    def build(graph):
+        return _model(tmp_path, dtype, graph=graph, guided_max_states=8, guide_vocab=lambda v: synthetic_vocab(v, seed=3))
+
+    eager, cfg = build(False)
+    prompts = _prompts(cfg["vocab_size"])
+    want, want_scores = stream(eager)
+    assert all(t[2] in allowed for t in want) and len({t[3] for t in want}) > 1
+    del eager
+    graph, _ = build(True)
+    stage, drop = graph._logits, graph._drop_decode_graphs
+    stage.min_edit_cap, stage.one_copy_words, stage.edit_rows = 8, 16, 0
+    stage.sampling, stage.edits = StagedInts(drop), StagedInts(drop)
+    stage.scores = StagedInts(drop, idle=-1, tail=stage.scores.tail)
+    stage.guide_rows = StagedInts(drop, idle=-1)
+    stage.reserve(1)
+    rows = lambda: (stage.sampling.words // 5, stage.edit_rows, stage.scores.words, stage.guide_rows.words)   # noqa: E731
+    assert rows() == (1, 1, 1, 1)
+    hits = _count_lookahead_hits(graph)
+    log = []        # per decode step: (edit buffer words, captures so far)
+    got, got_scores = stream(graph, lambda: log.append((stage.edits.words, graph.graph_captures)))
+    assert got == want
+    for step, (a, b) in enumerate(zip(got_scores, want_scores)):
+        assert [s is None for s in a] == [s is None for s in b] == [False, True, True, True], step
+        a, b = a[0], b[0]
+        assert (a.token_id, a.rank, [i for i, _ in a.top]) == (b.token_id, b.rank, [i for i, _ in b.top]), step
+        for x, y in zip((a.logprob,) + tuple(v for _, v in a.top), (b.logprob,) + tuple(v for _, v in b.top)):
+            assert abs(x - y) <= 2e-5 + 2.0 ** -22 * abs(y), (step, x, y)       # (test_gpu_logprobs._tol)
+    assert all(n >= 4 for n in rows()), rows()
+    grown = [k for k in range(1, len(log)) if log[k][0] > log[k - 1][0]]
+    assert grown and log[grown[0]][1] > log[grown[0] - 1][1]            # a growth between decode steps: captured again
+    assert hits[0] >= STEPS - 1         # every decode step but the first is the prepared one, the growing ones too
 
 
 def test_model_refuses_rows_without_a_history_and_verify_on_tracked_sequences(tmp_path):
