@@ -90,6 +90,24 @@ int swl_rotary(void *q, void *k, const void *cos_table, const void *sin_table,
                int32_t num_kv_heads, int32_t head_dim, int64_t q_tok_stride, int64_t k_tok_stride,
                int32_t dtype, swl_stream_t stream);
 
+/* ---- Projection bias + per-head QK RMSNorm + rotary (csrc/qk_prep.hip; no reference counterpart) ------------------
+ * What Qwen2 / Qwen2.5 (bias on q/k/v_proj) and Qwen3 (RMSNorm over head_dim on q and k) put between the projections
+ * and the KV store, in ONE launch, in place on q[T, H, D], k[T, KVH, D], v[T, KVH, D] (token strides as in swl_rotary).
+ * Table row of token t: pos_idx ? pos_idx[t] : t; a negative row is an inert row of a padded batch — q, k and v of that
+ * token keep their bits. Per (token, q or k head), in fp32 from the stored 16-bit values with nothing rounded in between:
+ *   f_i = x_i + bias[h*D + i]                                    (q_bias [H*D] / k_bias [KVH*D], each or NULL)
+ *   r = 1 / sqrt(sum_i f_i^2 / D + eps);  f_i = f_i * r * w_i    (q_norm_w / k_norm_w [D]: both or neither; fixed order)
+ *   y_i = f_i*c_i - f_{i+D/2}*s_i ;  y_{i+D/2} = f_{i+D/2}*c_i + f_i*s_i   (i < D/2)
+ *   x_i = round-to-nearest-even(y_i)
+ * v_i = rne(v_i + v_bias_i) when v_bias [KVH*D] is given; otherwise v is not touched and may be NULL. No scratch, no
+ * atomics, capturable; a row's bits do not depend on the batch. D in {32, 64, 128, 256}; checks as swl_rotary; a single
+ * norm weight without its twin: SWL_ERR_BAD_ARG; num_tokens == 0: SWL_OK, nothing launched. */
+int swl_qk_prep_rotary(void *q, void *k, void *v, const void *q_bias, const void *k_bias, const void *v_bias,
+                       const void *q_norm_w, const void *k_norm_w, float eps, const void *cos_table,
+                       const void *sin_table, const int32_t *pos_idx, int64_t num_tokens, int32_t num_q_heads,
+                       int32_t num_kv_heads, int32_t head_dim, int64_t q_tok_stride, int64_t k_tok_stride,
+                       int64_t v_tok_stride, int32_t dtype, swl_stream_t stream);
+
 /* ---- KV-cache store -----------------------------------------------------------------------
  * reference: kvcache_mgmt.py:10-48 (_fwd_kvcache_mgmt_prefill_kernel), launcher :81-109
  * For prefill seq s (id seq_ids[s], tokens [start_locs[s], +seq_lens[s]) of k/v), logical block j:

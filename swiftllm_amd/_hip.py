@@ -152,6 +152,10 @@ _SPECIAL = {
     # registered here for the same reason (their own contract: tests/test_guided_abi.py, tests/test_gpu_guided.py).
     "swl_guide_build_masks": ([_P, _I64, _I64, _I32, _P, _P, _P, _P, _I32, _P, _I32, _P], _I32),
     "swl_logits_mask": ([_P, _I64, _I32, _I64, _I32, _P, _I64, _I32, _P, _P], _I32),
+    # Projection bias + per-head QK RMSNorm + rotary (csrc/qk_prep.hip; Qwen2 / Qwen3): an "int rc = f(...)" entry too,
+    # registered here for the same reason (its own contract: tests/test_qk_prep_abi.py, tests/test_gpu_qk_prep.py).
+    "swl_qk_prep_rotary": ([_P, _P, _P, _P, _P, _P, _P, _P, _F32, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I64, _I64,
+                            _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

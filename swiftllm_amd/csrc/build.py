@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 SOURCES = [
     "rmsnorm.hip",
     "rotary.hip",
+    "qk_prep.hip",
     "kvcache.hip",
     "silu_mul.hip",
     "paged_attn.hip",

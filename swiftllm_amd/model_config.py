@@ -1,21 +1,35 @@
 """LlamaModelConfig — architecture hyper-parameters read from a HuggingFace `config.json`.
 
-Mirrors swiftllm/model_config.py:5-46 (attribute names, defaults, kv-slot size formula)."""
+Mirrors swiftllm/model_config.py:5-46 (attribute names, defaults, kv-slot size formula). Beyond the reference it also
+reads the Llama-shaped families whose differences sit between the q/k/v projections and attention: Mistral (optional
+`head_dim`, optional `sliding_window`), Qwen2 / Qwen2.5 (bias on q/k/v_proj) and dense Qwen3 (per-head RMSNorm on q and k,
+`head_dim` given in the config). What those checkpoints may ask for and this project does not build is refused here, with
+the reason, before any memory is touched."""
 import json
 import os
 
 import torch
 
+MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")
+MOE_TYPES = ("mixtral", "qwen2_moe", "qwen3_moe")
+# the attention kernels' tiles: q heads per kv head, and head_dim
+GROUP_SIZES = (1, 2, 4, 8)
+HEAD_DIMS = (32, 64, 128)
+
 
 class LlamaModelConfig:
-    """LLaMA 1/2/3 configuration. Attribute names follow the reference so layer/kernel code and
-    user scripts that poke at `model.model_config` keep working."""
+    """LLaMA 1/2/3, Mistral, Qwen2 / Qwen2.5 and dense Qwen3 configuration. Attribute names follow the reference so
+    layer/kernel code and user scripts that poke at `model.model_config` keep working."""
 
     def __init__(self, model_config: dict):
-        if model_config["model_type"] != "llama":
-            raise AssertionError(f"unsupported model_type {model_config['model_type']!r}")
+        model_type = model_config["model_type"]
+        if model_type in MOE_TYPES:
+            raise ValueError(f"model_type {model_type!r} is a mixture-of-experts variant; only the dense models are built")
+        if model_type not in MODEL_TYPES:
+            raise AssertionError(f"unsupported model_type {model_type!r}")
         if model_config["hidden_act"] != "silu":
             raise AssertionError(f"unsupported hidden_act {model_config['hidden_act']!r}")
+        self.model_type = model_type
         self.num_layers = model_config["num_hidden_layers"]
         self.num_q_heads = model_config["num_attention_heads"]
         self.num_kv_heads = model_config.get("num_key_value_heads", self.num_q_heads)
@@ -29,6 +43,50 @@ class LlamaModelConfig:
         self.rms_norm_eps = model_config["rms_norm_eps"]
         scaling = model_config.get("rope_scaling", 1.0)
         self.rope_scaling = 1.0 if scaling is None else scaling
+        # q/k/v_proj carry a bias; q and k get a per-head RMSNorm before rotary; lm_head is the embedding
+        self.qkv_bias = self.qk_norm = self.tie_word_embeddings = False
+        self.sliding_window = None      # the window that capped max_position_embeddings, when one applies
+        if model_type != "llama":
+            self._init_family(model_config)
+        self.q_size = self.num_q_heads * self.head_dim
+
+    def _init_family(self, c: dict):
+        """Mistral, Qwen2 and Qwen3: the fields Llama's parsing above does not read, and the refusals."""
+        kind = self.model_type
+        if c.get("head_dim") is not None:
+            self.head_dim = int(c["head_dim"])
+        self.qkv_bias = kind == "qwen2"
+        self.qk_norm = kind == "qwen3"
+        self.tie_word_embeddings = bool(c.get("tie_word_embeddings", False))
+        # transformers 5 writes rope_theta (and the rope type) into rope_parameters
+        rope = c.get("rope_parameters") or {}
+        if "rope_theta" not in c and rope.get("rope_theta") is not None:
+            self.rope_theta = self.rotary_base = rope["rope_theta"]
+        for field in ("rope_scaling", "rope_parameters"):
+            spec = c.get(field)
+            if isinstance(spec, dict):
+                rope_type = spec.get("rope_type", spec.get("type", "default"))
+                if rope_type not in (None, "default"):
+                    raise ValueError(f"{kind}: {field} asks for rope_type {rope_type!r}; only the default rotary embedding "
+                                     "is built (no YaRN, linear, dynamic or long-rope scaling)")
+        self.rope_scaling = 1.0
+        if c.get("attention_bias") and kind != "qwen2":
+            raise ValueError(f"{kind}: attention_bias is true, which puts a bias on o_proj as well; the o_proj bias is not built")
+        if c.get("mlp_bias"):
+            raise ValueError(f"{kind}: mlp_bias is true; biases on the MLP projections are not built")
+        if self.num_kv_heads <= 0 or self.num_q_heads % self.num_kv_heads or self.num_q_heads // self.num_kv_heads not in GROUP_SIZES:
+            raise ValueError(f"{kind}: {self.num_q_heads} query heads over {self.num_kv_heads} key/value heads is a ratio of "
+                             f"{self.num_q_heads / max(self.num_kv_heads, 1):g}; the attention kernels are built for the "
+                             f"ratios {GROUP_SIZES}")
+        if self.head_dim not in HEAD_DIMS:
+            raise ValueError(f"{kind}: head_dim {self.head_dim}; the attention kernels are built for head_dim in {HEAD_DIMS}")
+        # Inside the window, windowed and full attention are the same function: serve the window and nothing beyond it
+        # (the engine refuses requests that outgrow the rope table). No windowed attention kernel is built.
+        window = c.get("sliding_window")
+        if window is not None and (kind == "mistral" or c.get("use_sliding_window")) and window < self.max_position_embeddings:
+            print(f"[ModelConfig] {kind}: sliding_window {window} < max_position_embeddings {self.max_position_embeddings}: "
+                  f"serving contexts up to {window} tokens (no windowed attention beyond the window)", flush=True)
+            self.max_position_embeddings = self.sliding_window = int(window)
 
     def get_kvslot_size(self, dtype: torch.dtype = torch.float16) -> int:
         """Bytes of KV cache one token occupies (K and V, all layers); `dtype` is the POOL's element type (1 byte for

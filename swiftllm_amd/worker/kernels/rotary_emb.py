@@ -42,6 +42,37 @@ def rotary_embedding_inplace(q: torch.Tensor, k: torch.Tensor, infer_state):
               token_stride(q, "q"), token_stride(k, "k"), _hip.dtype_code(q.dtype), _hip.stream())
 
 
+def qk_prep_rotary_inplace(q: torch.Tensor, k: torch.Tensor, v, infer_state, *, q_bias=None, k_bias=None, v_bias=None,
+                           q_norm=None, k_norm=None, eps: float = 0.0):
+    """What Qwen2 / Qwen2.5 and Qwen3 put where Llama has `rotary_embedding_inplace`: the projection biases ([H*D],
+    [KVH*D], [KVH*D]) added to q, k and v, the per-head RMSNorm of q and k (weights [D], both or neither), then rotate-half
+    RoPE — one launch, in place, fp32 inside with one rounding at the end (csrc/qk_prep.hip). `v` is touched only with a
+    `v_bias`. The rope tables and positions are taken from `infer_state` as `rotary_embedding_inplace` takes them."""
+    _hip.require_gpu_tensor(q, "q")
+    num_tokens = q.shape[0]
+    if num_tokens == 0:
+        return
+    cos, sin = infer_state.position_cos, infer_state.position_sin
+    pos_idx = getattr(infer_state, "position_indices", None)
+    h, kvh, d = q.shape[1], k.shape[1], q.shape[2]
+    assert cos.is_contiguous() and sin.is_contiguous() and cos.dtype == q.dtype == k.dtype
+    assert cos.shape[-1] * 2 == d == k.shape[2]
+    if pos_idx is None:
+        assert cos.shape[0] == num_tokens
+    else:
+        assert pos_idx.dtype == torch.int32 and pos_idx.is_contiguous() and pos_idx.numel() == num_tokens
+    for t, n, what in ((q_bias, h * d, "q_bias"), (k_bias, kvh * d, "k_bias"), (v_bias, kvh * d, "v_bias"),
+                       (q_norm, d, "q_norm"), (k_norm, d, "k_norm")):
+        assert t is None or (t.dtype == q.dtype and t.is_contiguous() and t.numel() == n and t.device == q.device), what
+    if v_bias is not None:
+        assert v is not None and v.dtype == q.dtype and tuple(v.shape) == tuple(k.shape)
+    _hip.call("swl_qk_prep_rotary", _hip.ptr(q), _hip.ptr(k), _hip.ptr(v if v_bias is not None else None),
+              _hip.ptr(q_bias), _hip.ptr(k_bias), _hip.ptr(v_bias), _hip.ptr(q_norm), _hip.ptr(k_norm), float(eps),
+              _hip.ptr(cos), _hip.ptr(sin), _hip.ptr(pos_idx), num_tokens, h, kvh, d,
+              token_stride(q, "q"), token_stride(k, "k"), token_stride(v, "v") if v_bias is not None else 0,
+              _hip.dtype_code(q.dtype), _hip.stream())
+
+
 def rotary_embedding_and_store_kvcache_decode(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                                               k_cache: torch.Tensor, v_cache: torch.Tensor,
                                               block_table: torch.Tensor, model_config,

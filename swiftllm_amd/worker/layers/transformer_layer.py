@@ -23,8 +23,12 @@ Launches per layer by route (pure decode of m sequences unless said; default swi
 | PLAIN, PLAIN, QKV.FUSED_DECODE    | fuse_splitk_consumers or use_skinny_gemm off     | add_norm, q/k/v, rotary+store, attention, o, add_norm, up_gate (+ silu), down |
 | PLAIN, PLAIN, QKV.FUSED_PREFILL   | a prompt row in the batch                        | the same with the prompt rotary+store and prefill attention (riding decodes on the side stream) |
 | PLAIN, PLAIN, QKV.ROTARY_THEN_STORE | FP8 pools, fuse_rope_kvstore off, no positions | ... rotary, (quantising) store ... (QKV.ROTARY_ONLY: ignore_kvcache) |
+| SPLITK_FUSED (or _DEFERRED), SPLITK, QKV.ROTARY_THEN_STORE | plain_qkv (Qwen2 / Qwen3 / q_size != hidden)          | add_norm, qkv, prep, store, attention, o, add_norm (or add_scale), silu_gate, down: 9 (as FP8 pools) |
+| PLAIN, PLAIN, QKV.ROTARY_THEN_STORE | plain_qkv, a prompt row (or the switches above off) | add_norm, q/k/v, prep, store, attention, o, add_norm, up_gate (+ silu), down |
 | lora                              | some row names an adapter                        | the plain sequence with the adapter update after every projection |
 
+"prep" is the one launch between the projections and the store: bias + per-head QK-norm + rotary (swl_qk_prep_rotary) for
+a model with a q/k/v bias or a QK-norm, swl_rotary for one that only decouples q_size from hidden (Mistral-Nemo).
 The first layer of a step receives a tensor, so its input norm is the fused add+norm whatever the route of the others.
 """
 import enum
@@ -39,7 +43,7 @@ from ..kernels.linear import (RawResidual, SplitKPartials, _TINY_MAX_KC, _TINY_P
                               linear_splitk_from_splitk, linear_splitk_nf, linear_splitk_nx)
 from ..kernels.rmsnorm import (RowScalePending, add_scale_from_splitk, deferred_norm_ok, fused_add_rmsnorm_inplace,
                                fused_add_rmsnorm_from_splitk)
-from ..kernels.rotary_emb import (rotary_embedding_inplace, rotary_embedding_and_store_kvcache_decode,
+from ..kernels.rotary_emb import (qk_prep_rotary_inplace, rotary_embedding_inplace, rotary_embedding_and_store_kvcache_decode,
                                   rotary_embedding_and_store_kvcache_decode_from_splitk,
                                   rotary_embedding_and_store_kvcache_prefill)
 from ..kernels.kvcache_mgmt import store_kvcache
@@ -141,9 +145,13 @@ class LayerFacts(NamedTuple):
     fly_ffn: bool               # the SiLU-gate GEMM can apply a norm itself (NF / NX / pending row scale)
     tiny: bool                  # qkv and up/gate can sum the previous projection's slabs themselves
     merge: bool                 # o_proj can merge flash-decoding partials itself
+    # the model has a q/k/v bias, a per-head QK-norm, or q_size != hidden (Qwen2, Qwen3, Mistral-Nemo): q/k/v stay plain
+    # tensors up to the store — none of the forms that consume the qkv projection's slabs, and no rotary + store fusion
+    plain_qkv: bool = False
 
 
-def layer_facts(engine_config, dtype, hidden: int, num_q_heads: int, head_dim: int, shapes: dict, packed, lib) -> LayerFacts:
+def layer_facts(engine_config, dtype, hidden: int, num_q_heads: int, head_dim: int, shapes: dict, packed, lib,
+                plain_qkv: bool = False) -> LayerFacts:
     """`shapes`: (N, K) of "qkv" (absent without the fused projection), "o", "up_gate", "down"; `packed`: the names that
     carry a packed twin; `lib`: the loaded library, asked for its host arithmetic only (split counts, shape support)."""
     def takes(name):            # the weight-streaming GEMMs take the shape
@@ -173,7 +181,8 @@ def layer_facts(engine_config, dtype, hidden: int, num_q_heads: int, head_dim: i
               and splits("qkv", True) in (1, 2, 4) and chunked("qkv", splits("qkv", True))
               and up_n % 128 == 0 and up_k % 128 == 0 and up_k <= _TINY_MAX_KC and splits("o", True) > 1 and splits("down", True) > 1),
         merge=("o" in packed and head_dim % 8 == 0 and shapes["o"][1] == num_q_heads * head_dim
-               and splits("o", True) > 1 and chunked("o", splits("o", True))))
+               and splits("o", True) > 1 and chunked("o", splits("o", True))),
+        plain_qkv=bool(plain_qkv))
 
 
 def decide_route(f: LayerFacts, s: StepFacts) -> LayerRoute:
@@ -182,7 +191,7 @@ def decide_route(f: LayerFacts, s: StepFacts) -> LayerRoute:
     attention = Attn.DECODE if not s.prefill else Attn.VERIFY if s.verify else Attn.PAGED if s.chunked else Attn.FRESH
     # rotary + KV store can be one launch; the projections' slabs can go to fused consumers; ... to the attention prologue
     # (a LoRA step takes none of the fused forms: they consume a projection's output before a delta could be added)
-    rope_store = not (s.lora or s.ignore_kvcache or f.kv_fp8) and s.positions and f.tuning.fuse_rope_kvstore
+    rope_store = not (s.lora or s.ignore_kvcache or f.kv_fp8 or f.plain_qkv) and s.positions and f.tuning.fuse_rope_kvstore
     fast = f.skinny and not (s.lora or s.prefill) and s.m > 0 and f.tuning.fuse_splitk_consumers
     slab_attn = (fast and rope_store and f.fused_qkv and f.tuning.fuse_rope_into_attention and f.head_dim in (32, 64, 128)
                  and s.m <= 256)      # (batches the slab-producing GEMMs serve)
@@ -240,10 +249,12 @@ class LlamaTransformerLayer:
         the packed twins of the weights are rebuilt (LlamaModel.repack_decode_weights)."""
         cfg, w = self.model_config, self.weight
         named = dict(qkv=w.qkv_proj, o=w.o_proj, up_gate=w.up_gate_proj, down=w.down_proj)
+        # bias + QK-norm + rotary in one launch where the model has either (Qwen2 / Qwen3); otherwise swl_rotary
+        self.qk_prep = getattr(w, "q_norm", None) is not None or getattr(w, "q_bias", None) is not None
         self.facts = layer_facts(self.engine_config, w.o_proj.dtype, cfg.hidden_size, cfg.num_q_heads, cfg.head_dim,
                                  {name: tuple(t.shape) for name, t in named.items() if t is not None},
                                  {name for name, t in named.items() if getattr(t, "_swl_packed", None) is not None},
-                                 _hip.load())
+                                 _hip.load(), plain_qkv=self.qk_prep or cfg.num_q_heads * cfg.head_dim != cfg.hidden_size)
         self._routes = {}           # StepFacts -> LayerRoute
 
     def route(self, input_embds, st) -> LayerRoute:
@@ -272,6 +283,21 @@ class LlamaTransformerLayer:
         return (linear(x, w.q_proj, sk).view(t, cfg.num_q_heads, cfg.head_dim),
                 linear(x, w.k_proj, sk).view(t, cfg.num_kv_heads, cfg.head_dim),
                 linear(x, w.v_proj, sk).view(t, cfg.num_kv_heads, cfg.head_dim))
+
+    def _rotary(self, q, k, v, st):
+        """The launch between the projections and the KV store on the routes that keep the two apart."""
+        if not self.qk_prep:
+            rotary_embedding_inplace(q, k, st)
+            return
+        w = self.weight
+        qk_prep_rotary_inplace(q, k, v, st, q_bias=w.q_bias, k_bias=w.k_bias, v_bias=w.v_bias, q_norm=w.q_norm,
+                               k_norm=w.k_norm, eps=self.model_config.rms_norm_eps)
+
+    def _attn_out_like(self, x: torch.Tensor) -> torch.Tensor:
+        """The attention output buffer [tokens, q_size]: the (already consumed) normed activations themselves when they
+        have that width, a fresh buffer when q_size != hidden."""
+        qs = self.model_config.num_q_heads * self.model_config.head_dim
+        return x if x.shape[1] == qs else x.new_empty((x.shape[0], qs))
 
     def forward(self, input_embds, residual_buf: torch.Tensor, k_cache: torch.Tensor,
                 v_cache: torch.Tensor, block_table: torch.Tensor, infer_state):
@@ -331,9 +357,10 @@ class LlamaTransformerLayer:
             elif route.qkv is QKV.FUSED_PREFILL:
                 rotary_embedding_and_store_kvcache_prefill(q, k, v, *at)
             else:
-                rotary_embedding_inplace(q, k, st)
+                self._rotary(q, k, v, st)
                 if route.qkv is QKV.ROTARY_THEN_STORE:
                     store_kvcache(k, v, *at)
+        x = self._attn_out_like(x)
         self._attention(route, q, k, v, x.view(-1, cfg.num_q_heads, cfg.head_dim), k_cache, v_cache, block_table, st)
         return x
 
@@ -426,10 +453,11 @@ class LlamaTransformerLayer:
             lora_apply(x, v, groups.v_proj, batch)
             q = q.view(t, cfg.num_q_heads, cfg.head_dim)
             k, v = k.view(t, cfg.num_kv_heads, cfg.head_dim), v.view(t, cfg.num_kv_heads, cfg.head_dim)
-        rotary_embedding_inplace(q, k, st)
+        self._rotary(q, k, v, st)
         if route.qkv is QKV.ROTARY_THEN_STORE:
             store_kvcache(k, v, k_cache, v_cache, block_table, cfg, ecfg, st, self.layer_id)
-        # attention output overwrites the (already consumed) normed activations
+        # attention output overwrites the (already consumed) normed activations (a fresh buffer when q_size != hidden)
+        x = self._attn_out_like(x)
         self._attention(route, q, k, v, x.view(-1, cfg.num_q_heads, cfg.head_dim), k_cache, v_cache, block_table, st)
         q = k = v = qkv = None
 

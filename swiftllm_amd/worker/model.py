@@ -87,6 +87,13 @@ class LlamaModel:
         self.model_config = LlamaModelConfig.load_from_model_path(engine_config.model_path)
         self.dtype = _DTYPES[getattr(engine_config, "dtype", "float16")]
         self.device = torch.device("cuda")
+        cfg = self.model_config
+        # a q/k/v bias, a per-head QK-norm or q_size != hidden: the layers keep q/k/v plain up to the KV store
+        self.plain_qkv = bool(cfg.qkv_bias or cfg.qk_norm or cfg.q_size != cfg.hidden_size)
+        if self.plain_qkv and getattr(engine_config, "decode_engine", False):
+            raise ValueError(f"tuning={{'decode_engine': True}} cannot serve this {cfg.model_type} model: the persistent "
+                             "one-sequence step is laid out for Llama's projections (no q/k/v bias, no per-head QK-norm, "
+                             "q_proj as wide as hidden_size)")
         # element type of the KV pools: the activation dtype, or e4m3fn (EngineConfig.kv_cache_dtype = "fp8_e4m3")
         self.kv_fp8 = getattr(engine_config, "kv_cache_dtype", "auto") == "fp8_e4m3"
         self.kv_dtype = torch.float8_e4m3fn if self.kv_fp8 else self.dtype
@@ -489,7 +496,10 @@ class LlamaModel:
             freqs = torch.cat([torch.outer(t / low, inv_low), torch.outer(t / high, inv_high)], dim=-1)
         else:
             inv_freq = 1.0 / (base ** (torch.arange(0, dim, 2, device=dev, dtype=f32) / dim))
-            t = torch.arange(cfg.max_position_embeddings * scaling + 128, device=dev, dtype=f32) / scaling
+            rows = cfg.max_position_embeddings * scaling + 128
+            if getattr(cfg, "sliding_window", None) is not None:
+                rows = cfg.sliding_window   # exactly the window: beyond it full attention is no longer the model's function
+            t = torch.arange(rows, device=dev, dtype=f32) / scaling
             freqs = torch.outer(t, inv_freq)
         self._cos_cached = torch.cos(freqs).to(self.dtype).contiguous()
         self._sin_cached = torch.sin(freqs).to(self.dtype).contiguous()

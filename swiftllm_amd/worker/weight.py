@@ -6,7 +6,9 @@ shape checks, safetensors (single file or `model.safetensors.index.json`) prefer
 `up_proj`/`gate_proj` concatenated into `up_gate_proj` = [up ; gate] (weight.py:133), and the
 "rope_scaling is a dict => Llama-3.2 => lm_head tied to the embedding" sniff (weight.py:199-213).
 Differences: dtype and device are parameters (the reference hard-codes fp16 / "cuda"), and q/k/v can
-additionally be concatenated into one `qkv_proj` for a single fused projection GEMM.
+additionally be concatenated into one `qkv_proj` for a single fused projection GEMM. Beyond the reference: the Llama-shaped
+families of model_config.py — q_proj / o_proj sized by num_q_heads * head_dim (Qwen3, Mistral-Nemo), Qwen3's per-head
+q_norm / k_norm, Qwen2's q/k/v_proj biases, and a tied lm_head selected by `tie_word_embeddings`.
 """
 import json
 import os
@@ -21,21 +23,40 @@ class WeightSpec(NamedTuple):
     shape: Tuple[int, ...]
 
 
+def _q_size(cfg) -> int:
+    """Width of q_proj's output: num_q_heads * head_dim, which Qwen3 and Mistral-Nemo decouple from hidden_size."""
+    return cfg.num_q_heads * cfg.head_dim
+
+
 def layer_weight_specs(cfg, layer_id: int) -> List[WeightSpec]:
-    h, kv = cfg.hidden_size, cfg.num_kv_heads * cfg.head_dim
+    h, kv, qs = cfg.hidden_size, cfg.num_kv_heads * cfg.head_dim, _q_size(cfg)
     inter = cfg.ffn_inter_dim
     pre = f"model.layers.{layer_id}."
     return [
         WeightSpec("attn_norm", pre + "input_layernorm.weight", (h,)),
-        WeightSpec("q_proj", pre + "self_attn.q_proj.weight", (h, h)),
+        WeightSpec("q_proj", pre + "self_attn.q_proj.weight", (qs, h)),
         WeightSpec("k_proj", pre + "self_attn.k_proj.weight", (kv, h)),
         WeightSpec("v_proj", pre + "self_attn.v_proj.weight", (kv, h)),
-        WeightSpec("o_proj", pre + "self_attn.o_proj.weight", (h, h)),
+        WeightSpec("o_proj", pre + "self_attn.o_proj.weight", (h, qs)),
         WeightSpec("ffn_norm", pre + "post_attention_layernorm.weight", (h,)),
         WeightSpec("up_proj", pre + "mlp.up_proj.weight", (inter, h)),
         WeightSpec("gate_proj", pre + "mlp.gate_proj.weight", (inter, h)),
         WeightSpec("down_proj", pre + "mlp.down_proj.weight", (h, inter)),
-    ]
+    ] + layer_family_specs(cfg, layer_id)
+
+
+def layer_family_specs(cfg, layer_id: int) -> List[WeightSpec]:
+    """The per-layer tensors Llama does not have: Qwen3's per-head q/k RMSNorm weights, Qwen2's q/k/v_proj biases. They
+    are vectors — not projection_tensors(), never packed."""
+    kv, qs, d = cfg.num_kv_heads * cfg.head_dim, _q_size(cfg), cfg.head_dim
+    pre = f"model.layers.{layer_id}.self_attn."
+    out = []
+    if getattr(cfg, "qk_norm", False):
+        out += [WeightSpec("q_norm", pre + "q_norm.weight", (d,)), WeightSpec("k_norm", pre + "k_norm.weight", (d,))]
+    if getattr(cfg, "qkv_bias", False):
+        out += [WeightSpec("q_bias", pre + "q_proj.bias", (qs,)), WeightSpec("k_bias", pre + "k_proj.bias", (kv,)),
+                WeightSpec("v_bias", pre + "v_proj.bias", (kv,))]
+    return out
 
 
 def global_weight_specs(cfg, model_version: str) -> List[WeightSpec]:
@@ -62,13 +83,22 @@ def _fill(obj, specs: List[WeightSpec], getter: Getter, dtype: torch.dtype, devi
 
 class LlamaTransformerLayerWeight:
     """Weights of one transformer block: attn_norm, q/k/v/o_proj, ffn_norm, up_gate_proj, down_proj
-    (and qkv_proj = [q ; k ; v] when fused)."""
+    (and qkv_proj = [q ; k ; v] when fused). Qwen3: q_norm, k_norm [head_dim]. Qwen2: q_bias, k_bias, v_bias — with the
+    fused projection they are three slices of one qkv_bias = [q ; k ; v]."""
 
     def __init__(self, layer_id: int, model_config, dtype: torch.dtype):
         self.layer_id = layer_id
         self.model_config = model_config
         self.dtype = dtype
         self.qkv_proj = None
+        self.q_norm = self.k_norm = None
+        self.qkv_bias = self.q_bias = self.k_bias = self.v_bias = None
+
+    def slice_qkv_bias(self):
+        """q_bias / k_bias / v_bias as views of the assembled qkv_bias (what the kernel receives)."""
+        cfg = self.model_config
+        qs, kv = _q_size(cfg), cfg.num_kv_heads * cfg.head_dim
+        self.q_bias, self.k_bias, self.v_bias = self.qkv_bias[:qs], self.qkv_bias[qs:qs + kv], self.qkv_bias[qs + kv:]
 
     def load(self, getter: Getter, device: torch.device, fuse_qkv: bool):
         _fill(self, layer_weight_specs(self.model_config, self.layer_id), getter, self.dtype, device)
@@ -77,6 +107,9 @@ class LlamaTransformerLayerWeight:
         if fuse_qkv:
             self.qkv_proj = torch.cat((self.q_proj, self.k_proj, self.v_proj), dim=0).contiguous()
             del self.q_proj, self.k_proj, self.v_proj
+            if self.q_bias is not None:
+                self.qkv_bias = torch.cat((self.q_bias, self.k_bias, self.v_bias), dim=0).contiguous()
+                self.slice_qkv_bias()
 
 
 class LlamaWeight:
@@ -194,7 +227,7 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
     from concurrent.futures import ThreadPoolExecutor
     cfg, dtype = weight.model_config, weight.dtype
     table = _read_safetensors_index(model_path, files)
-    h, kv, inter = cfg.hidden_size, cfg.num_kv_heads * cfg.head_dim, cfg.ffn_inter_dim
+    h, kv, inter, qs = cfg.hidden_size, cfg.num_kv_heads * cfg.head_dim, cfg.ffn_inter_dim, _q_size(cfg)
 
     # destination plan: (checkpoint key, expected shape, destination tensor, first destination row)
     plan = []
@@ -218,14 +251,30 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
         plan.append((specs["up_proj"].key, specs["up_proj"].shape, layer.up_gate_proj, 0))
         plan.append((specs["gate_proj"].key, specs["gate_proj"].shape, layer.up_gate_proj, inter))
         if fuse_qkv:
-            layer.qkv_proj = dest((h + 2 * kv, h))          # [q ; k ; v]
-            for attr, row in (("q_proj", 0), ("k_proj", h), ("v_proj", h + kv)):
+            layer.qkv_proj = dest((qs + 2 * kv, h))         # [q ; k ; v]
+            for attr, row in (("q_proj", 0), ("k_proj", qs), ("v_proj", qs + kv)):
                 plan.append((specs[attr].key, specs[attr].shape, layer.qkv_proj, row))
         else:
             for attr in ("q_proj", "k_proj", "v_proj"):
                 t = dest(specs[attr].shape)
                 setattr(layer, attr, t)
                 plan.append((specs[attr].key, specs[attr].shape, t, 0))
+        for attr in ("q_norm", "k_norm"):                   # Qwen3
+            if attr in specs:
+                t = dest(specs[attr].shape)
+                setattr(layer, attr, t)
+                plan.append((specs[attr].key, specs[attr].shape, t, 0))
+        if "q_bias" in specs:                               # Qwen2
+            if fuse_qkv:
+                layer.qkv_bias = dest((qs + 2 * kv,))       # [q ; k ; v], assembled in place like qkv_proj
+                layer.slice_qkv_bias()
+                for attr, row in (("q_bias", 0), ("k_bias", qs), ("v_bias", qs + kv)):
+                    plan.append((specs[attr].key, specs[attr].shape, layer.qkv_bias, row))
+            else:
+                for attr in ("q_bias", "k_bias", "v_bias"):
+                    t = dest(specs[attr].shape)
+                    setattr(layer, attr, t)
+                    plan.append((specs[attr].key, specs[attr].shape, t, 0))
 
     # validate before moving a byte
     esize = torch.empty((), dtype=dtype).element_size()
@@ -307,12 +356,16 @@ def pack_decode_weights(weight: "LlamaWeight") -> int:
 
 
 def detect_model_version(model_path: str) -> str:
-    """'llama3.2' when config.json carries a dict-valued rope_scaling, else 'llama'."""
+    """'llama3.2' (lm_head tied to the embedding) when config.json carries a dict-valued rope_scaling, else 'llama'. The
+    other families (mistral, qwen2, qwen3) say it themselves: `tie_word_embeddings`."""
     cfg_path = os.path.join(model_path, "config.json")
     if os.path.exists(cfg_path):
         with open(cfg_path, "r", encoding="utf-8") as f:
-            if isinstance(json.load(f).get("rope_scaling"), dict):
-                return "llama3.2"
+            config = json.load(f)
+        if config.get("model_type", "llama") != "llama":
+            return "llama3.2" if config.get("tie_word_embeddings") else "llama"
+        if isinstance(config.get("rope_scaling"), dict):
+            return "llama3.2"
     return "llama"
 
 
@@ -323,7 +376,10 @@ def load_weights(model_config, dtype: torch.dtype, model_path: str, use_dummy: b
     reference's tensor-by-tensor safetensors path."""
     device = torch.device(device)
     if model_version == "auto":
-        model_version = detect_model_version(model_path)
+        if getattr(model_config, "model_type", "llama") != "llama":
+            model_version = "llama3.2" if model_config.tie_word_embeddings else "llama"
+        else:
+            model_version = detect_model_version(model_path)
     weight = LlamaWeight(model_config, dtype, model_version)
     if use_dummy:
         getter = _dummy_getter(dtype, device)
