@@ -114,6 +114,14 @@ def _mask_case(dtype, n, stride, rows, offset):
 @pytest.mark.parametrize("rows", [1, 7, 33])
 @pytest.mark.parametrize("offset", [0, 1])
 def test_mask_kernel_equals_the_reference_bit_for_bit(dtype, n, stride, rows, offset):
+    _hold_mask_kernel_to_the_reference(dtype, n, stride, rows, offset)
+
+
+def test_mask_kernel_equals_the_reference_at_a_qwen_vocabulary():
+    _hold_mask_kernel_to_the_reference(torch.bfloat16, 151936, 151936, 7, 0)
+
+
+def _hold_mask_kernel_to_the_reference(dtype, n, stride, rows, offset):
     K = _K()
     flat, masks, index, words, num_mask_rows = _mask_case(dtype, n, stride, rows, offset)
     want = flat.clone()

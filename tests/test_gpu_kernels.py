@@ -624,7 +624,8 @@ def test_gemm_silu_gate_fusion_equals_two_ops(dtype, M, I, Kd):
 
 # ---- greedy sampling -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("rows,n", [(1, 8), (3, 512), (32, 128256), (7, 32000), (5, 1000)])
+@pytest.mark.parametrize("rows,n", [(1, 8), (3, 512), (32, 128256), (7, 32000), (5, 1000), (7, 131072), (7, 151936),
+                                    (3, 152064)])
 def test_argmax_rows_matches_torch_with_lowest_index_ties(dtype, rows, n):
     from swiftllm_amd.worker.kernels.sampling import argmax_rows
     g = gen(rows * 31 + n)

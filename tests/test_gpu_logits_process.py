@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 DTYPES = [torch.float16, torch.bfloat16]
 # (n, row_stride): 16-byte rows; 16-byte rows with a scalar tail; 2-byte rows (the scalar path); the Llama-3 vocabulary
-WIDTHS = [(1000, 1008), (1003, 1008), (1003, 1011), (128256, 128264)]
+WIDTHS = [(1000, 1008), (1003, 1008), (1003, 1011), (128256, 128264), (151936, 151936), (152069, 152072)]
 IN_PROMPT = -2 ** 31
 INF = math.inf
 PAD = 7.0       # what the padding columns hold

@@ -119,83 +119,113 @@ def test_parity(dtype, n):
             refs = _check(x, chosen, TOP_N, _launch(x, chosen, TOP_N), refs=refs, what=(scale, mode))
 
 
-@pytest.mark.parametrize("dtype", list(DTYPES.values()))
-def test_ties(dtype):
-    n = 4097
+# The kernel holds the first 131072 columns of a row in registers and re-reads the rest on every pass (csrc/logits_keys.h).
+# The four tests below run at their own small width with `off` = 0 and again on a Qwen-wide row whose columns below
+# `off` = 131072 are ballast that never reaches the top: the tied values, the peak, the non-finite entries and the picked
+# tokens then all lie in the streamed part. (`off` = 0 leaves every input and every assertion as it was.)
+HELD = 131072
+WIDE = (151936, HELD)
+
+
+def _cases(small_n, wide=(WIDE,)):
+    """(dtype, n, off): the test's own width under the ids it always had, then the streamed widths."""
+    dtypes = list(DTYPES.values())
+    return [pytest.param(d, small_n, 0, id=f"dtype{i}") for i, d in enumerate(dtypes)] + \
+        [pytest.param(d, n, off, id=f"{n}-{off}-dtype{i}") for n, off in wide for i, d in enumerate(dtypes)]
+
+
+def _ballast(rows, off, g):
+    """[rows, off] values below anything the tests put behind them (about -8 +- 2.5)."""
+    return torch.randn(rows, off, generator=g) * 0.5 - 8.0
+
+
+@pytest.mark.parametrize("dtype,n,off", _cases(4097))
+def test_ties(dtype, n, off):
+    t = n - off
     g = torch.Generator().manual_seed(1)
     levels = torch.tensor([-1.5, 0.25, 0.5, 3.0])
-    quant = levels[torch.randint(0, 4, (3, n), generator=g)]
-    const = torch.full((1, n), 0.75)
-    zeros = torch.where(torch.rand(2, n, generator=g) < 0.5, torch.tensor(0.0), torch.tensor(-0.0))
+    quant = levels[torch.randint(0, 4, (3, t), generator=g)]
+    const = torch.full((1, t), 0.75)
+    zeros = torch.where(torch.rand(2, t, generator=g) < 0.5, torch.tensor(0.0), torch.tensor(-0.0))
     zeros[1, ::5] = -1.0
-    x = torch.cat([quant, const, zeros]).to(dtype).cuda()
+    head = _ballast(6, off, g).to(dtype)
+    x = torch.cat([head, torch.cat([quant, const, zeros]).to(dtype)], 1).cuda()
     top_n = (20, 5, 1, 20, 20, 7)
-    chosen = [n - 1, 17, 0, 1234, 99, 4000]
+    chosen = [off + c for c in (t - 1, 17, 0, 1234, 99, 4000)]
     lp, ids, rank = out = _launch(x, chosen, top_n)
     _check(x, chosen, top_n, out)
-    # the constant row: every logprob is -log n, the top ids are 0 .. N-1, the rank of c is c + 1
-    assert ids[3, 1:21].tolist() == list(range(20)) and rank[3] == 1234 + 1
-    assert np.abs(lp[3, :21] + math.log(n)).max() <= _tol(math.log(n))
+    # the constant row: every logprob is -log n (-log of the row's mass in units of one constant element, with ballast),
+    # the top ids are 0 .. N-1, the rank of c is c + 1
+    assert ids[3, 1:21].tolist() == list(range(off, off + 20)) and rank[3] == 1234 + 1
+    log_mass = math.log(t + float(torch.exp(head[3].double() - 0.75).sum()))
+    assert off or log_mass == math.log(n)
+    assert np.abs(lp[3, :21] + log_mass).max() <= _tol(log_mass)
     # +0 and -0 are one value: ids ascending whatever the sign
-    assert ids[4, 1:21].tolist() == list(range(20)) and rank[4] == 100
+    assert ids[4, 1:21].tolist() == list(range(off, off + 20)) and rank[4] == 100
 
 
-@pytest.mark.parametrize("dtype", list(DTYPES.values()))
-def test_peaked(dtype):
-    n = 32000
+@pytest.mark.parametrize("dtype,n,off", _cases(32000))
+def test_peaked(dtype, n, off):
     g = torch.Generator().manual_seed(2)
     x = torch.randn(2, n, generator=g)
-    x[0, 777] = x[0].max() + 60.0
+    x[0, off + 777] = x[0].max() + 60.0
     x[1, n - 1] = x[1].max() + 60.0
     x = x.to(dtype).cuda()
-    chosen, top_n = [777, 5], (20, 3)
+    chosen, top_n = [off + 777, off + 5], (20, 3)
     lp, ids, rank = out = _launch(x, chosen, top_n)
     _check(x, chosen, top_n, out)
     assert rank[0] == 1 and abs(lp[0, 0]) <= 2e-5 and ids[1, 1] == n - 1 and lp[1, 0] < -50
 
 
-@pytest.mark.parametrize("dtype", list(DTYPES.values()))
-def test_non_finite(dtype):
-    n = 4097
+@pytest.mark.parametrize("dtype,n,off", _cases(4097))
+def test_non_finite(dtype, n, off):
+    t = n - off
     g = torch.Generator().manual_seed(3)
-    x = torch.randn(5, n, generator=g) * 3
+    x = torch.randn(5, t, generator=g) * 3
     x[0] = -math.inf                            # all -inf
     x[1, 100] = math.inf                        # one +inf
     x[2, ::7] = math.nan                        # NaNs at every 7th element
-    x[3, torch.randperm(n, generator=g)[:n - 9]] = -math.inf    # 9 finite elements: -inf entries reach the top 20
+    x[3, torch.randperm(t, generator=g)[:t - 9]] = -math.inf    # 9 finite elements: -inf entries reach the top 20
     x[4] = math.nan                             # all NaN
-    x = x.to(dtype).cuda()
+    head = _ballast(5, off, g) - 12.0           # (below every finite element of rows 1 and 2)
+    head[0] = head[3] = -math.inf
+    head[4] = math.nan
+    x = torch.cat([head, x], 1).to(dtype).cuda()
     top_n = (5, 5, 20, 20, 3)
     finite3 = torch.isfinite(x[3].float()).nonzero().flatten().cpu().tolist()
-    chosen = [3, 100, 7, finite3[0], 2]         # (7: a NaN element of row 2)
+    assert len(finite3) == 9 and finite3[0] >= off
+    chosen = [off + 3, off + 100, off + 7, finite3[0], off + 2]         # (7: a NaN element of row 2)
     lp, ids, rank = out = _launch(x, chosen, top_n)
     _check(x, chosen, top_n, out)
-    assert np.isnan(lp[0, :6]).all() and ids[0, 1:6].tolist() == [0, 1, 2, 3, 4] and rank[0] == 4
-    assert np.isnan(lp[1, :6]).all() and ids[1, 1] == 100 and rank[1] == 1
-    assert math.isnan(lp[2, 0]) and np.isfinite(lp[2, 1:21]).all() and all(i % 7 for i in ids[2, 1:21])
+    assert np.isnan(lp[0, :6]).all() and ids[0, 1:6].tolist() == [0, 1, 2, 3, 4] and rank[0] == off + 4
+    assert np.isnan(lp[1, :6]).all() and ids[1, 1] == off + 100 and rank[1] == 1
+    assert math.isnan(lp[2, 0]) and np.isfinite(lp[2, 1:21]).all() and all(i >= off and (i - off) % 7 for i in ids[2, 1:21])
     assert sorted(ids[3, 1:10].tolist()) == finite3 and np.isfinite(lp[3, 1:10]).all()
     assert (lp[3, 10:21] == -math.inf).all()    # -inf entries report -inf and never precede a finite element
     # a -inf chosen element of a healthy row
-    banned = next(i for i in range(n) if i not in finite3)
+    banned = next(i for i in range(off, n) if i not in finite3)
     lp, ids, rank = _launch(x[3:4], [banned], (0,))
     assert lp[0, 0] == -math.inf and rank[0] == 9 + 1 + banned - sum(1 for i in finite3 if i < banned)
 
 
-@pytest.mark.parametrize("dtype", list(DTYPES.values()))
-@pytest.mark.parametrize("pad", [1, 8, 5])      # (n + 5 = 1008: 16-byte loads with a partial last vector)
-def test_layout(dtype, pad):
-    n = 1003
+@pytest.mark.parametrize("dtype,n,off", _cases(1003, (WIDE, (HELD + 3, HELD))))
+@pytest.mark.parametrize("pad", [1, 8, 5])      # (n + 5 = 1008, 131080: 16-byte loads with a partial last vector)
+def test_layout(dtype, pad, n, off):
     g = torch.Generator().manual_seed(4)
-    store = (torch.randn(6, n + pad, generator=g) * 4).to(dtype).cuda()
+    store = torch.randn(6, n + pad, generator=g) * 4
+    if off:
+        store[:, off:] += 12.0                  # (the streamed columns hold the top of every row)
+    store = store.to(dtype).cuda()
     store[:, n:] = 100.0                        # the padding between rows would win every comparison
     x = store[:, :n]
     assert x.stride(0) == n + pad
-    chosen = [5, -1, n, 0, n - 1, 2 ** 40]      # -1, n and 2^40: outside the row
+    chosen = [off + 5 if off + 5 < n else n - 2, -1, n, off, n - 1, 2 ** 40]    # -1, n and 2^40: outside the row
     out = _launch(x, chosen, TOP_N)             # (canary bands, non-asking rows and columns past top_n[r]: _launch, _check)
     _check(x, chosen, TOP_N, out)
     # top_n[r] > n_cap is clamped to n_cap
     top_n = (9, 5, -1, 7, 0, 3)
-    chosen = [1, 2, 3, 4, 5, 6]
+    base = min(off, n - 7)
+    chosen = [base + c for c in (1, 2, 3, 4, 5, 6)]
     _check(x, chosen, top_n, _launch(x, chosen, top_n, cap=5), cap=5)
     _check(x, chosen, top_n, _launch(x, chosen, top_n, cap=0), cap=0)
     # the list-taking form

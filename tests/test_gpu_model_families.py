@@ -31,7 +31,14 @@ PROMPT_LENS = (5, 16, 17, 48)
 STEPS = 12
 TORCH_DTYPE = {"float16": torch.float16, "bfloat16": torch.bfloat16}
 LEFT_OUT_CAP = {"float16": 0.15, "bfloat16": 0.50}
-SEED = {"qwen3_d128": 1, "qwen3_d64_tied": 2, "qwen2": 5, "mistral": 4}     # (HF stays within the caps: module docstring)
+SEED = {"qwen3_d128": 1, "qwen3_d64_tied": 2, "qwen2": 5, "mistral": 4,     # (HF stays within the caps: module docstring)
+        "qwen3_4b_layer": 2, "qwen3_wide_vocab": 35}   # (151936 near-equal logits: most seeds leave > 50 % open in bfloat16)
+# Two further cases, by overrides of the first qwen3 config: one layer at Qwen3-4B's real width — the only end-to-end run
+# where q_size (4096) != hidden at real width and hidden % 1024 != 0 (no deferred norm, uneven down-projection splits) —
+# and a Qwen vocabulary, 151936 columns: wider than the rows the sampling and logprob kernels keep in registers.
+CASES = {"qwen3_4b_layer": ("qwen3_d128", dict(hidden_size=2560, num_attention_heads=32, num_key_value_heads=8, head_dim=128,
+                                               intermediate_size=9728, num_hidden_layers=1)),
+         "qwen3_wide_vocab": ("qwen3_d128", dict(vocab_size=151936))}
 
 
 def _engine_config(path, **kw):
@@ -111,8 +118,9 @@ def family(tmp_path_factory):
         key = (name, dtype)
         if key not in _CACHE:
             path = str(tmp_path_factory.mktemp(f"{name}_{dtype}"))
-            hf = make_hf_checkpoint(path, name, TORCH_DTYPE[dtype], SEED[name])
-            prompts = _prompts(SEED[name])
+            base, overrides = CASES.get(name, (name, {}))
+            hf = make_hf_checkpoint(path, base, TORCH_DTYPE[dtype], SEED[name], **overrides)
+            prompts = _prompts(SEED[name], hf.config.vocab_size)      # (drawn from the whole vocabulary)
             model = _load(path, dtype)
             streams, logits = _generate(model, prompts)
             plain = model.plain_qkv
@@ -124,12 +132,39 @@ def family(tmp_path_factory):
 
 
 @pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
-@pytest.mark.parametrize("name", list(FAMILY_CONFIGS))
+@pytest.mark.parametrize("name", list(FAMILY_CONFIGS) + list(CASES))
 def test_family_matches_hf(family, name, dtype):
     path, hf, prompts, streams, logits, plain = family(name, dtype)
     assert plain is True        # every config here has a bias, a QK-norm or q_size != hidden
-    assert logits.shape == (STEPS + 1, 4, 512)
+    assert logits.shape == (STEPS + 1, 4, 151936 if name == "qwen3_wide_vocab" else 512)
     _hold_to_hf(name, dtype, hf, prompts, streams, logits)
+
+
+@pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
+def test_wide_vocabulary_rows_are_sampled_and_scored_as_the_references_say(family, dtype):
+    """Eight seeded sampling steps with logprobs on the 151936-column model: every token is the numpy reference's draw from
+    the tapped logits of its step wherever that draw is decided (margin > 1e-3, nucleus equal at p +- 1e-4: the rule of
+    tests/test_gpu_sampling.py), and the logprobs meet the bound of tests/test_gpu_logprobs.py (checked by its `_run`)."""
+    from swiftllm_amd import SamplingParams
+    from test_gpu_logprobs import _run
+    from test_gpu_sampling import _rows
+    path, _, prompts, _, _, _ = family("qwen3_wide_vocab", dtype)
+    prompts = prompts[:2]
+    model = _load(path, dtype)
+    sps = [SamplingParams(0.9, top_k=40, top_p=0.9, seed=900 + r, logprobs=5) for r in range(len(prompts))]
+    toks, logits, scores = _run(model, prompts, lambda k: sps, steps=7)
+    assert len(toks) == 8 and all(s is not None and len(s[0].top) == 5 for s in scores)
+    decided = 0
+    for k in range(8):
+        assert logits[k].shape == (len(prompts), 151936)
+        ref = _rows(logits[k].cpu(), sps, [len(p) + k for p in prompts], 0.9)
+        for r, (tok, ok) in enumerate(ref):
+            if ok:
+                decided += 1
+                assert toks[k][r] == tok, (k, r, toks[k][r], tok)
+    print(f"\n[qwen3_wide_vocab {dtype}] sampled rows decided by the reference: {decided} of {8 * len(prompts)}; "
+          f"tokens past column 131072: {sum(t >= 131072 for step in toks for t in step)}")
+    assert decided >= 8, decided
 
 
 @pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
