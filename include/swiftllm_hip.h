@@ -758,6 +758,48 @@ int swl_lora_expand(void *y, const float *t, const void *b_stack, const float *s
                     int32_t num_tokens, int32_t n, int32_t r_max, int32_t r_total, int32_t k_splits, int32_t num_slots,
                     int64_t y_row_stride, int32_t dtype, swl_stream_t stream);
 
+/* ---- mixture-of-experts FFN (Qwen3-MoE, Mixtral; csrc/moe.hip; no reference counterpart) -----------------------------------
+ * A step of num_tokens tokens, num_experts experts, top_k experts per token; pair p = t * top_k + slot. Limits (else
+ * SWL_ERR_UNSUPPORTED): num_experts <= 256, top_k <= 16, num_tokens * top_k <= swl_moe_max_pairs() = 4096 (longer steps are
+ * walked in token blocks by the caller), hidden % 64 == 0, inter % 32 == 0, row strides % 8 == 0. top_k > num_experts and a
+ * dtype other than SWL_F16 / SWL_BF16: SWL_ERR_BAD_ARG. Every entry validates before it launches; num_tokens == 0: SWL_OK,
+ * nothing launched. Device pointers: x, act, the weights, y and out 16-byte aligned.
+ *   swl_moe_supported: 1 when the GEMM entries take (hidden, inter, num_experts, top_k, dtype), else 0. Host only.
+ *   swl_moe_max_tiles: ceil(P / 16) + min(num_experts, P), P = num_tokens * top_k: the tiles swl_moe_align may use (0 for an
+ *     illegal step). Host only.
+ *   swl_moe_route: logits [num_tokens, num_experts] (logits_dtype SWL_F16, SWL_BF16 or SWL_MOE_LOGITS_F32, row stride in
+ *     elements) -> topk_ids [num_tokens, top_k] int32, topk_w [num_tokens, top_k] fp32: the top_k largest logits, ties to the
+ *     lowest expert id, slots in descending order; w = softmax over all experts (evaluated in fp64, ONE rounding to fp32),
+ *     divided by the slots' sum when norm_topk_prob. A row with a NaN or an infinity: ids 0 .. top_k - 1, weights 0.
+ *   swl_moe_align: topk_ids -> tile_rows [max_tiles * 16] int32 (pair index, -1 = padding) and tile_experts [max_tiles]
+ *     int32 (-1 = unused): every pair whose id is in [0, num_experts) once, a tile holds pairs of ONE expert, stable in the
+ *     pair index (a function of topk_ids alone). max_tiles < swl_moe_max_tiles(...): SWL_ERR_BAD_ARG. One workgroup, no host
+ *     synchronisation.
+ *   swl_moe_up_gate_silu: act[p, :] = up *_T T(silu(gate)), up / gate = T(x[p / top_k] . expert_up_gate[e][rows / inter +
+ *     rows]), fp32 accumulation; expert_up_gate [num_experts, 2 * inter, hidden] with each expert [up ; gate]; act
+ *     [num_tokens * top_k, inter] in the storage dtype.
+ *   swl_moe_down: y[p, :] = act[p] . expert_down[e]^T, expert_down [num_experts, hidden, inter]; y fp32
+ *     [num_tokens * top_k, hidden], unrounded.
+ *   swl_moe_combine: out[t, :] = T(sum_j topk_w[t, j] * y[t * top_k + j, :]), fp32, slot order, ONE rounding; no atomics.
+ * The bits of out[t] depend on x[t], its experts and its weights only: not on num_tokens, the tiling or the other rows. */
+#define SWL_MOE_LOGITS_F32 2
+int swl_moe_supported(int32_t hidden, int32_t inter, int32_t num_experts, int32_t top_k, int32_t dtype);
+int swl_moe_max_pairs(void);
+int swl_moe_max_tiles(int32_t num_tokens, int32_t top_k, int32_t num_experts);
+int swl_moe_route(int32_t *topk_ids, float *topk_w, const void *logits, int32_t num_tokens, int32_t num_experts,
+                  int32_t top_k, int32_t norm_topk_prob, int64_t logits_row_stride, int32_t logits_dtype,
+                  swl_stream_t stream);
+int swl_moe_align(int32_t *tile_rows, int32_t *tile_experts, const int32_t *topk_ids, int32_t num_tokens, int32_t top_k,
+                  int32_t num_experts, int32_t max_tiles, swl_stream_t stream);
+int swl_moe_up_gate_silu(void *act, const void *x, const void *expert_up_gate, const int32_t *tile_rows,
+                         const int32_t *tile_experts, int32_t max_tiles, int32_t num_tokens, int32_t top_k, int32_t hidden,
+                         int32_t inter, int32_t num_experts, int64_t x_row_stride, int32_t dtype, swl_stream_t stream);
+int swl_moe_down(float *y, const void *act, const void *expert_down, const int32_t *tile_rows, const int32_t *tile_experts,
+                 int32_t max_tiles, int32_t num_tokens, int32_t top_k, int32_t hidden, int32_t inter, int32_t num_experts,
+                 int32_t dtype, swl_stream_t stream);
+int swl_moe_combine(void *out, const float *y, const float *topk_w, int32_t num_tokens, int32_t top_k, int32_t hidden,
+                    int64_t out_row_stride, int32_t dtype, swl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,16 @@ _SPECIAL = {
     # registered here for the same reason (its own contract: tests/test_qk_prep_abi.py, tests/test_gpu_qk_prep.py).
     "swl_qk_prep_rotary": ([_P, _P, _P, _P, _P, _P, _P, _P, _F32, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I64, _I64,
                             _I32, _P], _I32),
+    # Mixture-of-experts FFN (csrc/moe.hip; Qwen3-MoE, Mixtral): host arithmetic and "int rc = f(...)" entries, registered
+    # here for the same reason (their own contract: tests/test_moe_abi.py, tests/test_gpu_moe_kernels.py).
+    "swl_moe_supported": ([_I32, _I32, _I32, _I32, _I32], _I32),
+    "swl_moe_max_pairs": ([], _I32),
+    "swl_moe_max_tiles": ([_I32, _I32, _I32], _I32),
+    "swl_moe_route": ([_P, _P, _P, _I32, _I32, _I32, _I32, _I64, _I32, _P], _I32),
+    "swl_moe_align": ([_P, _P, _P, _I32, _I32, _I32, _I32, _P], _I32),
+    "swl_moe_up_gate_silu": ([_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _P], _I32),
+    "swl_moe_down": ([_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P], _I32),
+    "swl_moe_combine": ([_P, _P, _P, _I32, _I32, _I32, _I64, _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

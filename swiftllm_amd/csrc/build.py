@@ -38,6 +38,7 @@ SOURCES = [
     "logprobs.hip",
     "guided.hip",
     "lora.hip",
+    "moe.hip",
     "decode_engine.hip",
 ]
 HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "decode_attn.h", "prefill_tile.h", "fp8_kv.h", "kv_store.h", "gemm_host.h", "logits_keys.h", "logits_bits.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]

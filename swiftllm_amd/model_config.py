@@ -3,7 +3,9 @@
 Mirrors swiftllm/model_config.py:5-46 (attribute names, defaults, kv-slot size formula). Beyond the reference it also
 reads the Llama-shaped families whose differences sit between the q/k/v projections and attention: Mistral (optional
 `head_dim`, optional `sliding_window`), Qwen2 / Qwen2.5 (bias on q/k/v_proj) and dense Qwen3 (per-head RMSNorm on q and k,
-`head_dim` given in the config). What those checkpoints may ask for and this project does not build is refused here, with
+`head_dim` given in the config), and the mixture-of-experts variants whose attention is one of those: Qwen3-MoE (dense
+Qwen3's attention) and Mixtral (Mistral's), with the expert geometry in `num_experts`, `num_experts_per_tok`,
+`moe_inter_dim` and `norm_topk_prob` (all zero / false for a dense model). What those checkpoints may ask for and this project does not build is refused here, with
 the reason, before any memory is touched."""
 import json
 import os
@@ -12,20 +14,26 @@ import torch
 
 MODEL_TYPES = ("llama", "mistral", "qwen2", "qwen3")
 MOE_TYPES = ("mixtral", "qwen2_moe", "qwen3_moe")
+# the mixture-of-experts variants that are built, and the dense family each takes its attention (and its parsing) from
+MOE_FAMILY = {"qwen3_moe": "qwen3", "mixtral": "mistral"}
+# what csrc/moe.hip takes: one wave routes a token (4 experts a lane), one lane holds a slot
+MOE_MAX_EXPERTS = 256
+MOE_MAX_TOP_K = 16
 # the attention kernels' tiles: q heads per kv head, and head_dim
 GROUP_SIZES = (1, 2, 4, 8)
 HEAD_DIMS = (32, 64, 128)
 
 
 class LlamaModelConfig:
-    """LLaMA 1/2/3, Mistral, Qwen2 / Qwen2.5 and dense Qwen3 configuration. Attribute names follow the reference so
+    """LLaMA 1/2/3, Mistral, Qwen2 / Qwen2.5, dense Qwen3, Qwen3-MoE and Mixtral configuration. Attribute names follow the reference so
     layer/kernel code and user scripts that poke at `model.model_config` keep working."""
 
     def __init__(self, model_config: dict):
         model_type = model_config["model_type"]
-        if model_type in MOE_TYPES:
-            raise ValueError(f"model_type {model_type!r} is a mixture-of-experts variant; only the dense models are built")
-        if model_type not in MODEL_TYPES:
+        if model_type in MOE_TYPES and model_type not in MOE_FAMILY:
+            raise ValueError(f"model_type {model_type!r} is a mixture-of-experts variant with a shared expert next to the "
+                             "routed ones; the shared expert is not built (qwen3_moe and mixtral are)")
+        if model_type not in MODEL_TYPES + tuple(MOE_FAMILY):
             raise AssertionError(f"unsupported model_type {model_type!r}")
         if model_config["hidden_act"] != "silu":
             raise AssertionError(f"unsupported hidden_act {model_config['hidden_act']!r}")
@@ -37,7 +45,7 @@ class LlamaModelConfig:
         self.head_dim = self.hidden_size // self.num_q_heads
         self.vocab_size = model_config["vocab_size"]
         self.max_position_embeddings = model_config["max_position_embeddings"]
-        self.ffn_inter_dim = model_config["intermediate_size"]
+        self.ffn_inter_dim = model_config.get("intermediate_size", 0) if model_type in MOE_FAMILY else model_config["intermediate_size"]
         self.rope_theta = model_config.get("rope_theta", 10000)
         self.rotary_base = model_config.get("rope_theta", model_config.get("rotary_base", 10000))
         self.rms_norm_eps = model_config["rms_norm_eps"]
@@ -46,13 +54,54 @@ class LlamaModelConfig:
         # q/k/v_proj carry a bias; q and k get a per-head RMSNorm before rotary; lm_head is the embedding
         self.qkv_bias = self.qk_norm = self.tie_word_embeddings = False
         self.sliding_window = None      # the window that capped max_position_embeddings, when one applies
+        # mixture-of-experts FFN: experts, experts per token, an expert's intermediate size, top-k weights renormalised
+        self.num_experts = self.num_experts_per_tok = self.moe_inter_dim = 0
+        self.norm_topk_prob = False
         if model_type != "llama":
             self._init_family(model_config)
+        if model_type in MOE_FAMILY:
+            self._init_moe(model_config)
         self.q_size = self.num_q_heads * self.head_dim
+
+    @property
+    def is_moe(self) -> bool:
+        return self.num_experts > 0
+
+    def _init_moe(self, c: dict):
+        """Qwen3-MoE and Mixtral: the expert geometry, and the refusals."""
+        kind = self.model_type
+        qwen = kind == "qwen3_moe"
+        # (transformers 5 names the count num_local_experts when it writes either family; the published Qwen3-MoE configs
+        # say num_experts)
+        experts = c.get("num_experts") or c.get("num_local_experts")
+        top_k = c.get("num_experts_per_tok")
+        inter = c.get("moe_intermediate_size" if qwen else "intermediate_size")
+        if not experts or not top_k or not inter:
+            raise ValueError(f"{kind}: a mixture-of-experts config without "
+                             f"{'num_experts' if qwen else 'num_local_experts'} / num_experts_per_tok / "
+                             f"{'moe_intermediate_size' if qwen else 'intermediate_size'}")
+        self.num_experts, self.num_experts_per_tok, self.moe_inter_dim = int(experts), int(top_k), int(inter)
+        self.norm_topk_prob = bool(c.get("norm_topk_prob", False)) if qwen else True
+        self.ffn_inter_dim = self.moe_inter_dim         # (no dense FFN in these models: the width an expert has)
+        if c.get("mlp_only_layers"):
+            raise ValueError(f"{kind}: mlp_only_layers {c['mlp_only_layers']} mixes dense and sparse layers; every layer "
+                             "must be a mixture-of-experts layer")
+        if c.get("decoder_sparse_step", 1) != 1:
+            raise ValueError(f"{kind}: decoder_sparse_step {c['decoder_sparse_step']} mixes dense and sparse layers; only "
+                             "decoder_sparse_step 1 is built")
+        if self.num_experts_per_tok > self.num_experts:
+            raise ValueError(f"{kind}: num_experts_per_tok {self.num_experts_per_tok} exceeds the {self.num_experts} experts")
+        if self.num_experts > MOE_MAX_EXPERTS or self.num_experts_per_tok > MOE_MAX_TOP_K:
+            raise ValueError(f"{kind}: {self.num_experts} experts, top-{self.num_experts_per_tok}; the routing kernel is built "
+                             f"for at most {MOE_MAX_EXPERTS} experts and top-{MOE_MAX_TOP_K}")
+        if self.hidden_size % 64 or self.moe_inter_dim % 32 or self.hidden_size // 16 > 65535 or self.moe_inter_dim // 16 > 65535:
+            raise ValueError(f"{kind}: hidden_size {self.hidden_size}, expert intermediate size {self.moe_inter_dim}; the expert "
+                             "GEMMs are built for hidden_size % 64 == 0 and an intermediate size % 32 == 0 (16-column blocks "
+                             "within a 65535-block grid)")
 
     def _init_family(self, c: dict):
         """Mistral, Qwen2 and Qwen3: the fields Llama's parsing above does not read, and the refusals."""
-        kind = self.model_type
+        kind = MOE_FAMILY.get(self.model_type, self.model_type)
         if c.get("head_dim") is not None:
             self.head_dim = int(c["head_dim"])
         self.qkv_bias = kind == "qwen2"

@@ -25,10 +25,13 @@ Launches per layer by route (pure decode of m sequences unless said; default swi
 | PLAIN, PLAIN, QKV.ROTARY_THEN_STORE | FP8 pools, fuse_rope_kvstore off, no positions | ... rotary, (quantising) store ... (QKV.ROTARY_ONLY: ignore_kvcache) |
 | SPLITK_FUSED (or _DEFERRED), SPLITK, QKV.ROTARY_THEN_STORE | plain_qkv (Qwen2 / Qwen3 / q_size != hidden)          | add_norm, qkv, prep, store, attention, o, add_norm (or add_scale), silu_gate, down: 9 (as FP8 pools) |
 | PLAIN, PLAIN, QKV.ROTARY_THEN_STORE | plain_qkv, a prompt row (or the switches above off) | add_norm, q/k/v, prep, store, attention, o, add_norm, up_gate (+ silu), down |
+| SPLITK_FUSED (or PLAIN), MOE      | a mixture-of-experts layer (Qwen3-MoE, Mixtral)  | ... o, add_norm, router, route, align, up_gate_silu, down, combine (prompt steps: the six MoE launches per block of tokens) |
 | lora                              | some row names an adapter                        | the plain sequence with the adapter update after every projection |
 
 "prep" is the one launch between the projections and the store: bias + per-head QK-norm + rotary (swl_qk_prep_rotary) for
 a model with a q/k/v bias or a QK-norm, swl_rotary for one that only decouples q_size from hidden (Mistral-Nemo).
+A mixture-of-experts layer ends the o_proj / FFN-norm stage with the normalised activations as a tensor, computes the router
+logits with the dense `linear()` on the [E, H] router weight, and hands a plain tensor to the next layer (kernels/moe.py).
 The first layer of a step receives a tensor, so its input norm is the fused add+norm whatever the route of the others.
 """
 import enum
@@ -51,6 +54,7 @@ from ..kernels.prefill_attn import prefill_attention, prefill_attention_paged
 from ..kernels.paged_attn import paged_attention, paged_attention_from_qkv_splitk, paged_attention_verify
 from ..kernels.silu_and_mul import silu_and_mul_inplace
 from ..kernels.lora import lora_apply
+from ..kernels.moe import moe_ffn
 
 # Where the row-owned projections win on MI355X (tools/gemm_rows_micro.py --layer, tools/rows_kernel_us.py): every
 # workgroup of such a projection pulls ALL of x through its own L1, so the win shrinks with the batch. With x staged as
@@ -97,12 +101,13 @@ ROWS_DOWN_MAX_M = 16
 #   ROWS_SSQ  ... carrying the rows' sums of squares
 #   SPLITK    slabs where the kernel splits K
 #   PLAIN     a tensor
+#   MOE       the mixture-of-experts FFN took the place of up/gate and down: a tensor
 Input = enum.Enum("Input", "TENSOR SLABS RAW RAW_SSQ")
 AttnNorm = enum.Enum("AttnNorm", "FUSED SCALE_PENDING TINY RAW_NF RAW_NX")
 QKV = enum.Enum("QKV", "SLABS_ATTN SLABS_ROTARY FUSED_DECODE FUSED_PREFILL ROTARY_THEN_STORE ROTARY_ONLY")
 Attn = enum.Enum("Attn", "DECODE FRESH PAGED VERIFY")
 OFfn = enum.Enum("OFfn", "ROWS_NF ROWS_NX TINY SPLITK_DEFERRED SPLITK_FUSED PLAIN")
-Down = enum.Enum("Down", "ROWS ROWS_SSQ SPLITK PLAIN")
+Down = enum.Enum("Down", "ROWS ROWS_SSQ SPLITK PLAIN MOE")
 
 
 class LayerRoute(NamedTuple):
@@ -148,10 +153,12 @@ class LayerFacts(NamedTuple):
     # the model has a q/k/v bias, a per-head QK-norm, or q_size != hidden (Qwen2, Qwen3, Mistral-Nemo): q/k/v stay plain
     # tensors up to the store — none of the forms that consume the qkv projection's slabs, and no rotary + store fusion
     plain_qkv: bool = False
+    # a mixture-of-experts FFN: the FFN norm ends in a tensor, the experts (kernels/moe.py) return one
+    moe: bool = False
 
 
 def layer_facts(engine_config, dtype, hidden: int, num_q_heads: int, head_dim: int, shapes: dict, packed, lib,
-                plain_qkv: bool = False) -> LayerFacts:
+                plain_qkv: bool = False, moe: bool = False) -> LayerFacts:
     """`shapes`: (N, K) of "qkv" (absent without the fused projection), "o", "up_gate", "down"; `packed`: the names that
     carry a packed twin; `lib`: the loaded library, asked for its host arithmetic only (split counts, shape support)."""
     def takes(name):            # the weight-streaming GEMMs take the shape
@@ -182,7 +189,7 @@ def layer_facts(engine_config, dtype, hidden: int, num_q_heads: int, head_dim: i
               and up_n % 128 == 0 and up_k % 128 == 0 and up_k <= _TINY_MAX_KC and splits("o", True) > 1 and splits("down", True) > 1),
         merge=("o" in packed and head_dim % 8 == 0 and shapes["o"][1] == num_q_heads * head_dim
                and splits("o", True) > 1 and chunked("o", splits("o", True))),
-        plain_qkv=bool(plain_qkv))
+        plain_qkv=bool(plain_qkv), moe=bool(moe))
 
 
 def decide_route(f: LayerFacts, s: StepFacts) -> LayerRoute:
@@ -198,10 +205,10 @@ def decide_route(f: LayerFacts, s: StepFacts) -> LayerRoute:
     # the 1/rms of a norm can be left to the consumer of the normalised activations: bfloat16, <= 32 sequences
     defer = f.tuning.defer_rmsnorm and deferred_norm_ok(s.m, f.hidden, f.dtype)
     deferred = slab_attn and defer and f.qkv_splits in (1, 2, 4)
-    rows = (f.tuning.rows_decode and slab_attn and (deferred or f.hidden % 1024 == 0) and s.m <= ROWS_O_MAX_M and f.rows_o
+    rows = (not f.moe and f.tuning.rows_decode and slab_attn and (deferred or f.hidden % 1024 == 0) and s.m <= ROWS_O_MAX_M and f.rows_o
             and f.fly_ffn)
     rows_down = rows and s.m <= ROWS_DOWN_MAX_M and f.rows_down and f.qkv_even
-    tiny = s.input is Input.SLABS and f.tuning.tiny_decode_batches and s.m <= TINY_POLICY_M and deferred and f.tiny
+    tiny = not f.moe and s.input is Input.SLABS and f.tuning.tiny_decode_batches and s.m <= TINY_POLICY_M and deferred and f.tiny
 
     if s.input in (Input.RAW, Input.RAW_SSQ):
         # the previous layer's route is this one: its down projection ran row-owned, in the form this layer's norm takes
@@ -219,7 +226,10 @@ def decide_route(f: LayerFacts, s: StepFacts) -> LayerRoute:
         qkv = QKV.FUSED_PREFILL if s.prefill else QKV.FUSED_DECODE
     else:
         qkv = QKV.ROTARY_ONLY if s.ignore_kvcache else QKV.ROTARY_THEN_STORE
-    if tiny:
+    if f.moe:
+        # the router and the experts read the normalised activations as a tensor: the forms that end in one
+        o_ffn, down = OFfn.SPLITK_FUSED if fast else OFfn.PLAIN, Down.MOE
+    elif tiny:
         o_ffn, down = OFfn.TINY, Down.SPLITK
     elif rows:
         o_ffn = OFfn.ROWS_NF if deferred else OFfn.ROWS_NX
@@ -242,19 +252,24 @@ class LlamaTransformerLayer:
         self.decoding_piggyback_stream = decoding_piggyback_stream
         self.layer_id = layer_id
         self.skinny = bool(engine_config.use_skinny_gemm)
+        self.moe_tap = None         # tests: a list that receives (layer_id, topk_ids, topk_w) per step (LlamaModel.moe_tap)
         self.refresh_facts()
 
     def refresh_facts(self):
         """(Re)compute the layer's static facts and forget the routes decided from them: at construction, and again when
         the packed twins of the weights are rebuilt (LlamaModel.repack_decode_weights)."""
         cfg, w = self.model_config, self.weight
-        named = dict(qkv=w.qkv_proj, o=w.o_proj, up_gate=w.up_gate_proj, down=w.down_proj)
+        self.moe = getattr(w, "expert_up_gate", None) is not None
+        named = dict(qkv=w.qkv_proj, o=w.o_proj, up_gate=getattr(w, "up_gate_proj", None), down=getattr(w, "down_proj", None))
         # bias + QK-norm + rotary in one launch where the model has either (Qwen2 / Qwen3); otherwise swl_rotary
         self.qk_prep = getattr(w, "q_norm", None) is not None or getattr(w, "q_bias", None) is not None
         self.facts = layer_facts(self.engine_config, w.o_proj.dtype, cfg.hidden_size, cfg.num_q_heads, cfg.head_dim,
-                                 {name: tuple(t.shape) for name, t in named.items() if t is not None},
+                                 {**{name: tuple(t.shape) for name, t in named.items() if t is not None},
+                                    **(dict(up_gate=tuple(w.expert_up_gate.shape[1:]), down=tuple(w.expert_down.shape[1:]))
+                                       if self.moe else {})},
                                  {name for name, t in named.items() if getattr(t, "_swl_packed", None) is not None},
-                                 _hip.load(), plain_qkv=self.qk_prep or cfg.num_q_heads * cfg.head_dim != cfg.hidden_size)
+                                 _hip.load(), plain_qkv=self.qk_prep or cfg.num_q_heads * cfg.head_dim != cfg.hidden_size,
+                                 moe=self.moe)
         self._routes = {}           # StepFacts -> LayerRoute
 
     def route(self, input_embds, st) -> LayerRoute:
@@ -416,6 +431,8 @@ class LlamaTransformerLayer:
             return linear_silu_gate(pend.x, w.up_gate_proj, row_scale=pend)
         attn_out = linear_splitk(x, w.o_proj) if route.o_ffn is OFfn.SPLITK_FUSED else linear(x, w.o_proj, sk)
         attn_out = self._add_norm(attn_out, residual_buf, w.ffn_norm)
+        if route.down is Down.MOE:
+            return attn_out     # the normalised activations: the experts take them from here (_down_proj)
         act = linear_silu_gate(attn_out, w.up_gate_proj) if sk else None
         if act is None:         # (shapes the one-launch form does not take)
             up_gate = linear(attn_out, w.up_gate_proj, sk)
@@ -425,6 +442,10 @@ class LlamaTransformerLayer:
 
     def _down_proj(self, route, act, residual_buf):
         w = self.weight
+        if route.down is Down.MOE:
+            cfg = self.model_config
+            return moe_ffn(act, w.router, w.expert_up_gate, w.expert_down, cfg.num_experts_per_tok, cfg.norm_topk_prob,
+                           self.skinny, tap=self.moe_tap, layer_id=self.layer_id)
         if route.down is Down.ROWS:
             linear_rows_add(act, w.down_proj, residual_buf)
             return RawResidual(residual_buf)

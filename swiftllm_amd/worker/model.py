@@ -94,6 +94,14 @@ class LlamaModel:
             raise ValueError(f"tuning={{'decode_engine': True}} cannot serve this {cfg.model_type} model: the persistent "
                              "one-sequence step is laid out for Llama's projections (no q/k/v bias, no per-head QK-norm, "
                              "q_proj as wide as hidden_size)")
+        # a mixture-of-experts model (Qwen3-MoE, Mixtral): what is not built for it is refused before any memory is touched
+        if cfg.is_moe:
+            if getattr(engine_config, "decode_engine", False):
+                raise ValueError(f"tuning={{'decode_engine': True}} cannot serve this {cfg.model_type} model: the persistent "
+                                 "one-sequence step has a dense FFN, no mixture-of-experts routing")
+            if int(getattr(engine_config, "max_loras", 0) or 0) > 0:
+                raise ValueError(f"max_loras > 0 cannot serve this {cfg.model_type} model: adapters on mixture-of-experts "
+                                 "layers (their experts have no adapter update) are not built")
         # element type of the KV pools: the activation dtype, or e4m3fn (EngineConfig.kv_cache_dtype = "fp8_e4m3")
         self.kv_fp8 = getattr(engine_config, "kv_cache_dtype", "auto") == "fp8_e4m3"
         self.kv_dtype = torch.float8_e4m3fn if self.kv_fp8 else self.dtype
@@ -156,6 +164,20 @@ class LlamaModel:
         # allocated by load_weights; None = off
         self.lora_store = None
         self._lora_staging = LoraStaging()      # pinned staging of a LoRA step's tile lists + the t workspace, reused
+        self._moe_tap = None
+
+    @property
+    def moe_tap(self):
+        """Tests: set to a list and every mixture-of-experts layer appends (layer_id, topk_ids.cpu(), topk_w.cpu()) per step
+        (prefill rows first, as the step's rows are ordered). None (the default) costs nothing. A tapped step copies to the
+        host, so it runs eager: never captured into, or replayed from, a decode hipGraph."""
+        return self._moe_tap
+
+    @moe_tap.setter
+    def moe_tap(self, tap):
+        self._moe_tap = tap
+        for layer in self.transformer_layers or ():
+            layer.moe_tap = tap
 
     # ------------------------------------------------------------------------------------------------
     @torch.inference_mode()
@@ -176,6 +198,7 @@ class LlamaModel:
                                   side_stream, i)
             for i in range(self.model_config.num_layers)
         ]
+        self.moe_tap = self._moe_tap
         self.post_layer = LlamaPostLayer(self.model_config, self.weight)
         self.post_layer.skinny = bool(getattr(self.engine_config, "use_skinny_gemm", False))
         if self.kv_fp8 and self.kv_scales is None:
@@ -282,7 +305,7 @@ class LlamaModel:
                 and ecfg.max_batch_size > 64):
             return
         from .kernels.linear import tune_wide_routes
-        stats = tune_wide_routes(self.weight.projection_tensors(), [lw.up_gate_proj for lw in self.weight.layers[:1]],
+        stats = tune_wide_routes(self.weight.projection_tensors(), [lw.up_gate_proj for lw in self.weight.layers[:1] if getattr(lw, "up_gate_proj", None) is not None],
                                  self.dtype, self.device, ecfg.model_path)
         if stats.get("measured") or stats.get("read"):
             print(f"[Model] decode-projection routing: {stats['measured']} (shape, bucket) classes measured, "
@@ -990,6 +1013,8 @@ class LlamaModel:
         if lora_slots is not None:
             return self._forward_step_lora(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts,
                                            prefill_ctx_lens, lora_slots)
+        if self._moe_tap is not None:
+            self._lookahead = None      # (tests) a tapped step copies the routing to the host: eager, not a replay
         la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts)
         if la is not None:      # the step that was prepared while the previous one ran: blocks, then the launch
             self.gpu_block_manager.allocate_blocks_for_seqs(la.seq_ids, la.lens)   # (the real sequences only)
@@ -999,7 +1024,7 @@ class LlamaModel:
         else:
             num_real = len(input_ids_list)
             pure_decode = len(decoding_seq_lens_list) == num_real and not ignore_kvcache
-            graph_step = pure_decode and self._use_hip_graph
+            graph_step = pure_decode and self._use_hip_graph and self._moe_tap is None
             if graph_step or (pure_decode and self._eager_uses_graph_buckets):
                 # pure decode on the replay path: the batch is rounded up to its bucket with inert rows (_decode_batch_bucket)
                 plan = self._plan_decode(seq_ids_list, list(decoding_seq_lens_list), input_ids_list, True)

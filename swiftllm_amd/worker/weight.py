@@ -8,7 +8,9 @@ shape checks, safetensors (single file or `model.safetensors.index.json`) prefer
 Differences: dtype and device are parameters (the reference hard-codes fp16 / "cuda"), and q/k/v can
 additionally be concatenated into one `qkv_proj` for a single fused projection GEMM. Beyond the reference: the Llama-shaped
 families of model_config.py — q_proj / o_proj sized by num_q_heads * head_dim (Qwen3, Mistral-Nemo), Qwen3's per-head
-q_norm / k_norm, Qwen2's q/k/v_proj biases, and a tied lm_head selected by `tie_word_embeddings`.
+q_norm / k_norm, Qwen2's q/k/v_proj biases, and a tied lm_head selected by `tie_word_embeddings`. A mixture-of-experts layer
+(Qwen3-MoE, Mixtral) has a `router` [E, H] and two stacked expert tensors in place of up_gate_proj / down_proj:
+`expert_up_gate` [E, 2 I, H] (each expert [up ; gate]) and `expert_down` [E, H, I] — one copy in HBM, never packed.
 """
 import json
 import os
@@ -32,6 +34,12 @@ def layer_weight_specs(cfg, layer_id: int) -> List[WeightSpec]:
     h, kv, qs = cfg.hidden_size, cfg.num_kv_heads * cfg.head_dim, _q_size(cfg)
     inter = cfg.ffn_inter_dim
     pre = f"model.layers.{layer_id}."
+    if getattr(cfg, "num_experts", 0):
+        ffn = [WeightSpec("router", pre + _moe_names(cfg)[0] + "gate.weight", (cfg.num_experts, h))]
+    else:
+        ffn = [WeightSpec("up_proj", pre + "mlp.up_proj.weight", (inter, h)),
+               WeightSpec("gate_proj", pre + "mlp.gate_proj.weight", (inter, h)),
+               WeightSpec("down_proj", pre + "mlp.down_proj.weight", (h, inter))]
     return [
         WeightSpec("attn_norm", pre + "input_layernorm.weight", (h,)),
         WeightSpec("q_proj", pre + "self_attn.q_proj.weight", (qs, h)),
@@ -39,10 +47,28 @@ def layer_weight_specs(cfg, layer_id: int) -> List[WeightSpec]:
         WeightSpec("v_proj", pre + "self_attn.v_proj.weight", (kv, h)),
         WeightSpec("o_proj", pre + "self_attn.o_proj.weight", (h, qs)),
         WeightSpec("ffn_norm", pre + "post_attention_layernorm.weight", (h,)),
-        WeightSpec("up_proj", pre + "mlp.up_proj.weight", (inter, h)),
-        WeightSpec("gate_proj", pre + "mlp.gate_proj.weight", (inter, h)),
-        WeightSpec("down_proj", pre + "mlp.down_proj.weight", (h, inter)),
-    ] + layer_family_specs(cfg, layer_id)
+    ] + ffn + layer_family_specs(cfg, layer_id)
+
+
+def _moe_names(cfg):
+    """(module prefix, up, gate, down) as the published checkpoints of the family name an expert's tensors."""
+    if cfg.model_type == "mixtral":
+        return "block_sparse_moe.", "w3", "w1", "w2"
+    return "mlp.", "up_proj", "gate_proj", "down_proj"
+
+
+def expert_weight_specs(cfg, layer_id: int) -> List[tuple]:
+    """Per expert of a mixture-of-experts layer: (WeightSpec, stacked attribute, first row inside the stack). The stacks
+    are expert_up_gate [E, 2 I, H] (rows e * 2 I: up, e * 2 I + I: gate) and expert_down [E, H, I] (rows e * H)."""
+    h, inter = cfg.hidden_size, cfg.moe_inter_dim
+    mod, up, gate, down = _moe_names(cfg)
+    out = []
+    for e in range(cfg.num_experts):
+        pre = f"model.layers.{layer_id}.{mod}experts.{e}."
+        out += [(WeightSpec("up_proj", pre + up + ".weight", (inter, h)), "expert_up_gate", e * 2 * inter),
+                (WeightSpec("gate_proj", pre + gate + ".weight", (inter, h)), "expert_up_gate", e * 2 * inter + inter),
+                (WeightSpec("down_proj", pre + down + ".weight", (h, inter)), "expert_down", e * h)]
+    return out
 
 
 def layer_family_specs(cfg, layer_id: int) -> List[WeightSpec]:
@@ -93,6 +119,17 @@ class LlamaTransformerLayerWeight:
         self.qkv_proj = None
         self.q_norm = self.k_norm = None
         self.qkv_bias = self.q_bias = self.k_bias = self.v_bias = None
+        # a mixture-of-experts layer: router [E, H], expert_up_gate [E, 2 I, H], expert_down [E, H, I]; such a layer has no
+        # up_gate_proj / down_proj attribute
+        # (up_gate_proj / down_proj are NOT pre-set here: a dense layer's attributes keep the order they always had, which
+        # is the order callers walk vars(layer) in when they re-initialise the weights from one seeded generator)
+        self.router = self.expert_up_gate = self.expert_down = None
+
+    def alloc_experts(self, device: torch.device):
+        cfg = self.model_config
+        e, h, inter = cfg.num_experts, cfg.hidden_size, cfg.moe_inter_dim
+        self.expert_up_gate = torch.empty((e, 2 * inter, h), dtype=self.dtype, device=device)
+        self.expert_down = torch.empty((e, h, inter), dtype=self.dtype, device=device)
 
     def slice_qkv_bias(self):
         """q_bias / k_bias / v_bias as views of the assembled qkv_bias (what the kernel receives)."""
@@ -102,8 +139,19 @@ class LlamaTransformerLayerWeight:
 
     def load(self, getter: Getter, device: torch.device, fuse_qkv: bool):
         _fill(self, layer_weight_specs(self.model_config, self.layer_id), getter, self.dtype, device)
-        self.up_gate_proj = torch.cat((self.up_proj, self.gate_proj), dim=0).contiguous()
-        del self.up_proj, self.gate_proj
+        if getattr(self.model_config, "num_experts", 0):
+            # every expert goes to its place inside the stacks: no second copy of the expert weights at any time
+            self.alloc_experts(device)
+            for spec, attr, row in expert_weight_specs(self.model_config, self.layer_id):
+                t = getter(spec)
+                assert isinstance(t, torch.Tensor), f"Weight {spec.key} is not a tensor"
+                assert tuple(t.shape) == tuple(spec.shape), \
+                    f"Shape of weight {spec.key} does not match: {tuple(t.shape)} vs {spec.shape}"
+                stack = getattr(self, attr)
+                stack.view(-1, stack.shape[-1])[row:row + spec.shape[0]].copy_(t)
+        else:
+            self.up_gate_proj = torch.cat((self.up_proj, self.gate_proj), dim=0).contiguous()
+            del self.up_proj, self.gate_proj
         if fuse_qkv:
             self.qkv_proj = torch.cat((self.q_proj, self.k_proj, self.v_proj), dim=0).contiguous()
             del self.q_proj, self.k_proj, self.v_proj
@@ -243,13 +291,19 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
         weight.lm_head = weight.wte
     for layer in weight.layers:
         specs = {s.attr: s for s in layer_weight_specs(cfg, layer.layer_id)}
-        for attr in ("attn_norm", "o_proj", "ffn_norm", "down_proj"):
+        moe = "router" in specs
+        for attr in ("attn_norm", "o_proj", "ffn_norm", "router" if moe else "down_proj"):
             t = dest(specs[attr].shape)
             setattr(layer, attr, t)
             plan.append((specs[attr].key, specs[attr].shape, t, 0))
-        layer.up_gate_proj = dest((2 * inter, h))           # [up ; gate] (reference weight.py:133)
-        plan.append((specs["up_proj"].key, specs["up_proj"].shape, layer.up_gate_proj, 0))
-        plan.append((specs["gate_proj"].key, specs["gate_proj"].shape, layer.up_gate_proj, inter))
+        if moe:                                             # every expert at its final offset inside the two stacks
+            layer.alloc_experts(device)
+            for spec, attr, row in expert_weight_specs(cfg, layer.layer_id):
+                plan.append((spec.key, spec.shape, getattr(layer, attr), row))
+        else:
+            layer.up_gate_proj = dest((2 * inter, h))       # [up ; gate] (reference weight.py:133)
+            plan.append((specs["up_proj"].key, specs["up_proj"].shape, layer.up_gate_proj, 0))
+            plan.append((specs["gate_proj"].key, specs["gate_proj"].shape, layer.up_gate_proj, inter))
         if fuse_qkv:
             layer.qkv_proj = dest((qs + 2 * kv, h))         # [q ; k ; v]
             for attr, row in (("q_proj", 0), ("k_proj", qs), ("v_proj", qs + kv)):
