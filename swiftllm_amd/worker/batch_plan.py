@@ -62,7 +62,7 @@ class BatchPlan:
     position_indices: np.ndarray        # [T]
     last_token_indices: np.ndarray      # [B]
     # sequences of the caller's batch; batch_size - num_real_seqs trailing rows are inert padding (length 0) that rounds a
-    # pure-decode batch up to its hipGraph bucket (worker/model.py: _decode_batch_bucket). -1: not set = batch_size
+    # pure-decode batch up to its hipGraph bucket (worker/decode_replay.py: decode_batch_bucket). -1: not set = batch_size
     num_real_seqs: int = -1
     # chunked prefill: tokens of each prefill sequence already resident in the KV pool (int32 [Bp]); None = every prompt
     # starts at position 0 (no segment is packed then: the layout is what it always was)

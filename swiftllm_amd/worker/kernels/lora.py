@@ -15,6 +15,8 @@ import torch
 
 from swiftllm_amd import _hip
 
+from ..step_logits import StagedInts
+
 TILE_ROWS = 16
 SUPPORTED_RANKS = (8, 16, 32, 64)
 
@@ -79,62 +81,39 @@ def group_supported(k: int, widths: Sequence[int], r_max: int) -> bool:
     return r_max in SUPPORTED_RANKS and k % 128 == 0 and all(w > 0 and w % 16 == 0 for w in widths) and len(widths) <= 4
 
 
-class LoraStaging:
+class LoraStaging(StagedInts):
     """What the LoRA steps of one model reuse from step to step: the pinned staging of the tile lists with its device twin
-    (as LlamaModel._upload_plan keeps for the batch plan; grown when a step needs more) and the fp32 t workspace."""
-    __slots__ = ("host", "host_np", "dev", "done", "t")
+    (a LoRA step is eager: a twin that moves has nobody to tell) and the fp32 t workspace."""
+    first_words = 4096
 
     def __init__(self):
-        self.host = self.host_np = self.dev = self.done = self.t = None
-
-    def upload(self, words: np.ndarray, device) -> torch.Tensor:
-        n = int(words.size)
-        if self.done is not None:
-            self.done.synchronize()     # (the previous step's copy out of the pinned buffer: long done)
-        if self.host is None or self.host.numel() < n:
-            cap = max(4096, 2 * n)
-            self.host = torch.empty(cap, dtype=torch.int32, pin_memory=True)
-            self.host_np = self.host.numpy()
-            self.dev = torch.empty(cap, dtype=torch.int32, device=device)
-            self.done = torch.cuda.Event()
-        self.host_np[:n] = words
-        self.dev[:n].copy_(self.host[:n], non_blocking=True)
-        self.done.record()
-        return self.dev[:n]
+        super().__init__(lambda: None)
+        self.t = None
 
 
 class LoraBatch:
     """A step's row grouping on the device and the t workspace the step's projections share. `staging`: the model's
-    LoraStaging (one pinned buffer reused by every step); None: buffers of this batch's own (tests, tools)."""
-    __slots__ = ("tile_rows", "tile_slots", "num_tiles", "num_tokens", "_t", "_staging")
+    LoraStaging (one pinned buffer reused by every step); None: one of this batch's own (tests, tools)."""
+    __slots__ = ("tile_rows", "tile_slots", "num_tiles", "num_tokens", "_staging")
 
-    def __init__(self, row_slots: Sequence[int], num_slots: int, device, staging: "LoraStaging" = None):
+    def __init__(self, row_slots: Sequence[int], num_slots: int, device, staging: LoraStaging = None):
         rows, slots = build_tiles(row_slots, num_slots)
         self.num_tiles, self.num_tokens = int(slots.size), len(row_slots)
-        self._t, self._staging = None, staging
+        self._staging = staging = staging if staging is not None else LoraStaging()
         if self.num_tiles == 0:
             self.tile_rows = self.tile_slots = None
             return
         words = np.concatenate([slots, rows])       # one buffer, one H2D copy
-        if staging is not None:
-            dev = staging.upload(words, device)
-        else:
-            host = torch.from_numpy(words)
-            if torch.device(device).type == "cuda":
-                host = host.pin_memory()
-            dev = host.to(device, non_blocking=True)
-        self.tile_slots, self.tile_rows = dev[:self.num_tiles], dev[self.num_tiles:]
+        staging.ensure(max(words.size, staging.first_words))
+        staging.begin()[:words.size] = words
+        staging.ship([(0, words.size)])
+        self.tile_slots, self.tile_rows = staging.staged[:self.num_tiles], staging.staged[self.num_tiles:words.size]
 
     def workspace(self, floats: int, device) -> torch.Tensor:
-        keep = self._staging if self._staging is not None else self
-        t = keep.t if keep is not self else self._t
-        if t is None or t.numel() < floats:
-            t = torch.empty(floats, dtype=torch.float32, device=device)
-            if keep is self:
-                self._t = t
-            else:
-                keep.t = t
-        return t
+        keep = self._staging
+        if keep.t is None or keep.t.numel() < floats:
+            keep.t = torch.empty(floats, dtype=torch.float32, device=device)
+        return keep.t
 
 
 def _row_stride(t: torch.Tensor) -> int:

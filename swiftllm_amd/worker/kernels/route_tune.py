@@ -46,7 +46,7 @@ def table_wide_wins(m: int, n: int, k: int) -> bool:
         qkv  (N = 6144)  27/41  27/41  28/31  29/30  29/37  37/30  37/40  38/43   -> always
         o    (N = 4096)  22/28  22/24  22/32  23/26  24/36  29/27  29/29  30/27   -> up to 192
     (up to 128 tokens both were already ours.) Thresholds sit on the 32-token bucket edges of the hipGraph replay cache
-    (`LlamaModel._decode_batch_bucket`) and nowhere else: a batch of 200 runs as 200 rows eagerly and as 224 rows in a replayed
+    (`decode_replay.decode_batch_bucket`) and nowhere else: a batch of 200 runs as 200 rows eagerly and as 224 rows in a replayed
     graph, and both must take the same side — the library's one good qkv kernel at 208 tokens is therefore not used (the
     bucket's replay shape, 224, is ours: `test_large_decode_batches_replay_their_hip_graph_bit_for_bit`). The plain up/gate
     projection only ties (53 / 54 at 128) and loses beyond; its SiLU-gate form is `table_wide_silu_wins`."""

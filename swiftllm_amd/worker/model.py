@@ -19,6 +19,7 @@ so examples/offline.py and the Engine drive it unchanged. Inside, the host side 
   * KV pools, block tables and scheduler defaults are sized from the 288 GB of one MI355X.
 The compute backend is libswiftllm_hip.so only; without a HIP device this class raises.
 """
+import functools
 import math
 import os
 import time
@@ -38,6 +39,7 @@ from swiftllm_amd.utils import GB
 from .batch_plan import BatchPlan, plan_batch, plan_verify
 from .block_manager import BlockManager
 from . import decode_engine as _decode_engine
+from .decode_replay import DecodeReplay, decode_batch_bucket, graph_bucket, plan_decode, stage_plan
 from .infer_state import LlamaInferState
 from .kernels.block_swapping import swap_blocks
 from .kernels.kv_copy import kv_copy_blocks
@@ -49,7 +51,7 @@ from .lora import LoraBatch, LoraStaging, LoraStep, LoraStore, parse_lora_module
 from .layers.pre_layer import LlamaPreLayer
 from .layers.transformer_layer import LlamaTransformerLayer
 from .layers.post_layer import LlamaPostLayer
-from .step_logits import PLAIN, LogitsStage, StepLogits
+from .step_logits import PLAIN, LogitsStage, StagedInts, StepLogits
 from .token_history import TokenHistory, row_entries
 from .weight import load_weights, pack_decode_weights
 
@@ -63,19 +65,6 @@ def _require_hip_device():
             "no HIP device visible: swiftllm_amd's data plane runs only on an AMD GPU (gfx950) "
             "through libswiftllm_hip.so; there is no CPU path")
     _hip.load()
-
-
-class _DecodeGraph:
-    """A captured pure-decode forward for one batch size."""
-    __slots__ = ("graph", "out_tokens", "logits", "seq_block_size", "num_seq_blocks", "engine")
-
-
-class _DecodeLookahead:
-    """Everything the NEXT decode step of the same batch needs, prepared while the GPU was still busy with this one."""
-    __slots__ = ("seq_ids", "lens", "tokens", "plan", "dev", "logits")
-
-    def __init__(self):
-        self.logits = PLAIN     # the StepLogits of the step it was prepared behind
 
 
 class LlamaModel:
@@ -119,35 +108,29 @@ class LlamaModel:
         self.k_swap = self.v_swap = None
         self.cpu_block_manager = self.gpu_block_manager = None
 
-        self._meta_host = None      # pinned int32 staging for per-forward metadata
-        self._meta_host_np = None
-        self._meta_dev = None       # its device twin (fixed address: hipGraph replays read it)
-        self._meta_done = None
         self._num_slots = 256        # CUs: one 8-wave paged-attention workgroup each
-        self._decode_graphs = {}     # (batch, split width, split count, logits kept) + StepLogits.flags -> _DecodeGraph, LRU order
-        self._lookahead = None       # _DecodeLookahead of the step that is expected next (graph replay only)
-        self._decode_lookahead = True    # (tests switch it off to hold the fast path to the plain one)
         # optional callable, invoked by forward() in the calling thread once the step's kernels are enqueued and before
         # the host blocks on the sampled tokens (server/engine.py hides its per-request fan-out behind the running step)
         self.after_launch_hook = None
-        self._la_host = self._la_host_np = self._la_done = None
-        self._eager_uses_graph_buckets = False   # tests: eager launches at the replay path's split geometry
         # SWL_HOST_PROFILE=1: wall-clock split of forward() on the host (plan / blocks / upload / launch / wait for the
         # tokens), summed over calls — tools read it with host_profile()
         self._host_prof = {} if os.environ.get("SWL_HOST_PROFILE") else None
-        self._graph_pool = None
         self._scratch = None
         # the one-sequence persistent decode step (worker/decode_engine.py); None: shape / device / memory / switch say no
         self._engine = None
         self.engine_fallbacks = 0    # steps re-run on the multi-launch path after the engine reported a timed-out hand-off
-        self.graph_captures = 0      # hipGraph captures so far (the first at a batch bucket = one warm-up forward + one capture)
-        self.graph_capture_s = 0.0   # host seconds spent in them: serving reports both
-        self._warmed_buckets = set()
-        # a step's logits options (seeded sampling, logits processing, per-token logprobs, guided decoding): their persistent
-        # device buffers and pinned staging (worker/step_logits.py); one that grows moves, and the captured graphs go (bound
-        # weakly — a dropped model frees its HBM at once — and looked up at the call: tests wrap _drop_decode_graphs)
+        # hipGraph replay of pure-decode steps and the decode look-ahead (worker/decode_replay.py: what forgets a captured
+        # graph or a prepared step, and why, is listed there). It and the staged buffers below reach the model weakly — a
+        # dropped model frees its HBM at once — and look drop_graphs up at the call: tests wrap it on the replay object.
         me = weakref.ref(self)
-        self._logits = LogitsStage(lambda: me()._drop_decode_graphs())
+        graphs_moved = lambda: me().replay.drop_graphs()    # noqa: E731
+        # the per-forward metadata (batch_plan.py): pinned int32 staging and its device twin at a fixed address
+        self._plan_ints = StagedInts(graphs_moved)
+        self.replay = DecodeReplay(lambda *step: me()._stage_decode(*step), lambda *seqs: me()._plan_next_decode(*seqs),
+                                   self._plan_ints, engine_config)
+        # a step's logits options (seeded sampling, logits processing, per-token logprobs, guided decoding): their persistent
+        # device buffers and pinned staging (worker/step_logits.py); one that grows moves, and the captured graphs go
+        self._logits = LogitsStage(graphs_moved)
         # logits processing: the token history of every sequence that asks for it (worker/token_history.py; started by its
         # prefill, dropped by free_seqs_resources)
         self._histories = {}
@@ -165,6 +148,14 @@ class LlamaModel:
         self.lora_store = None
         self._lora_staging = LoraStaging()      # pinned staging of a LoRA step's tile lists + the t workspace, reused
         self._moe_tap = None
+
+    # what bench.py and the serving tools read of the replay cache (everything else of it: `replay`)
+    _decode_graphs = property(lambda self: self.replay.graphs)
+    graph_captures = property(lambda self: self.replay.captures)
+    graph_capture_s = property(lambda self: self.replay.capture_s)
+
+    def _graph_bucket(self, plan: BatchPlan):
+        return graph_bucket(plan)
 
     @property
     def moe_tap(self):
@@ -210,7 +201,7 @@ class LlamaModel:
         # (... as are the guide mask pool and the vocabulary's device form, when guided decoding is on)
         if int(getattr(ecfg, "guided_max_states", 0) or 0) > 0:
             self._init_guided()
-        self._logits.reserve(max(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
+        self._logits.reserve(max(decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_batch_size)))
         # (... and so are the adapter slot stacks: the KV pool is sized with them)
         if int(getattr(ecfg, "max_loras", 0) or 0) > 0:
             self.lora_store = LoraStore(self.model_config, int(ecfg.max_loras), int(ecfg.max_lora_rank), self.dtype,
@@ -385,7 +376,7 @@ class LlamaModel:
         # its share): a max_batch_size decode forward's activations, [B, vocab] logits (+ fp32 argmax candidates) and
         # split-K scratch. The eager prefill peak above does not contain it.
         graph_bytes = 0
-        if self._use_hip_graph:
+        if self.replay.on:
             graph_bytes = self._measure_decode_graph_bytes()
             free_memory, _ = torch.cuda.mem_get_info()      # (the measurement may have grown the regular pool as well)
             peak_memory = max(peak_memory, total_memory - free_memory)
@@ -404,11 +395,11 @@ class LlamaModel:
         """What the private memory pool of the decode hipGraphs will hold: MEASURED (r03-r04 used a formula) as
         the allocator's high-water mark over one eager pure-decode forward at max_batch_size on a throw-away KV pool of one
         block per sequence — a capture allocates what the eager forward allocates, into its own pool, and all captures share
-        ONE pool (_forward_decode_graph), so the largest batch sets its size. 25 % + 16 MiB on top for the allocator's
+        ONE pool (DecodeReplay.run), so the largest batch sets its size. 25 % + 16 MiB on top for the allocator's
         rounding. Falls back to the r04 formula when the throw-away pool cannot be built."""
         cfg, ecfg = self.model_config, self.engine_config
         # the largest CAPTURED batch: max_batch_size rounded up to its replay bucket (up to 15 inert rows more, ADVICE r05)
-        b = min(self._decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_seqs_in_block_table))
+        b = min(decode_batch_bucket(int(ecfg.max_batch_size)), int(ecfg.max_seqs_in_block_table))
         formula = b * cfg.vocab_size * 8 + b * (cfg.hidden_size + cfg.ffn_inter_dim) * 64 + (64 << 20)
         if b <= 0:
             return formula
@@ -429,9 +420,9 @@ class LlamaModel:
             torch.cuda.synchronize()
             peak = torch.cuda.max_memory_allocated() - base
             # + what every cached graph keeps alive in the shared pool after its capture: its sampled-token tensor (the
-            # [B, vocab] logits are retained only while a test taps them — _forward_decode_graph), rounded to the
+            # [B, vocab] logits are retained only while a test taps them — DecodeReplay.run), rounded to the
             # allocator's 512-byte granule, for a full replay cache
-            retained = self._MAX_DECODE_GRAPHS * (-(-b * 8 // 512) * 512 + 512)
+            retained = self.replay.max_graphs * (-(-b * 8 // 512) * 512 + 512)
             measured = int(peak * 1.25) + (16 << 20) + retained
             print(f"[Model.profile] decode activations at batch {b}: {peak / 2**20:.1f} MiB "
                   f"(hipGraph pool reserve {measured / 2**20:.1f} MiB; r04 formula: {formula / 2**20:.1f} MiB)")
@@ -441,8 +432,8 @@ class LlamaModel:
             return formula
         finally:
             self.k_cache, self.v_cache, self.gpu_block_manager, self.cpu_block_manager, ecfg.use_hip_graph = saved
-            self._lookahead = None
-            self._drop_decode_graphs()
+            self.replay.drop_prepared()
+            self.replay.drop_graphs()
             torch.cuda.empty_cache()
 
     @torch.inference_mode()
@@ -469,8 +460,8 @@ class LlamaModel:
         self.cpu_block_manager = BlockManager("CPU", ecfg.num_cpu_blocks,
                                               ecfg.max_seqs_in_block_table, ecfg.max_blocks_per_seq,
                                               ecfg.block_size, self.device)
-        self._drop_decode_graphs()
-        self._lookahead = None
+        self.replay.drop_graphs()
+        self.replay.drop_prepared()
 
     @torch.inference_mode()
     def set_kv_scales(self, k_scale: torch.Tensor, v_scale: torch.Tensor):
@@ -495,7 +486,7 @@ class LlamaModel:
             if mgr is not None and mgr.host.num_free_blocks < mgr.host.num_blocks:
                 raise RuntimeError("set_kv_scales while sequences hold KV blocks: their stored codes were quantised with "
                                    "the old scales (free or finish them first)")
-        self._lookahead = None
+        self.replay.drop_prepared()
         self.kv_scales.copy_(both)
         self.kv_inv_scales.copy_(1.0 / both)        # fp32 division on the host, one rounding
 
@@ -528,24 +519,6 @@ class LlamaModel:
         self._sin_cached = torch.sin(freqs).to(self.dtype).contiguous()
 
     # ------------------------------------------------------------------------------------------------
-    def _upload_plan(self, plan: BatchPlan):
-        """Pack the plan's int32 arrays into pinned memory, one async H2D copy, return device views."""
-        layout, total = plan.packed_layout()
-        if self._meta_done is not None:
-            self._meta_done.synchronize()
-        if self._meta_host is None or self._meta_host.numel() < total:
-            ecfg = self.engine_config
-            cap = max(total, 2 * ecfg.max_tokens_in_batch + 8 * ecfg.max_batch_size + 64)
-            self._meta_host = torch.empty(cap, dtype=torch.int32, pin_memory=True)
-            self._meta_host_np = self._meta_host.numpy()
-            self._meta_dev = torch.empty(cap, dtype=torch.int32, device=self.device)
-            self._meta_done = torch.cuda.Event()
-            self._drop_decode_graphs()     # captured graphs point into the old buffer
-        plan.pack_into(self._meta_host_np)
-        self._meta_dev[:total].copy_(self._meta_host[:total], non_blocking=True)
-        self._meta_done.record()
-        return {name: self._meta_dev[off:off + n] for name, off, n in layout}
-
     def _make_infer_state(self, plan: BatchPlan, dev: dict, ignore_kvcache: bool, opts: StepLogits = PLAIN,
                           scratch_rows: int = None) -> LlamaInferState:
         """`scratch_rows`: rows whose flash-decoding partials the persistent scratch must hold when the step splits its
@@ -556,7 +529,7 @@ class LlamaModel:
                                       self.model_config.num_q_heads, self.model_config.head_dim, nsb) // 4
             if self._scratch is None or self._scratch.numel() < need:
                 self._scratch = torch.empty(need, dtype=torch.float32, device=self.device)
-                self._drop_decode_graphs()
+                self.replay.drop_graphs()
         return LlamaInferState(
             batch_size=plan.batch_size, num_tokens=plan.num_tokens,
             seq_ids=dev["seq_ids"], softmax_scale=self.model_config.head_dim ** -0.5,
@@ -618,180 +591,19 @@ class LlamaModel:
         torch.cuda.synchronize()
         self._engine.reset()
         self._engine = None
-        self._drop_decode_graphs()
-        self._lookahead = None
+        self.replay.drop_graphs()
+        self.replay.drop_prepared()
         self.engine_fallbacks += 1
 
-    # ---- hipGraph replay of pure-decode steps ------------------------------------------------------------
-    @property
-    def _use_hip_graph(self) -> bool:       # (read at every use: tools flip it on a live model)
-        return getattr(self.engine_config, "use_hip_graph", False)
+    def _stage_decode(self, plan: BatchPlan, dev: dict, opts: StepLogits):
+        """DecodeReplay's way to one eager decode step: its infer state now (the scratch it sizes may move), the launch later."""
+        return functools.partial(self._forward, dev["input_ids"], self._make_infer_state(plan, dev, False, opts))
 
-    def _drop_decode_graphs(self):
-        """Forget every captured decode graph (their buffers moved, or the pool / engine they were captured against is gone)
-        AND the private memory pool they shared. The pool handle must go with them: once its last graph is destroyed the
-        caching allocator marks the pool freeable (use_count 0) but keeps it on its books until the next cache flush, and a
-        new capture into that id trips `it->second->use_count > 0` (HIPCachingAllocator.cpp) — met in r06 by the serving
-        sweep (tools/serve_bench.py --sweep: the flash-decoding scratch grew after graphs had been captured) and by
-        bench.py's engine leg. The next capture opens a fresh pool; the old one's memory returns to the device on the
-        allocator's next flush."""
-        self._decode_graphs.clear()
-        self._graph_pool = None
-        self._warmed_buckets.clear()     # (workspaces may have been re-sized: warm up again before the next capture)
-
-    # LRU bound of the replay cache. Since r06b a cached graph pins only its sampled-token tensor in the shared pool (the
-    # [B, vocab] logits are kept only under a test's tap), so the bound is about host-side graph objects, not HBM. 48 (r05)
-    # thrashed under a serving sweep with ShareGPT-like lengths at max batch 256: 14 batch buckets x ~5 single-split widths
-    # + the split geometries of small batches = well over 100 live keys, 23-53 captures per 1000 forwards at 40-200 req/s
-    # (profiles/r06b_serve_sweep_sharegpt_*.jsonl).
-    _MAX_DECODE_GRAPHS = 256
-
-    def _graph_bucket(self, plan: BatchPlan):
-        """Captured launch geometry must cover every replay, and the number of distinct geometries a long-running
-        server meets must stay small (every new one costs a warm-up run + a capture, and memory): the split width
-        — `select_seq_block_size` drifts in 64-token steps as sequences grow — is rounded up to a multiple of
-        1/16..1/32 of itself (at most 16 widths per octave), and the split count is taken for the longest sequence
-        rounded up to its next 64-token boundary and then to a power of two (surplus workgroups exit on their first
-        instruction). A single split stays a single split (its width only has to cover the longest sequence).
-        (r01/r02 rounded the width to a POWER of two: at Llama-2-7B dims, 4 x 16.4k tokens, that turned the balanced
-        8256 + 8139 split into 16384 + 11 — half the workgroups idle, the attention kernel 224 instead of 175 us and
-        graph replay 12 % slower than eager launches.)"""
-        sbs = int(plan.seq_block_size)
-        if plan.num_seq_blocks > 1:
-            quantum = max(64, 1 << max(0, sbs.bit_length() - 5))
-            sbs = -(-sbs // quantum) * quantum
-        horizon = -(-(plan.max_decoding_len + 1) // 64) * 64
-        nsb_cap = -(-horizon // sbs)
-        if nsb_cap > 1:
-            nsb_cap = 1 << (nsb_cap - 1).bit_length()
-        else:
-            # one split: any width >= the longest sequence is the same launch; key on a power of two of it
-            sbs = max(256, 1 << (horizon - 1).bit_length())
-        return sbs, nsb_cap
-
-    def _decode_batch_bucket(self, batch: int) -> int:
-        """Captured batch size that serves a pure-decode batch of `batch` sequences. The replay cache is keyed on the batch
-        size, and a server's batch drifts by one sequence at a time: keyed on the EXACT size (r01-r04) every new size paid a
-        warm-up forward plus a capture. Sizes are rounded up — to a multiple of 8 up to 32 sequences, of 16 up to 64, of 32
-        beyond (the projections' cost moves in 32-token blocks there) — and the surplus rows are INERT: length-0 sequences, which every
-        decode kernel treats as a no-op (paged attention: the workgroup exits before its prologue; rotary / KV store: nothing
-        read, nothing stored; the projections, norms and the sampler are row-independent, so whatever an inert row holds
-        never reaches a real one). 1 and 2 stay exact (their own launch path). The reference has no graphs
-        (swiftllm/worker/model.py:228-249 launches eagerly); results are those of the exact-size launch."""
-        if batch <= 2:
-            return batch
-        # r06b: 16 between 32 and 64 (the medium kernels serve two token blocks whatever the count), 32 beyond 64 (the wide
-        # GEMMs and the library work in 32-token blocks: 129 -> 160 costs what 144 did) — 14 buckets up to 256 instead of 22
-        step = 8 if batch <= 32 else 16 if batch <= 64 else 32
-        return -(-batch // step) * step
-
-    def _plan_decode(self, seq_ids_list: List[int], lens: List[int], tokens, pad: bool) -> BatchPlan:
-        """Plan of a pure-decode step; `pad`: rounded up to its batch bucket with inert rows (token 0, length 0)."""
-        b = len(lens)
-        bp = self._decode_batch_bucket(b) if pad else b
-        ids = tokens if tokens is not None else [(0,)] * b
-        if bp > b:
-            ids = list(ids) + [(0,)] * (bp - b)
-            seq_ids_list = list(seq_ids_list) + [seq_ids_list[0]] * (bp - b)
-            lens = list(lens) + [0] * (bp - b)
-        plan = plan_batch(ids, seq_ids_list, lens, self.model_config.num_kv_heads, self._num_slots)
-        plan.num_real_seqs = b
-        return plan
-
-    def _forward_decode_graph(self, plan: BatchPlan, dev: dict, opts: StepLogits = PLAIN) -> torch.Tensor:
-        sbs, nsb_cap = self._graph_bucket(plan)
-        use_engine = self._engine is not None and plan.batch_size == 1
-        tap = self.post_layer.logits_tap
-        tap_len = len(tap) if tap is not None else 0
-        # (the engine has one launch geometry; a graph captured while a test taps the logits keeps its [B, vocab] tensor
-        # alive in the shared pool, one captured without the tap does not — up to 65 MB per graph at 256 sequences, ADVICE r05)
-        # (each logits option in use makes the step a graph of its own: StepLogits.flags; plain graphs are as they were)
-        key = ((1, 0, 0) if use_engine else (plan.batch_size, sbs, nsb_cap)) + (tap is not None,) + opts.flags
-        entry = self._decode_graphs.pop(key, None)
-        plan.seq_block_size, plan.num_seq_blocks = sbs, nsb_cap
-        if entry is None:
-            self.graph_captures += 1
-            t_cap = time.perf_counter()
-            state = self._make_infer_state(plan, dev, False, opts)
-            # one eager run on a side stream first (library handles, workspaces, allocator pools): nothing may be lazily
-            # initialised while the stream is capturing. Once per BATCH BUCKET (r06b): a new split geometry at a batch size
-            # that has been captured before launches the same kernels on the same shapes — only the attention grid moves.
-            warm_key = (key[0], use_engine, tap is not None) + opts.flags
-            if warm_key not in self._warmed_buckets:
-                warm = torch.cuda.Stream()
-                warm.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(warm):
-                    self._forward(dev["input_ids"], state)
-                torch.cuda.current_stream().wait_stream(warm)
-                self._warmed_buckets.add(warm_key)
-            while len(self._decode_graphs) >= self._MAX_DECODE_GRAPHS:      # least recently used first
-                self._decode_graphs.pop(next(iter(self._decode_graphs)))
-            if self._graph_pool is None:
-                # ONE private memory pool for all captures: graphs never run concurrently (one stream), so they can
-                # share their activation memory instead of each pinning its own after the KV pool took the rest
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            entry = _DecodeGraph()
-            entry.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(entry.graph, pool=self._graph_pool):
-                entry.out_tokens = self._forward(dev["input_ids"], state)
-            entry.logits = self.post_layer.last_logits if tap is not None else None
-            if tap is None:
-                self.post_layer.last_logits = None      # (drop the last reference: the buffer returns to the shared pool)
-            entry.seq_block_size, entry.num_seq_blocks = sbs, nsb_cap
-            entry.engine = use_engine
-            if tap is not None:
-                del tap[tap_len:]               # what the warm-up run and the capture appended
-            self.graph_capture_s += time.perf_counter() - t_cap
-        self._decode_graphs[key] = entry        # (re)inserted last = most recently used
-        entry.graph.replay()
-        n = plan.real_seqs
-        if tap is not None:                     # (tests) one entry per forward, as on the eager path; a copy: the
-            tap.append(entry.logits[:n].clone())    # graph's own tensor is overwritten by the next replay
-        return entry.out_tokens[:n]
-
-    # ---- decode look-ahead: the host side of step k+1 runs while the GPU executes step k ---------------------------------
-    def _prepare_next_decode(self, plan: BatchPlan, seq_ids_list: List[int], tokens_dev: torch.Tensor, opts: StepLogits = PLAIN):
-        """Called right after the graph of a pure-decode step was launched, before the host blocks on its tokens. A
-        generation loop calls forward again with the same sequences, every length + 1 and the tokens just sampled: plan
-        that step now (numpy) and enqueue — behind the running graph, on the same stream — the H2D copy of its metadata and
-        a device copy of the sampled tokens into its input-id slots. If the next call is that step (forward checks), it
-        only takes its KV blocks and launches: ~40 us of host work per step the GPU no longer waits for
-        (tools/host_overhead.py: plan 18 + upload 24 us at batch 32). If it is not, nothing is lost: the ordinary path
-        re-plans and re-uploads. (Blocks are NOT taken early: a scheduler that counts the pool down to its last block must
-        find the allocator exactly where its own books say it is.)"""
-        b = plan.real_seqs
-        next_lens = [n + 1 for n in plan.seq_lengths_list[:b]]
-        if max(next_lens) > self._cos_cached.shape[0]:
+    def _plan_next_decode(self, seq_ids_list: List[int], lens: List[int]) -> Optional[BatchPlan]:
+        """DecodeReplay's plan of the step after a decode step; None when a sequence would leave the rotary table."""
+        if max(lens) > self._cos_cached.shape[0]:
             return None
-        nxt = self._plan_decode(seq_ids_list, next_lens, None, True)
-        layout, total = nxt.packed_layout()
-        if self._la_host is None or self._la_host.numel() < total:
-            self._la_host = torch.empty(max(total, self._meta_host.numel()), dtype=torch.int32, pin_memory=True)
-            self._la_host_np = self._la_host.numpy()
-            self._la_done = torch.cuda.Event()
-        else:
-            self._la_done.synchronize()     # (the previous look-ahead copy out of this pinned buffer: long done)
-        nxt.pack_into(self._la_host_np)
-        self._meta_dev[:total].copy_(self._la_host[:total], non_blocking=True)
-        self._la_done.record()
-        dev = {name: self._meta_dev[off:off + n] for name, off, n in layout}
-        dev["input_ids"][:b].copy_(tokens_dev)  # int64 -> int32 on the device: the host has not seen them yet (inert rows: 0)
-        la = _DecodeLookahead()     # (`logits`: what the next step must continue, StepLogits.continues)
-        la.seq_ids, la.lens, la.plan, la.dev, la.tokens, la.logits = list(seq_ids_list), next_lens, nxt, dev, None, opts
-        return la
-
-    def _take_lookahead(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts: StepLogits = PLAIN):
-        """The prepared step, if this call is it (any other call drops the preparation): the same sequences, every length
-        + 1, the tokens just returned, and logits options that continue those of the step it was prepared behind."""
-        la, self._lookahead = self._lookahead, None
-        if (la is None or la.tokens is None or ignore_kvcache or not self._decode_lookahead or not self._use_hip_graph
-                or len(input_ids_list) != len(la.lens) or list(decoding_seq_lens_list) != la.lens
-                or list(seq_ids_list) != la.seq_ids or not opts.continues(la.logits)):
-            return None
-        for ids, tok in zip(input_ids_list, la.tokens):
-            if len(ids) != 1 or ids[0] != tok:
-                return None
-        return la
+        return plan_decode(seq_ids_list, lens, None, True, self.model_config.num_kv_heads, self._num_slots)
 
     # ------------------------------------------------------------------------------------------------
     def _tokens_to_host(self, tokens: torch.Tensor, scoring=None) -> List[int]:
@@ -869,16 +681,16 @@ class LlamaModel:
             edits = self._track_histories(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                                           sampling_params or [None] * len(input_ids_list), prefill_ctx_lens, undo)
         opts = StepLogits.of(sampling, edits, scoring, guides)
+        step = functools.partial(self._forward_step, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache,
+                                 opts, prefill_ctx_lens, lora_slots)
         try:
             try:
-                return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts,
-                                          prefill_ctx_lens, lora_slots)
+                return step()
             except _decode_engine.DecodeEngineError as exc:
                 # bounded hand-off timed out inside the persistent one-sequence step: its KV writes are re-done below with
                 # the same values by the multi-launch HIP path, which serves one-sequence steps from here on
                 self._engine_failed(int(str(exc)))
-                return self._forward_step(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts,
-                                          prefill_ctx_lens, lora_slots)
+                return step()
         except BaseException:
             self._rollback_histories(undo)
             raise
@@ -1002,9 +814,31 @@ class LlamaModel:
         if not ignore_kvcache:
             self.gpu_block_manager.allocate_blocks_for_seqs(seq_ids_list, plan.seq_lengths_list[:num_real])
         t_blocks = time.perf_counter()
-        dev = self._upload_plan(plan)
+        ecfg = self.engine_config       # (pinned memory, one async H2D copy; the buffer's first capacity serves any step)
+        dev = stage_plan(self._plan_ints, plan, 2 * ecfg.max_tokens_in_batch + 8 * ecfg.max_batch_size + 64)
         self._logits.upload(opts, plan.batch_size)
         return dev, t_plan, t_blocks
+
+    def _launch_eager(self, plan: BatchPlan, seq_ids_list, ignore_kvcache: bool = False, opts: StepLogits = PLAIN,
+                      lora=None, scratch_rows: int = None):
+        """The eager step, whoever drives it: _begin_step, the infer state (`lora`, `scratch_rows`: what a LoRA and a verify
+        step attach), the forward, after_launch_hook. Returns every row's token and the host times of host_profile's sections."""
+        dev, t_plan, t_blocks = self._begin_step(plan, seq_ids_list, ignore_kvcache, opts)
+        t_upload = time.perf_counter()
+        state = self._make_infer_state(plan, dev, ignore_kvcache, opts, scratch_rows)
+        state.lora = lora
+        tokens = self._forward(dev["input_ids"], state)
+        if self.after_launch_hook is not None:
+            self.after_launch_hook()
+        return tokens, (t_plan, t_blocks, t_upload)
+
+    def _launch_replay(self, plan: BatchPlan, dev: dict, seq_ids_list, opts: StepLogits):
+        """A pure-decode step on the replay path: its graph, then — behind it — the preparation of the step expected next."""
+        tokens = self.replay.run(plan, dev, opts, self._engine is not None and plan.batch_size == 1, self.post_layer)
+        self.replay.prepare_next(plan, seq_ids_list, tokens, opts)
+        if self.after_launch_hook is not None:
+            self.after_launch_hook()
+        return tokens
 
     def _forward_step(self, input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts: StepLogits = PLAIN,
                       prefill_ctx_lens=None, lora_slots=None):
@@ -1014,44 +848,39 @@ class LlamaModel:
             return self._forward_step_lora(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts,
                                            prefill_ctx_lens, lora_slots)
         if self._moe_tap is not None:
-            self._lookahead = None      # (tests) a tapped step copies the routing to the host: eager, not a replay
-        la = self._take_lookahead(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts)
+            self.replay.drop_prepared()     # (tests) a tapped step copies the routing to the host: eager, not a replay
+        la = self.replay.take(input_ids_list, seq_ids_list, decoding_seq_lens_list, ignore_kvcache, opts)
         if la is not None:      # the step that was prepared while the previous one ran: blocks, then the launch
             self.gpu_block_manager.allocate_blocks_for_seqs(la.seq_ids, la.lens)   # (the real sequences only)
             self._logits.upload(opts, la.plan.batch_size, hit=True)
-            tokens = self._forward_decode_graph(la.plan, la.dev, opts)
-            nxt = self._prepare_next_decode(la.plan, la.seq_ids, tokens, opts)
+            tokens = self._launch_replay(la.plan, la.dev, la.seq_ids, opts)
         else:
             num_real = len(input_ids_list)
             pure_decode = len(decoding_seq_lens_list) == num_real and not ignore_kvcache
-            graph_step = pure_decode and self._use_hip_graph and self._moe_tap is None
-            if graph_step or (pure_decode and self._eager_uses_graph_buckets):
-                # pure decode on the replay path: the batch is rounded up to its bucket with inert rows (_decode_batch_bucket)
-                plan = self._plan_decode(seq_ids_list, list(decoding_seq_lens_list), input_ids_list, True)
+            graph_step = pure_decode and self.replay.on and self._moe_tap is None
+            in_buckets = pure_decode and self.replay.eager_in_buckets
+            if graph_step or in_buckets:
+                # pure decode on the replay path: the batch is rounded up to its bucket with inert rows (decode_batch_bucket)
+                plan = plan_decode(seq_ids_list, list(decoding_seq_lens_list), input_ids_list, True,
+                                   self.model_config.num_kv_heads, self._num_slots)
             else:
                 plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                                   self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
-            dev, t1, t2 = self._begin_step(plan, seq_ids_list, ignore_kvcache, opts)
-            t3 = time.perf_counter() if prof is not None else 0.0
-            nxt = None
             if graph_step:
-                tokens = self._forward_decode_graph(plan, dev, opts)
-                if self._decode_lookahead:
-                    nxt = self._prepare_next_decode(plan, list(seq_ids_list), tokens, opts)
+                dev, t1, t2 = self._begin_step(plan, seq_ids_list, ignore_kvcache, opts)
+                t3 = time.perf_counter()
+                tokens = self._launch_replay(plan, dev, list(seq_ids_list), opts)
             else:
-                if pure_decode and self._eager_uses_graph_buckets:
-                    plan.seq_block_size, plan.num_seq_blocks = self._graph_bucket(plan)
-                tokens = self._forward(dev["input_ids"], self._make_infer_state(plan, dev, ignore_kvcache, opts))[:num_real]
+                if in_buckets:
+                    plan.seq_block_size, plan.num_seq_blocks = graph_bucket(plan)
+                tokens, (t1, t2, t3) = self._launch_eager(plan, seq_ids_list, ignore_kvcache, opts)
+                tokens = tokens[:num_real]
                 tap = self.post_layer.logits_tap
                 if tap and plan.batch_size > num_real:      # (tests) a padded eager step: the real rows only, as on replay
                     tap[-1] = tap[-1][:num_real]
-        if self.after_launch_hook is not None:
-            self.after_launch_hook()
         t4 = time.perf_counter() if prof is not None else 0.0
         out = self._tokens_to_host(tokens, opts.scoring)
-        if nxt is not None:
-            nxt.tokens = out
-        self._lookahead = nxt
+        self.replay.tokens_known(out)
         if prof is not None:
             t5 = time.perf_counter()
             sections = ((("launch", t4 - t0), ("lookahead_hits", 1.0)) if la is not None else      # (a hit: all of it is launch)
@@ -1064,19 +893,15 @@ class LlamaModel:
                            prefill_ctx_lens, lora_slots):
         """A step with at least one adapter row: the plain plan of the batch (never padded to a replay bucket), eager
         launches, the prepared look-ahead dropped; the row -> slot tiles go up in a buffer of their own."""
-        self._lookahead = None
+        self.replay.drop_prepared()
         num_real = len(input_ids_list)
         plan = plan_batch(input_ids_list, seq_ids_list, decoding_seq_lens_list,
                           self.model_config.num_kv_heads, self._num_slots, prefill_ctx_lens=prefill_ctx_lens)
-        dev = self._begin_step(plan, seq_ids_list, ignore_kvcache, opts)[0]
         num_prefill = num_real - len(decoding_seq_lens_list)
         row_slots = rows_of_sequences(lora_slots, [len(ids) for ids in input_ids_list[:num_prefill]])
-        state = self._make_infer_state(plan, dev, ignore_kvcache, opts)
-        state.lora = LoraStep(LoraBatch(row_slots, self.lora_store.max_loras, self.device, self._lora_staging),
-                              self.lora_store.layers)
-        tokens = self._forward(dev["input_ids"], state)[:num_real]
-        if self.after_launch_hook is not None:
-            self.after_launch_hook()
+        lora = LoraStep(LoraBatch(row_slots, self.lora_store.max_loras, self.device, self._lora_staging),
+                        self.lora_store.layers)
+        tokens = self._launch_eager(plan, seq_ids_list, ignore_kvcache, opts, lora=lora)[0][:num_real]
         if self._host_prof is not None:
             self._host_prof["calls"] = self._host_prof.get("calls", 0.0) + 1.0
         return self._tokens_to_host(tokens, opts.scoring)
@@ -1123,14 +948,10 @@ class LlamaModel:
                              "argmax of the raw logits")
         ctx = [int(c) for c in ctx_lens]
         self._check_prefill_ctx(input_ids_list, seq_ids_list, [], False, ctx)     # (all-zero contexts pass: None)
-        self._lookahead = None      # a prepared decode step does not survive a verify step
+        self.replay.drop_prepared()     # a prepared decode step does not survive a verify step
         self.gpu_block_manager.host.surplus_ok.update(seq_ids_list)     # rejected drafts leave their block with the sequence
         plan = plan_verify(input_ids_list, seq_ids_list, ctx, self.model_config.num_kv_heads, self._num_slots)
-        dev = self._begin_step(plan, seq_ids_list)[0]
-        tokens = self._forward(dev["input_ids"], self._make_infer_state(plan, dev, False, PLAIN, plan.num_tokens))
-        if self.after_launch_hook is not None:
-            self.after_launch_hook()
-        flat = tokens.tolist()
+        flat = self._launch_eager(plan, seq_ids_list, scratch_rows=plan.num_tokens)[0].tolist()
         out, at = [], 0
         for ids in input_ids_list:
             out.append(flat[at:at + len(ids)])
@@ -1152,7 +973,7 @@ class LlamaModel:
         Reference: model.py:361-379. Block ids come from the host mirrors — no device read-back."""
         if len(seq_ids_list) == 0:
             return
-        self._lookahead = None
+        self.replay.drop_prepared()
         src_mgr = self.cpu_block_manager if is_swap_in else self.gpu_block_manager
         dst_mgr = self.gpu_block_manager if is_swap_in else self.cpu_block_manager
         counts = src_mgr.get_num_allocated_blocks_host(seq_ids_list)
@@ -1179,7 +1000,7 @@ class LlamaModel:
         """Release everything the sequences hold, on both pools. Reference: model.py:402-408."""
         if len(seq_ids_list) == 0:
             return
-        self._lookahead = None
+        self.replay.drop_prepared()
         for sid in seq_ids_list:
             self._histories.pop(sid, None)
         self.gpu_block_manager.free_blocks_for_seqs(seq_ids_list)
@@ -1225,7 +1046,7 @@ class LlamaModel:
                 raise ValueError(f"copy_kv_prefix: destination sequence {dst} already owns "
                                  f"{mgr.host.num_allocated(dst)} blocks")
         src_blocks = [b for src, n in zip(src_seq_ids, num_tokens) for b in mgr.get_block_ids_host(src)[:n // bs]]
-        self._lookahead = None
+        self.replay.drop_prepared()
         mgr.allocate_blocks_for_seqs(dst_seq_ids, num_tokens)      # (raises before it commits when the pool is short)
         dst_blocks = [b for dst in dst_seq_ids for b in mgr.get_block_ids_host(dst)]
         if len(dst_blocks) != len(src_blocks) or not sources.isdisjoint(dst_seq_ids) or set(dst_blocks) & set(src_blocks):

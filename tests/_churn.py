@@ -280,36 +280,38 @@ class TraceRecorder:
       sampled, processed, any_params   some row draws / has its logits processed / has sampling params at all (forward)
       accepted, drafts  per sequence (verify)
       state         (num_prefilled, prompt_len, outputs) of each request at the call (swap_out, swap_in, free)
-    On a LlamaModel (it has _take_lookahead) also: `lookahead` (the prepared step was taken), `la_dropped` (a prepared step
+    On a LlamaModel (it has a `replay`, worker/decode_replay.py) also: `lookahead` (the prepared step was taken), `la_dropped` (a prepared step
     existed and this call dropped it), `graph_key` (the replayed graph), `captured` (it was captured by this call), and
-    `drops` (captured graphs forgotten by _drop_decode_graphs during this call). `before_free` callbacks run with the
+    `drops` (captured graphs forgotten by replay.drop_graphs during this call). `before_free` callbacks run with the
     sequence ids before the blocks go."""
     NAMES = ("forward", "forward_verify", "swap_in_seqs", "swap_out_seqs", "free_seqs_resources")
-    SPIES = ("_take_lookahead", "_forward_decode_graph", "_drop_decode_graphs")
+    SPIES = ("take", "run", "drop_graphs")
 
     def __init__(self, model, resolve):
         self.model, self.resolve = model, resolve
         self.events = []
         self.before_free = []
         self._cur = None
-        self._real = hasattr(model, "_take_lookahead")
-        self._inner = {name: getattr(model, name) for name in self.NAMES + (self.SPIES if self._real else ())}
+        self.replay = getattr(model, "replay", None)
+        self._real = self.replay is not None
+        self._inner = {name: getattr(model, name) for name in self.NAMES}
+        self._inner.update({name: getattr(self.replay, name) for name in (self.SPIES if self._real else ())})
         model.forward, model.forward_verify = self._forward, self._verify
         model.swap_in_seqs = functools.partial(self._move, "swap_in")
         model.swap_out_seqs = functools.partial(self._move, "swap_out")
         model.free_seqs_resources = functools.partial(self._move, "free")
         if self._real:
-            model._take_lookahead, model._forward_decode_graph = self._spy_lookahead, self._spy_graph
-            model._drop_decode_graphs = self._spy_drop
+            self.replay.take, self.replay.run = self._spy_lookahead, self._spy_graph
+            self.replay.drop_graphs = self._spy_drop
 
     def detach(self):
         for name in self._inner:
-            delattr(self.model, name)
+            delattr(self.replay if name in self.SPIES else self.model, name)
 
     def _open(self, kind, seq_ids, **fields):
         ev = dict(kind=kind, seq_ids=list(seq_ids), reqs=[self.resolve(s) for s in seq_ids], drops=0, **fields)
         if self._real:
-            ev["la_pending"] = self.model._lookahead is not None
+            ev["la_pending"] = self.replay.prepared is not None
         self.events.append(ev)
         self._cur = ev
         return ev
@@ -351,7 +353,7 @@ class TraceRecorder:
         self._close(ev)
 
     def _spy_lookahead(self, *args, **kw):
-        la = self._inner["_take_lookahead"](*args, **kw)
+        la = self._inner["take"](*args, **kw)
         ev = self._cur
         if ev is not None and "lookahead" not in ev:       # (the engine fallback runs a step twice: the first call counts)
             ev["lookahead"] = la is not None
@@ -359,21 +361,21 @@ class TraceRecorder:
         return la
 
     def _spy_graph(self, *args, **kw):
-        before = self.model.graph_captures
-        out = self._inner["_forward_decode_graph"](*args, **kw)
+        before = self.replay.captures
+        out = self._inner["run"](*args, **kw)
         if self._cur is not None:
-            self._cur["graph_key"] = next(reversed(self.model._decode_graphs))     # (re)inserted last = the one replayed
-            self._cur["captured"] = self.model.graph_captures > before
+            self._cur["graph_key"] = next(reversed(self.replay.graphs))     # (re)inserted last = the one replayed
+            self._cur["captured"] = self.replay.captures > before
         return out
 
     def _spy_drop(self):
         if self._cur is not None:
-            self._cur["drops"] += len(self.model._decode_graphs)
-        return self._inner["_drop_decode_graphs"]()
+            self._cur["drops"] += len(self.replay.graphs)
+        return self._inner["drop_graphs"]()
 
 
 def bucket(batch: int) -> int:
-    """LlamaModel._decode_batch_bucket for batches of at most 32 sequences."""
+    """decode_replay.decode_batch_bucket for batches of at most 32 sequences."""
     return batch if batch <= 2 else -(-batch // 8) * 8
 
 

@@ -1,7 +1,7 @@
 """Correctness at BASELINE configs[3] geometry: Llama-2-7B heads (32 query = 32 kv heads of 128:
 G = 1, the VALU attend_block of csrc/paged_attn.hip, not the matrix-core one), batch 4, ~16.4k-token contexts,
 multi-split flash-decoding — the launch geometry the product picks for it with eager launches (batch_plan) AND the one
-hipGraph replay buckets it to (LlamaModel._graph_bucket) — against the CPU oracle, against the compiled reference
+hipGraph replay buckets it to (decode_replay.graph_bucket) — against the CPU oracle, against the compiled reference
 Triton kernel, and end to end (2 layers at Llama-2-7B width, KV pool filled directly: no 16k-token prompt pass on the
 CPU side) with graph replay held bit-equal to eager launches at the replay geometry.
 
@@ -35,10 +35,10 @@ LENS = [16416, 16405, 16384, 16385]     # BASELINE configs[3]: 4 x ~16k, around 
 def _geometries():
     """(name, seq_block_size, num_seq_blocks) the product launches this batch with: eager plan and replay bucket."""
     from swiftllm_amd.worker.batch_plan import plan_batch
-    from swiftllm_amd.worker.model import LlamaModel
+    from swiftllm_amd.worker.decode_replay import graph_bucket
     plan = plan_batch([[0]] * len(LENS), list(range(len(LENS))), LENS, KVH, 256)
     eager = (int(plan.seq_block_size), int(plan.num_seq_blocks))
-    bucket = LlamaModel._graph_bucket(None, plan)
+    bucket = graph_bucket(plan)
     return [("eager_plan",) + eager, ("graph_bucket",) + tuple(int(x) for x in bucket)]
 
 
@@ -154,7 +154,7 @@ def test_configs3_decode_forward_vs_oracle_and_replay_equals_eager(tmp_path, dty
         with torch.inference_mode():
             model.k_cache.copy_(k0)
             model.v_cache.copy_(v0)
-        model._eager_uses_graph_buckets = bucketed
+        model.replay.eager_in_buckets = bucketed
         model.post_layer.logits_tap = []
         toks, logits, c, f = [], [], list(first), toks0
         for s in range(steps):

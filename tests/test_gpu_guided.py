@@ -249,7 +249,7 @@ def _first_argmax(row: torch.Tensor) -> int:
 @pytest.mark.parametrize("mode", ["graph_lookahead", "graph_no_lookahead", "eager"])
 def test_model_masks_the_logits_the_token_is_picked_from(tmp_path, dtype, mode):
     model, cfg = _model(tmp_path, dtype, use_hip_graph=mode != "eager")
-    model._decode_lookahead = mode == "graph_lookahead"
+    model.replay.lookahead = mode == "graph_lookahead"
     v = cfg["vocab_size"]
     prompts = _prompts(v)
     pattern = "[0-9]{4}-[0-9]{2}"
@@ -271,7 +271,7 @@ def test_model_masks_the_logits_the_token_is_picked_from(tmp_path, dtype, mode):
     assert cursors[0].complete and re.fullmatch(pattern.encode(), cursors[0].text)
     assert cursors[2].complete and cursors[2].text in (b"yes", b"no", b"maybe")
     if mode == "graph_lookahead":
-        assert model.graph_captures >= 1
+        assert model.replay.captures >= 1
     for c in (cursors[0], cursors[2]):
         model.guide_store.release(c.guide)
 
@@ -508,19 +508,19 @@ def test_nothing_asked_nothing_launched(tmp_path, monkeypatch):
     model, cfg = _model(tmp_path, use_hip_graph=True)
     trace(model, prompts, "absent")                      # (captures the plain graph)
     plain_toks, plain = trace(model, prompts, "absent")  # ... and this is what its replay launches
-    captures = model.graph_captures
+    captures = model.replay.captures
     cur = _cursor(model, "tokens", [5, 6, 7])
     del seen[:]
     _drive(model, prompts, [0, 1, 2], [None, cur, None], 3)
     assert seen.count("swl_guide_build_masks") == 0      # (an allowed-token guide: its row is written by the host)
     assert seen.count("swl_logits_mask") == 1 + 2        # the prefill, the warm-up run and the capture of the guided graph
-    assert model.graph_captures == captures + 1
+    assert model.replay.captures == captures + 1
     cur2 = _cursor(model, "regex", "[0-9]+")
     del seen[:]
     _drive(model, prompts, [0, 1, 2], [cur2, None, None], 3)
     assert seen.count("swl_guide_build_masks") == 1 and seen.count("swl_logits_mask") == 1     # built once; graph replayed
     assert trace(model, prompts, "absent") == (plain_toks, plain)
-    assert "swl_logits_mask" not in plain and model.graph_captures == captures + 1
+    assert "swl_logits_mask" not in plain and model.replay.captures == captures + 1
 
 
 # ---- the engine -----------------------------------------------------------------------------------------------------------

@@ -234,7 +234,7 @@ def _model(tmp_path, dtype, graph=False, guide_vocab=None, **kw):
         model.set_guide_vocab(guide_vocab(cfg["vocab_size"]))
     model.load_weights()
     model.init_kvcache_and_swap(40)
-    model._eager_uses_graph_buckets = True      # eager steps at the replay path's batch bucket and split geometry
+    model.replay.eager_in_buckets = True      # eager steps at the replay path's batch bucket and split geometry
     return model, cfg
 
 
@@ -282,13 +282,13 @@ def _generate(model, prompts, sps, chunk=None, tap=False):
 
 def _count_lookahead_hits(model):
     """Wrap the model's look-ahead lookup; returns a one-element list holding the number of hits so far."""
-    hits, inner = [0], model._take_lookahead
+    hits, inner = [0], model.replay.take
 
     def spy(*a, **kw):
         la = inner(*a, **kw)
         hits[0] += la is not None
         return la
-    model._take_lookahead = spy
+    model.replay.take = spy
     return hits
 
 
@@ -358,16 +358,16 @@ def test_model_streams_are_the_same_on_every_path(tmp_path, dtype):
     assert [t[0] for t in want] == [t[0] for t in plain]                # the plain row is the all-plain stream
     assert [t[1] for t in want] != [t[1] for t in plain]                # ... and the penalties change theirs
     assert _generate(model, prompts, sps, chunk=16)[0] == want          # the 40-token prompt in chunks of 16
-    model._decode_lookahead = False
+    model.replay.lookahead = False
     assert _generate(model, prompts, sps)[0] == want
     del model
     graph, _ = _model(tmp_path, dtype, graph=True)
     hits = _count_lookahead_hits(graph)
     assert _generate(graph, prompts, sps)[0] == want                    # replay + look-ahead hits
-    assert graph.graph_captures > 0
+    assert graph.replay.captures > 0
     assert hits[0] >= STEPS - 1         # every decode step but the first is the prepared one: entries uploaded on a hit
     assert _generate(graph, prompts, sps, chunk=16)[0] == want
-    graph._decode_lookahead = False
+    graph.replay.lookahead = False
     hits[0] = 0
     assert _generate(graph, prompts, sps)[0] == want                    # replay, every step planned afresh
     assert hits[0] == 0
@@ -386,16 +386,16 @@ def test_entry_buffer_growth_drops_the_graphs_and_the_stream_goes_on(tmp_path, d
     from swiftllm_amd.worker.step_logits import StagedInts
     stage = graph._logits
     stage.min_edit_cap, stage.one_copy_words = 8, 16
-    stage.edits = StagedInts(graph._drop_decode_graphs)     # (allocated at load with the class's capacity)
+    stage.edits = StagedInts(graph.replay.drop_graphs)     # (allocated at load with the class's capacity)
     stage.edit_rows = 0
     hits = _count_lookahead_hits(graph)
     log = []            # per forward: (buffer words, captures so far, look-ahead hits so far, graphs cached before the call)
     inner = graph.forward
 
     def spy(*a, **kw):
-        cached = len(graph._decode_graphs)
+        cached = len(graph.replay.graphs)
         out = inner(*a, **kw)
-        log.append((stage.edits.dev.numel(), graph.graph_captures, hits[0], cached))
+        log.append((stage.edits.dev.numel(), graph.replay.captures, hits[0], cached))
         return out
     graph.forward = spy
     assert _generate(graph, prompts, sps)[0] == want
@@ -447,7 +447,7 @@ def test_every_staged_buffer_can_move_under_captured_graphs(tmp_path, dtype):
     assert all(t[2] in allowed for t in want) and len({t[3] for t in want}) > 1
     del eager
     graph, _ = build(True)
-    stage, drop = graph._logits, graph._drop_decode_graphs
+    stage, drop = graph._logits, graph.replay.drop_graphs
     stage.min_edit_cap, stage.one_copy_words, stage.edit_rows = 8, 16, 0
     stage.sampling, stage.edits = StagedInts(drop), StagedInts(drop)
     stage.scores = StagedInts(drop, idle=-1, tail=stage.scores.tail)
@@ -457,7 +457,7 @@ def test_every_staged_buffer_can_move_under_captured_graphs(tmp_path, dtype):
     assert rows() == (1, 1, 1, 1)
     hits = _count_lookahead_hits(graph)
     log = []        # per decode step: (edit buffer words, captures so far)
-    got, got_scores = stream(graph, lambda: log.append((stage.edits.words, graph.graph_captures)))
+    got, got_scores = stream(graph, lambda: log.append((stage.edits.words, graph.replay.captures)))
     assert got == want
     for step, (a, b) in enumerate(zip(got_scores, want_scores)):
         assert [s is None for s in a] == [s is None for s in b] == [False, True, True, True], step

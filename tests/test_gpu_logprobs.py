@@ -408,20 +408,20 @@ def test_a_run_that_asks_for_nothing_launches_what_it_launched(tmp_path, monkeyp
     monkeypatch.setattr(_hip, "call", spy)
     quiet = [None, _sp(stop_token_ids=(1,)), _sp(0.7, seed=3)]       # params, but nobody asks
     plain_toks = _run(model, prompts, lambda k: None)[0]
-    captures = model.graph_captures
-    assert captures == len(model._decode_graphs) == 1 and "swl_logprobs" not in seen
+    captures = model.replay.captures
+    assert captures == len(model.replay.graphs) == 1 and "swl_logprobs" not in seen
     _run(model, prompts, lambda k: quiet)
     assert "swl_logprobs" not in seen
-    quiet_captures = model.graph_captures
+    quiet_captures = model.replay.captures
     seen.clear()
     _run(model, prompts, lambda k: [_sp(logprobs=1)] * 3)
     assert seen.count("swl_logprobs") == 1 + 2      # the prefill, the warm-up run and the capture of the scored graph
-    scored_captures = model.graph_captures
+    scored_captures = model.replay.captures
     assert scored_captures == quiet_captures + 1
     # ... and afterwards: the plain run replays the graph it captured, entry point for entry point
     seen.clear()
     assert _run(model, prompts, lambda k: None)[0] == plain_toks
-    assert model.graph_captures == scored_captures and "swl_logprobs" not in seen
+    assert model.replay.captures == scored_captures and "swl_logprobs" not in seen
 
 
 # ---- the engine ----------------------------------------------------------------------------------------------------------

@@ -324,7 +324,7 @@ def test_nothing_changes_when_no_adapter_is_named(tmp_path):
             toks = _run(model, prompts, 6, [0, 1, 2], lora=[None, None, None])
         else:
             toks = _run(model, prompts, 6, [0, 1, 2])
-        runs.append((toks, [t.clone() for t in model.post_layer.logits_tap], model.graph_captures))
+        runs.append((toks, [t.clone() for t in model.post_layer.logits_tap], model.replay.captures))
         del model
     (t0, l0, c0), (t1, l1, c1) = runs
     assert t0 == t1 and c0 == c1 and c0 >= 1

@@ -294,7 +294,7 @@ def test_full_width_layers_fast_path_equals_reference_op_sequence(tmp_path, dtyp
         model = LlamaModel(_engine_config(str(tmp_path), **base, **opts))
         model.load_weights()
         model.init_kvcache_and_swap(48 * 48)
-        model._eager_uses_graph_buckets = bucketed
+        model.replay.eager_in_buckets = bucketed
         model.post_layer.logits_tap = []
         tap = model.post_layer.logits_tap
         toks = [model.forward(prompts, seq_ids, [])]
@@ -328,7 +328,7 @@ def test_full_width_layers_fast_path_equals_reference_op_sequence(tmp_path, dtyp
                 if x != y:
                     top2 = ref_logits[step][seq].topk(2).values
                     assert float(top2[0] - top2[1]) <= 8 * eps * float(top2[0].abs().clamp(min=1.0)), (name, step, seq)
-    # Graph replay buckets the flash-decoding split geometry (model._graph_bucket: width rounded to a 1/16..1/32
+    # Graph replay buckets the flash-decoding split geometry (decode_replay.graph_bucket: width rounded to a 1/16..1/32
     # quantum, count to a power of two), so its fp32 summation order may differ from the eager plan's; at the SAME
     # geometry replay and eager launches are the same kernels on the same data: bit-equal logits and tokens.
     assert results["hipgraph"][0] == results["eager_bucketed"][0]
@@ -440,7 +440,7 @@ def test_decode_fast_path_survives_realistic_norm_weights_and_residual_outliers(
 @pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
 def test_decode_lookahead_changes_nothing_but_the_host_path(tmp_path, dtype):
     """LlamaModel prepares the next decode step's metadata while the GPU runs the current one (model.py:
-    _prepare_next_decode) and skips plan + upload when the next call is exactly that step. Same graphs, same kernels, same
+    DecodeReplay.prepare_next) and skips plan + upload when the next call is exactly that step. Same graphs, same kernels, same
     data: tokens and logits must be BIT-equal to the model with the look-ahead off, through block-boundary crossings,
     graph-bucket changes, a call that breaks the prediction (other input tokens), a freed-and-reused sequence slot, a
     prefill in between, and a shrinking batch; and the fast path must actually have been taken."""
@@ -455,7 +455,7 @@ def test_decode_lookahead_changes_nothing_but_the_host_path(tmp_path, dtype):
         def run(lookahead):
             model = _make_model(tmp_path / ("on" if lookahead else "off"), cfg, sd, 64, max_blocks_per_seq=32,
                                 max_tokens_in_batch=512, dtype=dtype)
-            model._decode_lookahead = lookahead
+            model.replay.lookahead = lookahead
             tap = model.post_layer.logits_tap
             trace = []
 
@@ -630,7 +630,7 @@ def test_large_decode_batches_replay_their_hip_graph_bit_for_bit(tmp_path, batch
         toks = _run_script(model, prompts, 4)
         runs[graph] = (toks, [t.clone() for t in model.post_layer.logits_tap])
         if graph:
-            assert len(model._decode_graphs) >= 1
+            assert len(model.replay.graphs) >= 1
         del model
         torch.cuda.empty_cache()
     assert runs[True][0] == runs[False][0]
@@ -664,8 +664,8 @@ def test_graphs_are_recaptured_after_the_flash_decoding_scratch_grows(tmp_path):
             out.append(toks[0])
         pools = []
         if graph:
-            assert len(model._decode_graphs) >= 1
-            pools.append(model._graph_pool)
+            assert len(model.replay.graphs) >= 1
+            pools.append(model.replay.pool)
             scratch0 = model._scratch.numel() if model._scratch is not None else 0
         for step in range(3):                   # all six: a larger scratch, every graph dropped, new captures
             lens = [n + 1 for n in lens]
@@ -673,7 +673,7 @@ def test_graphs_are_recaptured_after_the_flash_decoding_scratch_grows(tmp_path):
             out.append(list(toks))
         if graph:
             assert model._scratch is not None and model._scratch.numel() > scratch0, "the scenario did not grow the scratch"
-            assert model._graph_pool is not None and model._graph_pool != pools[0]
+            assert model.replay.pool is not None and model.replay.pool != pools[0]
         runs[graph] = (out, [t.clone() for t in model.post_layer.logits_tap])
         del model
         torch.cuda.empty_cache()
@@ -684,7 +684,7 @@ def test_graphs_are_recaptured_after_the_flash_decoding_scratch_grows(tmp_path):
 
 @pytest.mark.parametrize("dtype", ["float16", "bfloat16"])
 def test_decode_batch_buckets_replay_equals_exact_eager_launches(tmp_path, dtype):
-    """hipGraph replay rounds a pure-decode batch up to its bucket with inert rows (worker/model.py: _decode_batch_bucket):
+    """hipGraph replay rounds a pure-decode batch up to its bucket with inert rows (worker/decode_replay.py: decode_batch_bucket):
     a batch that shrinks 7 -> 6 -> 5 -> 4 -> 3 as sequences finish replays ONE captured graph (batch 8) and returns, step
     for step, the tokens AND the logits of exact-size eager launches, bit for bit (every decode kernel is row-independent
     and treats a length-0 sequence as a no-op); the finished sequences' blocks are freed and the KV of the survivors is
@@ -716,8 +716,8 @@ def test_decode_batch_buckets_replay_equals_exact_eager_launches(tmp_path, dtype
         runs[graph] = (out, logits)
         if graph:
             # one BATCH bucket (8) for the five batch sizes; the split geometry of these short, shrinking sequences adds its
-            # own key dimension (_graph_bucket)
-            assert {k[0] for k in model._decode_graphs} == {8} and model.graph_captures <= 2, list(model._decode_graphs)
+            # own key dimension (graph_bucket)
+            assert {k[0] for k in model.replay.graphs} == {8} and model.replay.captures <= 2, list(model.replay.graphs)
         del model
         torch.cuda.empty_cache()
     assert runs[True][0] == runs[False][0]

@@ -189,7 +189,7 @@ def test_eager_launches_give_the_bits_of_graph_replay(family, dtype):
     streams, logits = _generate(model, prompts)
     assert streams == base_streams
     assert torch.equal(logits, base_logits)
-    assert model.graph_captures == 0
+    assert model.replay.captures == 0
 
 
 def _serve(model, waves, output_len):

@@ -84,7 +84,7 @@ def moe(tmp_path_factory):
             assert model.moe_tap is None
             model.moe_tap = []
             streams, logits = _generate(model, prompts)
-            assert model.graph_captures == 0                 # a tapped step is never captured
+            assert model.replay.captures == 0                 # a tapped step is never captured
             cfg = model.model_config
             ids, ws = _tapped_ids(model.moe_tap, prompts, cfg.num_layers, cfg.num_experts_per_tok)
             model.moe_tap = None
@@ -148,12 +148,12 @@ def test_graph_replay_gives_the_bits_of_eager_launches(moe, dtype):
     path, _, prompts, base_streams, base_logits, _, _ = moe("qwen3_moe", dtype)
     replay = _load(path, dtype)                               # use_hip_graph is on by default; no tap: decode steps replay
     streams, logits = _generate(replay, prompts)
-    assert replay.graph_captures >= 1
+    assert replay.replay.captures >= 1
     assert streams == base_streams and torch.equal(logits, base_logits)     # ... the tapped (eager) base run included
     del replay
     eager = _load(path, dtype, use_hip_graph=False)
     streams, logits = _generate(eager, prompts)
-    assert eager.graph_captures == 0
+    assert eager.replay.captures == 0
     assert streams == base_streams and torch.equal(logits, base_logits)
 
 

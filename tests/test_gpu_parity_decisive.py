@@ -71,7 +71,7 @@ def test_greedy_ids_bit_exact_for_128_free_running_steps_on_the_decisive_checkpo
     # BASELINE configs[1]: the same first request as a batch of ONE (the tiny-batch decode path in bfloat16: the projections
     # sum the previous projection's slabs themselves, csrc/gemm_tiny.hip), free-running
     solo_toks, _, _ = P.generate(model, prompts[:1], GEN, logits_steps=[])
-    graphs = len(getattr(model, "_decode_graphs", {}) or {})
+    graphs = len(model.replay.graphs)
     del model
     torch.cuda.empty_cache()
     assert blk_lo >= P.HIGH_BLOCK, (blk_lo, blk_hi)

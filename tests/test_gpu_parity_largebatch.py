@@ -113,7 +113,7 @@ def test_large_batch_decode_at_llama3_8b_width(tmp_path, batch):
             feed = want_toks[s]
     finally:
         _hip.call = orig_call
-    assert model.graph_captures >= 1 and "swl_paged_attn_decode_qkv_rs" not in calls   # (> 32 sequences: exact norm)
+    assert model.replay.captures >= 1 and "swl_paged_attn_decode_qkv_rs" not in calls   # (> 32 sequences: exact norm)
     assert "swl_paged_attn_decode_qkv" in calls, sorted(set(calls))     # slab-fed attention serves up to 256 sequences
     assert any(c.startswith("swl_gemm_packed_wide") for c in calls), sorted(set(calls))
     del model

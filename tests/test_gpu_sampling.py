@@ -209,7 +209,7 @@ def test_model_seeded_stream_is_the_same_everywhere(tmp_path):
     assert _stream(graph, prompt, sp, vocab=v) == want
     assert _stream(graph, prompt, sp, others=23, vocab=v) == want
     assert _stream(graph, prompt, sp, others=23, swap_at=9, vocab=v) == want
-    graph._decode_lookahead = False
+    graph.replay.lookahead = False
     assert _stream(graph, prompt, sp, others=7, vocab=v) == want
 
 

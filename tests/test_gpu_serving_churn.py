@@ -7,7 +7,7 @@ in advance whatever the schedule does. Per case:
   * streams: every request with an expectation has error None and exactly its expected stream (the stop-token request
     holds one position — where its second stop token is banned — to "not that token"; every other position is exact);
   * coverage: the conditions C2 of tests/test_serving_churn_host.py hold for the trace of the REAL run, and with graph
-    replay on also: a look-ahead hit, a prepared look-ahead dropped, a capture after _drop_decode_graphs();
+    replay on also: a look-ahead hit, a prepared look-ahead dropped, a capture after replay.drop_graphs();
   * KV audit: when a request finishes, and before its blocks go, K and V of every (layer, position, kv-head) of its
     prompt + outputs[:-1] are read through the allocator's host mirror and compared with the pools of the CPU oracle after
     ONE whole-prompt forward of the same tokens: max|d| <= TAU * max|row|, TAU = 1/8. A stale, misplaced or unwritten
@@ -147,10 +147,10 @@ def _serve_and_hold(model, dtype, sc, tag, audit=True):
         if audit and sc.requests[index].exact:
             worst[0] = max(worst[0], _audit(model, dtype, req, sid))
             worst[1] += 1
-    captures = model.graph_captures
+    captures = model.replay.captures
     eng, reqs, rec = _churn.serve(model, model.engine_config, sc, before_free=before_free)
     c = _churn.coverage(rec.events, sc.requests)
-    print(f"\n[churn {tag}] {_show(c)}; graph keys {len(c['graph_keys'])}, captures {model.graph_captures - captures}; "
+    print(f"\n[churn {tag}] {_show(c)}; graph keys {len(c['graph_keys'])}, captures {model.replay.captures - captures}; "
           f"drafts accepted {eng.num_accepted_tokens} / {eng.num_draft_tokens}; "
           f"KV audit: worst ratio {worst[0]:.5f} over {worst[1]} sequences (TAU {TAU})")
     _churn.assert_streams(sc, reqs)

@@ -357,7 +357,7 @@ def test_graph_bucket_keeps_splits_balanced_and_few():
     quantised width must stay within a few percent of the planner's (balanced splits: the longest one sets the kernel
     time), cover the longest sequence with the captured split count, and take few distinct values per octave."""
     import types
-    from swiftllm_amd.worker.model import LlamaModel
+    from swiftllm_amd.worker.decode_replay import graph_bucket
     from swiftllm_amd.worker.batch_plan import select_seq_block_size
     widths = set()
     for batch, kvh, n0 in ((4, 32, 16372), (32, 8, 1024), (1, 8, 1024), (8, 8, 40000), (2, 32, 131000)):
@@ -365,7 +365,7 @@ def test_graph_bucket_keeps_splits_balanced_and_few():
             lens = [n0 + step] * batch
             sbs = select_seq_block_size(lens, kvh, 256)
             plan = types.SimpleNamespace(seq_block_size=sbs, num_seq_blocks=-(-max(lens) // sbs), max_decoding_len=max(lens))
-            q, cap = LlamaModel._graph_bucket(None, plan)
+            q, cap = graph_bucket(plan)
             widths.add((batch, kvh, n0, q, cap))
             assert cap * q >= max(lens) + 1
             if plan.num_seq_blocks > 1:
@@ -376,18 +376,14 @@ def test_graph_bucket_keeps_splits_balanced_and_few():
 
 
 def test_decode_batch_buckets_and_inert_rows():
-    """hipGraph replay keys on the batch rounded up to a bucket (worker/model.py: _decode_batch_bucket) and fills the
+    """hipGraph replay keys on the batch rounded up to a bucket (worker/decode_replay.py: decode_batch_bucket) and fills the
     surplus rows with inert sequences: few distinct buckets over 1..256 (14 since r06b), never smaller than the batch, at
     most 7 / 15 / 31 rows of padding up to 32 / 64 / 256 sequences, thresholds of the launch paths (2 / 32 / 64 / 256) are bucket boundaries; the padded plan has the layout
     of an exact plan of the bucket size (a captured graph finds its metadata at fixed addresses), length 0 / position -1
     / token 0 in the inert rows, and the planner's split width does not see them."""
-    import types
-    from swiftllm_amd.worker.model import LlamaModel
+    from swiftllm_amd.worker.decode_replay import decode_batch_bucket, plan_decode
     from swiftllm_amd.worker.batch_plan import plan_batch
-    m = LlamaModel.__new__(LlamaModel)
-    m.model_config = types.SimpleNamespace(num_kv_heads=8)
-    m._num_slots = 256
-    buckets = {b: m._decode_batch_bucket(b) for b in range(1, 257)}
+    buckets = {b: decode_batch_bucket(b) for b in range(1, 257)}
     assert all(v >= b and v - b <= (7 if b <= 32 else 15 if b <= 64 else 31) for b, v in buckets.items())
     assert buckets[1] == 1 and buckets[2] == 2 and buckets[3] == 8 and buckets[32] == 32 and buckets[33] == 48
     assert buckets[64] == 64 and buckets[65] == 96 and buckets[129] == 160 and buckets[250] == 256 and buckets[256] == 256
@@ -395,13 +391,13 @@ def test_decode_batch_buckets_and_inert_rows():
     for limit in (32, 64, 128, 256):     # a batch on one side of a launch-path threshold is never padded across it
         assert all(v <= limit for b, v in buckets.items() if b <= limit)
     lens = [1100, 37, 5]
-    plan = m._plan_decode([7, 3, 9], lens, [[11], [12], [13]], True)
+    plan = plan_decode([7, 3, 9], lens, [[11], [12], [13]], True, 8, 256)
     exact = plan_batch([[0]] * 8, [0] * 8, [1] * 8, 8, 256)
     assert plan.batch_size == 8 and plan.real_seqs == 3 and plan.packed_layout() == exact.packed_layout()
     assert plan.input_ids.tolist() == [11, 12, 13, 0, 0, 0, 0, 0]
     assert plan.decoding_seq_lens.tolist() == lens + [0] * 5 and plan.position_indices.tolist() == [1099, 36, 4] + [-1] * 5
     assert plan.seq_ids.tolist()[:3] == [7, 3, 9] and plan.seq_lengths_list[:3] == lens
-    unpadded = m._plan_decode([7, 3, 9], lens, [[11], [12], [13]], False)
+    unpadded = plan_decode([7, 3, 9], lens, [[11], [12], [13]], False, 8, 256)
     assert unpadded.batch_size == 3 and unpadded.real_seqs == 3
     assert (plan.seq_block_size, plan.num_seq_blocks, plan.max_decoding_len) == \
         (unpadded.seq_block_size, unpadded.num_seq_blocks, unpadded.max_decoding_len)
@@ -542,23 +538,22 @@ def test_engine_config_tuning_switches():
 
 
 def test_decode_lookahead_is_taken_only_by_the_exact_continuation():
-    """LlamaModel._take_lookahead (host logic only): the step prepared behind the running graph is used by the call that
+    """DecodeReplay.take (host logic only): the step prepared behind the running graph is used by the call that
     continues the same sequences with every length + 1 and exactly the tokens returned — and dropped by anything else
     (other tokens, other lengths, other sequences, a profile run, hipGraph off, look-ahead off, tokens not yet known)."""
     import types
-    from swiftllm_amd.worker.model import LlamaModel, _DecodeLookahead
+    from swiftllm_amd.worker.decode_replay import DecodeReplay, _DecodeLookahead
 
     def fresh(tokens=(7, 8, 9)):
-        m = LlamaModel.__new__(LlamaModel)
-        m.engine_config = types.SimpleNamespace(use_hip_graph=True)
-        m._decode_lookahead = True
+        m = DecodeReplay("no eager step", "no planner", "no staged buffer", types.SimpleNamespace(use_hip_graph=True))
+        assert m.lookahead is True and m.prepared is None
         la = _DecodeLookahead()
         la.seq_ids, la.lens, la.tokens, la.plan, la.dev = [4, 0, 2], [11, 21, 31], list(tokens) if tokens else None, "plan", "dev"
-        m._lookahead = la
+        m.prepared = la
         return m, la
     ids = [[7], [8], [9]]
     m, la = fresh()
-    assert m._take_lookahead(ids, [4, 0, 2], [11, 21, 31], False) is la and m._lookahead is None
+    assert m.take(ids, [4, 0, 2], [11, 21, 31], False) is la and m.prepared is None
     for args in (([[7], [8], [1]], [4, 0, 2], [11, 21, 31], False),        # another token
                  (ids, [4, 0, 2], [11, 21, 32], False),                    # another length
                  (ids, [4, 2, 0], [11, 21, 31], False),                    # other sequences / order
@@ -566,15 +561,15 @@ def test_decode_lookahead_is_taken_only_by_the_exact_continuation():
                  ([[7], [8], [9, 9]], [4, 0, 2], [11, 21, 31], False),     # not one token each
                  (ids, [4, 0, 2], [11, 21, 31], True)):                    # a profile run (ignore_kvcache)
         m, _ = fresh()
-        assert m._take_lookahead(*args) is None and m._lookahead is None, args
+        assert m.take(*args) is None and m.prepared is None, args
     m, _ = fresh()
     m.engine_config.use_hip_graph = False
-    assert m._take_lookahead(ids, [4, 0, 2], [11, 21, 31], False) is None
+    assert m.take(ids, [4, 0, 2], [11, 21, 31], False) is None
     m, _ = fresh()
-    m._decode_lookahead = False
-    assert m._take_lookahead(ids, [4, 0, 2], [11, 21, 31], False) is None
+    m.lookahead = False
+    assert m.take(ids, [4, 0, 2], [11, 21, 31], False) is None
     m, _ = fresh(tokens=None)
-    assert m._take_lookahead(ids, [4, 0, 2], [11, 21, 31], False) is None
+    assert m.take(ids, [4, 0, 2], [11, 21, 31], False) is None
 
 
 def test_blas_row_blocks_cover_every_row_once():
@@ -727,11 +722,11 @@ def test_wide_gemm_routing_is_the_measured_table():
     assert [_wide_wins(m, *o) for m in (96, 128, 160, 192, 200, 224, 256)] == [True, True, True, True, False, False, False]
     assert [_wide_silu_wins(m) for m in (96, 128, 129, 256)] == [True, True, False, False]
     # a threshold inside a replay bucket would route a batch differently in eager launches and in its padded graph
-    from swiftllm_amd.worker.model import LlamaModel
+    from swiftllm_amd.worker.decode_replay import decode_batch_bucket
     for shape in (qkv, o, up_gate, down, lm_head, (8192, 2048), (3072, 2048)):
         for m in range(65, 257):
-            assert _wide_wins(m, *shape) == _wide_wins(LlamaModel._decode_batch_bucket(None, m), *shape), (m, shape)
-            assert _wide_silu_wins(m) == _wide_silu_wins(LlamaModel._decode_batch_bucket(None, m)), m
+            assert _wide_wins(m, *shape) == _wide_wins(decode_batch_bucket(m), *shape), (m, shape)
+            assert _wide_silu_wins(m) == _wide_silu_wins(decode_batch_bucket(m)), m
 
 
 def test_bench_prefill_flops_and_full_depth_cpu_baseline():

@@ -47,7 +47,7 @@ def test_a_hit_resends_entries_and_mask_rows_only():
 
 
 def test_a_lookahead_built_without_arguments_is_a_plain_steps():
-    from swiftllm_amd.worker.model import _DecodeLookahead
+    from swiftllm_amd.worker.decode_replay import _DecodeLookahead
     la = _DecodeLookahead()
     assert la.logits is PLAIN and PLAIN.continues(la.logits)
     assert not StepLogits(scoring=[1]).continues(la.logits)
@@ -77,3 +77,50 @@ def test_staged_ints_grow_by_doubling_and_tell_their_owner():
         assert buf.back.numel() == buf.back_np.size == 200 * tail
         buf.resize(8)                                               # the owner's own rule (the edit buffer): exactly this
         assert buf.words == 8 and len(moves) == 4 and bool((buf.dev[:8] == idle).all())
+
+
+def test_the_staged_plan_moves_only_when_a_plan_outgrows_it(monkeypatch):
+    """decode_replay.stage_plan on CPU tensors (the copies' event is a recorder: there is no device to record on): a plan
+    within the capacity leaves the twin where it is, a larger one moves it and tells the owner exactly once, and the views
+    returned are the plan's packed layout over the twin, holding what the plan holds."""
+    from swiftllm_amd.worker.batch_plan import plan_batch
+    from swiftllm_amd.worker.decode_replay import plan_decode, stage_plan
+    waits = []
+
+    class Event:
+        def record(self):
+            waits.append("record")
+
+        def synchronize(self):
+            waits.append("wait")
+    monkeypatch.setattr(torch.cuda, "Event", Event)
+    moves = []
+    ints = StagedInts(lambda: moves.append(1), alloc=lambda words, pinned: torch.full((words,), 12345, dtype=torch.int32))
+
+    def check(plan, dev):
+        layout, total = plan.packed_layout()
+        assert list(dev) == [name for name, _, _ in layout] and sum(n for _, _, n in layout) <= total <= ints.words
+        for name, off, n in layout:
+            assert dev[name].numel() == n and (n == 0 or dev[name].data_ptr() == ints.dev.data_ptr() + 4 * off), name
+            assert dev[name].tolist() == ints.host[off:off + n].tolist(), name
+        for name in ("input_ids", "seq_ids", "decoding_seq_lens", "position_indices"):
+            assert dev[name].tolist() == getattr(plan, name).tolist(), name
+
+    small = plan_decode([7, 3, 9], [1100, 37, 5], [[11], [12], [13]], True, 8, 256)
+    total = small.packed_layout()[1]
+    check(small, stage_plan(ints, small, floor=total + 40))
+    assert moves == [1] and ints.words == total + 40 and waits == ["record"]      # the first capacity: the floor
+    assert bool((ints.dev[total:] == 0).all())       # (one copy of the plan's words: past them the fresh twin's zeros)
+    twin = ints.dev
+    check(small, stage_plan(ints, small, floor=total + 40))
+    other = plan_batch([[5, 6, 7], [8]], [2, 1], [9], 8, 256)      # a prompt and a decode: another layout, still within
+    assert other.packed_layout()[1] <= ints.words
+    check(other, stage_plan(ints, other))
+    assert moves == [1] and ints.dev is twin and waits == ["record"] + ["wait", "record"] * 2
+    big = plan_decode(list(range(40)), [50] * 40, None, True, 8, 256)
+    assert big.packed_layout()[1] > ints.words
+    check(big, stage_plan(ints, big, floor=total + 40))
+    assert moves == [1, 1] and ints.dev is not twin and ints.words >= big.packed_layout()[1]
+    twin = ints.dev
+    check(small, stage_plan(ints, small))           # a smaller plan afterwards: stays
+    assert moves == [1, 1] and ints.dev is twin

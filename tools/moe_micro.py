@@ -156,7 +156,7 @@ def step_section():
         out[f"qwen3_30b_a3b_b{batch}_step_ms"] = {"median": round(1000.0 * statistics.median(times), 3),
                                                   "min": round(1000.0 * min(times), 3),
                                                   "max": round(1000.0 * max(times), 3), "n": len(times)}
-    out["graph_captures"] = model.graph_captures
+    out["graph_captures"] = model.replay.captures
     return out
 
 

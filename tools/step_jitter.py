@@ -31,8 +31,8 @@ def main():
                           reserved_gb=round(torch.cuda.memory_reserved() / 1e9, 3),
                           allocated_gb=round(torch.cuda.memory_allocated() / 1e9, 3))), flush=True)
     for trial in range(a.trials):
-        model._drop_decode_graphs()
-        model._lookahead = None
+        model.replay.drop_graphs()
+        model.replay.drop_prepared()
         run = bench.DecodeRun(model, a.batch, cfg["vocab_size"], seed=3 + trial)
         run.jump_to(1088 - a.steps // 2 - 8)
         for _ in range(8):
@@ -62,7 +62,7 @@ def main():
                               alloc_retries=st1["num_alloc_retries"] - st0["num_alloc_retries"],
                               ooms=st1["num_ooms"] - st0["num_ooms"], free_gb=round(free1 / 1e9, 3),
                               reserved_gb=round(torch.cuda.memory_reserved() / 1e9, 3),
-                              graphs=len(model._decode_graphs))), flush=True)
+                              graphs=len(model.replay.graphs))), flush=True)
 
 
 if __name__ == "__main__":
