@@ -781,7 +781,18 @@ int swl_lora_expand(void *y, const float *t, const void *b_stack, const float *s
  *   swl_moe_down: y[p, :] = act[p] . expert_down[e]^T, expert_down [num_experts, hidden, inter]; y fp32
  *     [num_tokens * top_k, hidden], unrounded.
  *   swl_moe_combine: out[t, :] = T(sum_j topk_w[t, j] * y[t * top_k + j, :]), fp32, slot order, ONE rounding; no atomics.
- * The bits of out[t] depend on x[t], its experts and its weights only: not on num_tokens, the tiling or the other rows. */
+ * The bits of out[t] depend on x[t], its experts and its weights only: not on num_tokens, the tiling or the other rows.
+ *
+ * The row-tile form for prompt-sized steps (csrc/moe_wide.hip). swl_moe_up_gate_silu_wide and swl_moe_down_wide take the
+ * arguments of their twins plus row_tiles in {2, 4} (another positive value: SWL_ERR_UNSUPPORTED; <= 0:
+ * SWL_ERR_BAD_ARG), apply the same checks with the same codes, read the same tables of swl_moe_align and write the SAME BITS:
+ * a workgroup serves up to row_tiles consecutive tiles of one expert with one pass over a 32-column (up and gate) or
+ * 64-column (down) block of its weights, every element summed in the order of the 16-row kernels. Their grids are functions
+ * of (max_tiles, row_tiles, inter or hidden); num_tokens == 0 or max_tiles == 0: SWL_OK, nothing launched.
+ *   swl_moe_wide_row_tiles: which form a call of this step should take: 0 = the 16-row entries, else the row_tiles to pass.
+ *     Host arithmetic on its arguments only (graph capture and replay agree); 0 for an illegal step, for num_tokens <= 32
+ *     and wherever num_tokens * top_k / num_experts < 32 (fewer than two tiles per expert: no weight reuse to have); else 4
+ *     where hidden * inter >= 2^24, else 2. Passing row_tiles where it returns 0 is legal and slower. */
 #define SWL_MOE_LOGITS_F32 2
 int swl_moe_supported(int32_t hidden, int32_t inter, int32_t num_experts, int32_t top_k, int32_t dtype);
 int swl_moe_max_pairs(void);
@@ -799,6 +810,14 @@ int swl_moe_down(float *y, const void *act, const void *expert_down, const int32
                  int32_t dtype, swl_stream_t stream);
 int swl_moe_combine(void *out, const float *y, const float *topk_w, int32_t num_tokens, int32_t top_k, int32_t hidden,
                     int64_t out_row_stride, int32_t dtype, swl_stream_t stream);
+int swl_moe_wide_row_tiles(int32_t num_tokens, int32_t top_k, int32_t num_experts, int32_t hidden, int32_t inter);
+int swl_moe_up_gate_silu_wide(void *act, const void *x, const void *expert_up_gate, const int32_t *tile_rows,
+                              const int32_t *tile_experts, int32_t max_tiles, int32_t num_tokens, int32_t top_k,
+                              int32_t hidden, int32_t inter, int32_t num_experts, int64_t x_row_stride, int32_t row_tiles,
+                              int32_t dtype, swl_stream_t stream);
+int swl_moe_down_wide(float *y, const void *act, const void *expert_down, const int32_t *tile_rows,
+                      const int32_t *tile_experts, int32_t max_tiles, int32_t num_tokens, int32_t top_k, int32_t hidden,
+                      int32_t inter, int32_t num_experts, int32_t row_tiles, int32_t dtype, swl_stream_t stream);
 
 #ifdef __cplusplus
 }

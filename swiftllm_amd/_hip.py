@@ -166,6 +166,10 @@ _SPECIAL = {
     "swl_moe_up_gate_silu": ([_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _P], _I32),
     "swl_moe_down": ([_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P], _I32),
     "swl_moe_combine": ([_P, _P, _P, _I32, _I32, _I32, _I64, _I32, _P], _I32),
+    # ... and their row-tile form for prompt-sized steps (csrc/moe_wide.hip; tests/test_moe_wide_abi.py)
+    "swl_moe_wide_row_tiles": ([_I32, _I32, _I32, _I32, _I32], _I32),
+    "swl_moe_up_gate_silu_wide": ([_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
+    "swl_moe_down_wide": ([_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

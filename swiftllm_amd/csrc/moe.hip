@@ -27,17 +27,13 @@
 // A row's sums never see another row's data (a padding row is a row of zeros, rows are the M side of the MFMA) and the order
 // of its additions is fixed by (H, I, k) alone: the bits of out[t] are a function of x[t], its experts and its weights. No
 // split over K depends on T. Unused tiles leave before any barrier (uniform branch on tile_experts).
+//
+// Prompt-sized steps: moe_wide.hip holds a second form of the two expert GEMMs (several 16-row tiles of one expert per pass
+// over the weights) that gives the same bits; the limits and step checks both files use are in moe_common.h.
 #include "attn_mfma.h"
+#include "moe_common.h"
 
 namespace swl {
-
-constexpr int kMoeMaxExperts = 256;
-constexpr int kMoeMaxTopK = 16;
-constexpr int kMoeMaxPairs = 4096;
-constexpr int kMoeWaves = 8;
-constexpr int kMoeLogitsF32 = 2;
-
-inline int moe_tile_bound(int pairs, int experts) { return (pairs + 15) / 16 + (experts < pairs ? experts : pairs); }
 
 template <typename L>
 __device__ __forceinline__ float moe_logit(const L *p) { return to_f(*p); }
@@ -294,16 +290,6 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(T *__restrict__ out, c
         for (int j = 0; j < 4; ++j) v[j] = to_t<T>(a[j]), v[4 + j] = to_t<T>(b[j]);
         store8(out + t * out_row_stride + h, v);
     }
-}
-
-inline bool moe_dtype_ok(int dtype) { return dtype == SWL_F16 || dtype == SWL_BF16; }
-
-// SWL_OK when (T, k, E) is a legal step, else the error code
-inline int moe_step_check(int num_tokens, int top_k, int num_experts) {
-    if (num_tokens < 0 || top_k <= 0 || num_experts <= 0 || top_k > num_experts) return SWL_ERR_BAD_ARG;
-    if (num_experts > kMoeMaxExperts || top_k > kMoeMaxTopK) return SWL_ERR_UNSUPPORTED;
-    if (static_cast<int64_t>(num_tokens) * top_k > kMoeMaxPairs) return SWL_ERR_UNSUPPORTED;
-    return SWL_OK;
 }
 
 } // namespace swl

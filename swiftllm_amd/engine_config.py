@@ -81,6 +81,12 @@ class EngineConfig:
     max_loras: int = 0
     max_lora_rank: int = 16
     lora_modules: list = None
+    # Mixture-of-experts models (kernels/moe.py, csrc/moe_wide.hip): the form of the expert GEMMs. -1 (default): per token
+    # block, the 16-row kernels or the weight-reusing row-tile form, whichever swl_moe_wide_row_tiles names for the block's
+    # size; 0: always the 16-row kernels; 2 / 4: always the row-tile form with that many tiles a workgroup. The bits are the
+    # same in every setting; forcing 2 / 4 is for tests and measurements (with few rows per expert it is slower). Ignored for
+    # dense models.
+    moe_wide_tiles: int = -1
     # Guided decoding (swiftllm_amd/guided, csrc/guided.hip): rows of the device pool of per-state
     # token bitmasks, one row (ceil(vocab / 32) int32 words: 16 KiB at Llama-3's vocabulary) per DFA state of a resident
     # guide. 0 (default): off — no pool, no new code path, and a guided request is answered with an error. > 0: load_weights
@@ -136,6 +142,7 @@ class EngineConfig:
     SUPPORTED_BLOCK_SIZE = 16
     KV_CACHE_DTYPES = ("auto", "fp8_e4m3")
     LORA_RANKS = (8, 16, 32, 64)
+    MOE_WIDE_TILES = (-1, 0, 2, 4)
 
     def __post_init__(self):
         # The reference takes block_size as a Triton constexpr (paged_attn.py:27) and its CLI default is 16
@@ -157,6 +164,9 @@ class EngineConfig:
             raise ValueError(f"speculative_max_batch must be >= 0, got {self.speculative_max_batch}")
         if int(self.max_loras) < 0:
             raise ValueError(f"max_loras must be >= 0 (0 = off), got {self.max_loras}")
+        if int(self.moe_wide_tiles) not in self.MOE_WIDE_TILES:
+            raise ValueError(f"moe_wide_tiles must be one of {list(self.MOE_WIDE_TILES)} (-1 = choose per step, 0 = 16-row "
+                             f"kernels only), got {self.moe_wide_tiles}")
         if int(self.max_lora_rank) not in self.LORA_RANKS:
             raise ValueError(f"max_lora_rank must be one of {list(self.LORA_RANKS)}, got {self.max_lora_rank}")
         if self.lora_modules:

@@ -11,6 +11,11 @@ arguments; `moe_ffn` chains them behind the router GEMM. Nothing synchronises wi
 [pairs, I] 16-bit, y [pairs, H] fp32, the two tile tables) whatever the step; the buffers come from torch's caching
 allocator, so the profiling forward of `profile_num_blocks` sees them. There is no fallback: a shape the kernels do not take
 is an error.
+
+Prompt-sized steps: csrc/moe_wide.hip holds a second form of the two expert GEMMs in which a workgroup serves up to
+`row_tiles` (2 or 4) consecutive 16-row tiles of one expert with one pass over a block of its weights. It reads the same
+tile tables and writes the same bits, so `moe_ffn` picks the form per token block from `wide_row_tiles` (host arithmetic on
+(tokens, k, E, H, I): capture and replay agree) and a token's output does not depend on the choice. Still six launches.
 """
 import torch
 
@@ -21,6 +26,7 @@ TILE_ROWS = 16
 LOGITS_F32 = 2      # SWL_MOE_LOGITS_F32
 MAX_EXPERTS = 256
 MAX_TOP_K = 16
+WIDE_ROW_TILES = (2, 4)     # what swl_moe_*_wide take
 
 
 def supported(hidden: int, inter: int, num_experts: int, top_k: int, dtype: torch.dtype = torch.bfloat16) -> bool:
@@ -37,6 +43,12 @@ def max_pairs() -> int:
 def max_tiles(num_tokens: int, top_k: int, num_experts: int) -> int:
     """ceil(T k / 16) + min(E, T k): the tiles an alignment of the step can need."""
     return int(_hip.load().swl_moe_max_tiles(int(num_tokens), int(top_k), int(num_experts)))
+
+
+def wide_row_tiles(num_tokens: int, top_k: int, num_experts: int, hidden: int, inter: int) -> int:
+    """The form a call of this step should take: 0 = the 16-row kernels, else the `row_tiles` of the wide ones. 0 for
+    num_tokens <= 32 and wherever num_tokens * top_k / num_experts < 32."""
+    return int(_hip.load().swl_moe_wide_row_tiles(int(num_tokens), int(top_k), int(num_experts), int(hidden), int(inter)))
 
 
 def _logits_code(dtype: torch.dtype) -> int:
@@ -71,8 +83,9 @@ def moe_align(topk_ids: torch.Tensor, num_experts: int):
 
 
 def moe_up_gate_silu(x: torch.Tensor, expert_up_gate: torch.Tensor, tile_rows, tile_experts, top_k: int,
-                     act: torch.Tensor = None) -> torch.Tensor:
-    """x [T, H], expert_up_gate [E, 2 I, H] ([up ; gate] per expert) -> act [T k, I] = up * silu(gate) of every pair."""
+                     act: torch.Tensor = None, row_tiles: int = 0) -> torch.Tensor:
+    """x [T, H], expert_up_gate [E, 2 I, H] ([up ; gate] per expert) -> act [T k, I] = up * silu(gate) of every pair.
+    `row_tiles` > 0: the wide form (same bits)."""
     _hip.require_gpu_tensor(x, "x")
     e, two_i, h = expert_up_gate.shape
     assert x.dim() == 2 and x.shape[1] == h and x.stride(1) == 1 and x.dtype == expert_up_gate.dtype
@@ -82,15 +95,17 @@ def moe_up_gate_silu(x: torch.Tensor, expert_up_gate: torch.Tensor, tile_rows, t
         act = torch.empty((t * top_k, inter), dtype=x.dtype, device=x.device)
     assert act.is_contiguous() and tuple(act.shape) == (t * top_k, inter) and act.dtype == x.dtype
     assert tile_rows.numel() == tile_experts.numel() * TILE_ROWS
-    _hip.call("swl_moe_up_gate_silu", _hip.ptr(act), _hip.ptr(x), _hip.ptr(expert_up_gate), _hip.ptr(tile_rows),
-              _hip.ptr(tile_experts), tile_experts.numel(), t, int(top_k), h, inter, e, x.stride(0),
-              _hip.dtype_code(x.dtype), _hip.stream())
+    wide = (int(row_tiles),) if row_tiles > 0 else ()
+    _hip.call("swl_moe_up_gate_silu_wide" if wide else "swl_moe_up_gate_silu", _hip.ptr(act), _hip.ptr(x),
+              _hip.ptr(expert_up_gate), _hip.ptr(tile_rows), _hip.ptr(tile_experts), tile_experts.numel(), t, int(top_k), h,
+              inter, e, x.stride(0), *wide, _hip.dtype_code(x.dtype), _hip.stream())
     return act
 
 
 def moe_down(act: torch.Tensor, expert_down: torch.Tensor, tile_rows, tile_experts, top_k: int,
-             y: torch.Tensor = None) -> torch.Tensor:
-    """act [T k, I], expert_down [E, H, I] -> y fp32 [T k, H]: every pair's down projection, unrounded."""
+             y: torch.Tensor = None, row_tiles: int = 0) -> torch.Tensor:
+    """act [T k, I], expert_down [E, H, I] -> y fp32 [T k, H]: every pair's down projection, unrounded. `row_tiles` > 0:
+    the wide form (same bits)."""
     _hip.require_gpu_tensor(act, "act")
     e, h, inter = expert_down.shape
     assert act.dim() == 2 and act.shape[1] == inter and act.is_contiguous() and act.dtype == expert_down.dtype
@@ -100,8 +115,10 @@ def moe_down(act: torch.Tensor, expert_down: torch.Tensor, tile_rows, tile_exper
         y = torch.empty((pairs, h), dtype=torch.float32, device=act.device)
     assert y.is_contiguous() and tuple(y.shape) == (pairs, h) and y.dtype == torch.float32
     assert tile_rows.numel() == tile_experts.numel() * TILE_ROWS
-    _hip.call("swl_moe_down", _hip.ptr(y), _hip.ptr(act), _hip.ptr(expert_down), _hip.ptr(tile_rows), _hip.ptr(tile_experts),
-              tile_experts.numel(), pairs // top_k, int(top_k), h, inter, e, _hip.dtype_code(act.dtype), _hip.stream())
+    wide = (int(row_tiles),) if row_tiles > 0 else ()
+    _hip.call("swl_moe_down_wide" if wide else "swl_moe_down", _hip.ptr(y), _hip.ptr(act), _hip.ptr(expert_down),
+              _hip.ptr(tile_rows), _hip.ptr(tile_experts), tile_experts.numel(), pairs // top_k, int(top_k), h, inter, e,
+              *wide, _hip.dtype_code(act.dtype), _hip.stream())
     return y
 
 
@@ -119,11 +136,16 @@ def moe_combine(y: torch.Tensor, topk_w: torch.Tensor, out: torch.Tensor) -> tor
 
 
 def moe_ffn(x: torch.Tensor, router: torch.Tensor, expert_up_gate: torch.Tensor, expert_down: torch.Tensor, top_k: int,
-            norm_topk_prob: bool, skinny: bool = False, tap=None, layer_id: int = 0) -> torch.Tensor:
+            norm_topk_prob: bool, skinny: bool = False, tap=None, layer_id: int = 0, wide_tiles: int = -1) -> torch.Tensor:
     """The FFN of a mixture-of-experts layer on the normalised activations x [T, H]: a new [T, H] tensor. `tap` (tests): a
-    list that receives (layer_id, topk_ids.cpu(), topk_w.cpu()) — a host copy, so a tapped step is never graph-captured."""
+    list that receives (layer_id, topk_ids.cpu(), topk_w.cpu()) — a host copy, so a tapped step is never graph-captured.
+    `wide_tiles`: -1 = `wide_row_tiles` decides the form of the expert GEMMs per token block, 0 = always the 16-row
+    kernels, 2 / 4 = always the wide ones with that many row tiles (the bits are the same either way)."""
+    if wide_tiles not in (-1, 0) + WIDE_ROW_TILES:
+        raise ValueError(f"wide_tiles must be -1 (choose), 0 (16-row) or one of {list(WIDE_ROW_TILES)}, got {wide_tiles}")
     t = x.shape[0]
     e = router.shape[0]
+    h, inter = expert_down.shape[1], expert_down.shape[2]
     out = torch.empty_like(x)
     if t == 0:
         return out
@@ -138,8 +160,9 @@ def moe_ffn(x: torch.Tensor, router: torch.Tensor, expert_up_gate: torch.Tensor,
         rows, experts = moe_align(ids, e)
         if act is None or act.shape[0] != n * top_k:        # (a step's blocks share one workspace; the last may be shorter)
             act = y = None
-        act = moe_up_gate_silu(xs, expert_up_gate, rows, experts, top_k, act)
-        y = moe_down(act, expert_down, rows, experts, top_k, y)
+        form = wide_row_tiles(n, top_k, e, h, inter) if wide_tiles < 0 else wide_tiles
+        act = moe_up_gate_silu(xs, expert_up_gate, rows, experts, top_k, act, form)
+        y = moe_down(act, expert_down, rows, experts, top_k, y, form)
         moe_combine(y, w, out[t0:t0 + n])
         if tap is not None:
             tapped.append((ids, w))

@@ -2,6 +2,7 @@
 Nothing here is asserted anywhere.
 
     python tools/moe_micro.py [--iters 200] [--repeats 5] [--sections ffn:qwen3_30b_a3b,ffn:mixtral_8x7b,step] [--out FILE]
+    python tools/moe_micro.py --sections wide:qwen3_30b_a3b,wide:mixtral_8x7b --out profiles/moe_wide_micro.json
 
 Run without --child it starts one fresh child process per section, each under its own `timeout -k 10`, and stops at the
 first that fails (nothing more is started on the GPU after a fault or a time limit); the children's JSON is merged into one
@@ -15,6 +16,10 @@ ffn:<geometry>  One layer's FFN with dummy weights U(-1e-3, 1e-3) — the router
     whole FFN. Yardstick in the same run: the loop HF's eager experts module runs, with torch on the GPU — router
     F.linear, softmax, top-k, the host synchronisation that finds the experts hit, then per active expert index_select ->
     F.linear x 3 (up, gate, down) -> index_add. `ours_over_loop` < 1 means ours is faster.
+wide:<geometry>  The two forms of the expert GEMMs side by side (same weights and inputs as ffn:) at T = 64, 128, 256, 512,
+    1024, 2048 (one call where T k <= 4096) and 4096 (token blocks): us of up_gate_silu, down (one-call steps) and the whole
+    FFN with the form forced to the 16-row kernels (`rt0`) and to each row_tiles the wide kernels take (`rt2`, `rt4`), what
+    the chooser picks (`chosen`), and the torch loop in the same run. The forms' outputs are compared bit for bit first.
 step  A whole decode step at Qwen3-30B-A3B dimensions (48 layers, dummy weights, bfloat16, 1024-token contexts) at batch
     1 / 8 / 32: host wall time per forward() on graph replay.
 Each kernel figure is the median of `--repeats` runs of `--iters` back-to-back launches between two device events (a tenth
@@ -41,7 +46,7 @@ QWEN3_30B_A3B = dict(model_type="qwen3_moe", hidden_act="silu", hidden_size=2048
                      head_dim=128, num_experts=128, num_experts_per_tok=8, norm_topk_prob=True, decoder_sparse_step=1,
                      mlp_only_layers=[], vocab_size=151936, max_position_embeddings=40960, rms_norm_eps=1e-6,
                      rope_theta=1000000.0, tie_word_embeddings=False)
-SECTION_TIMEOUT_S = {"ffn": 300, "step": 420}
+SECTION_TIMEOUT_S = {"ffn": 300, "wide": 420, "step": 420}
 
 
 def _timed(fn, iters, repeats):
@@ -124,6 +129,41 @@ def ffn_section(name, iters, repeats):
     return out
 
 
+def wide_section(name, iters, repeats):
+    from swiftllm_amd.worker.kernels import moe as M
+    from swiftllm_amd.worker.kernels.linear import linear
+    H, I, E, k = GEOMETRIES[name]
+    dt, dev = torch.bfloat16, "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    u = lambda *shape: torch.empty(shape, dtype=dt, device=dev).uniform_(-1e-3, 1e-3, generator=g)     # noqa: E731
+    router, up_gate, down = u(E, H), u(E, 2 * I, H), u(E, H, I)
+    out = {}
+    for T in (64, 128, 256, 512, 1024, 2048, 4096):
+        n = max(2, iters // (1 if T < 256 else 10 if T < 2048 else 40))
+        x = torch.randn((T, H), device=dev, generator=g).to(dt)
+        res = {"chosen": [M.wide_row_tiles(min(T - t0, M.max_pairs() // k), k, E, H, I)
+                          for t0 in range(0, T, M.max_pairs() // k)]}
+        base = M.moe_ffn(x, router, up_gate, down, k, True, wide_tiles=0)
+        one_call = T * k <= M.max_pairs()
+        if one_call:
+            ids, _ = M.moe_route(linear(x, router, False), k, True)
+            rows, experts = M.moe_align(ids, E)
+        for rt in (0,) + M.WIDE_ROW_TILES:
+            assert torch.equal(M.moe_ffn(x, router, up_gate, down, k, True, wide_tiles=rt).view(torch.int16),
+                               base.view(torch.int16)), (T, rt)
+            form = {"ffn": _summary(_timed(lambda: M.moe_ffn(x, router, up_gate, down, k, True, wide_tiles=rt), n, repeats))}
+            if one_call:
+                act = M.moe_up_gate_silu(x, up_gate, rows, experts, k, row_tiles=rt)
+                y = M.moe_down(act, down, rows, experts, k, row_tiles=rt)
+                form["up_gate_silu"] = _summary(_timed(
+                    lambda: M.moe_up_gate_silu(x, up_gate, rows, experts, k, act, rt), n, repeats))
+                form["down"] = _summary(_timed(lambda: M.moe_down(act, down, rows, experts, k, y, rt), n, repeats))
+            res[f"rt{rt}"] = form
+        res["hf_loop"] = _summary(_timed(lambda: hf_loop(x, router, up_gate, down, k, I), max(2, n // 4), repeats))
+        out[f"wide_{name}_t{T}"] = res
+    return out
+
+
 def step_section():
     from swiftllm_amd import EngineConfig, LlamaModel
     S, steps, out = 1024, 32, {}
@@ -171,7 +211,8 @@ def main():
     if a.child:
         assert torch.cuda.is_available(), "needs a HIP device"
         kind, _, name = a.child.partition(":")
-        res = ffn_section(name, a.iters, a.repeats) if kind == "ffn" else step_section()
+        res = (ffn_section(name, a.iters, a.repeats) if kind == "ffn" else
+               wide_section(name, a.iters, a.repeats) if kind == "wide" else step_section())
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     merged = {"iters": a.iters, "repeats": a.repeats}
