@@ -819,6 +819,39 @@ int swl_moe_down_wide(float *y, const void *act, const void *expert_down, const 
                       const int32_t *tile_experts, int32_t max_tiles, int32_t num_tokens, int32_t top_k, int32_t hidden,
                       int32_t inter, int32_t num_experts, int32_t row_tiles, int32_t dtype, swl_stream_t stream);
 
+/* ---- FP8 (e4m3) expert weights (csrc/moe_fp8.hip, csrc/moe_fp8_wide.hip; the storage contract: csrc/moe_fp8.h) -----------
+ * expert_up_gate / expert_down hold one OCP e4m3fn code per element in the row-major order of the 16-bit stacks, with one
+ * fp32 scale per OUTPUT ROW (up_gate_scale [num_experts, 2 * inter], down_scale [num_experts, hidden]); a weight means
+ * fp(code) * scale[row]. Activations, act, y and dtype are those of the 16-bit entries.
+ *   swl_moe_fp8_supported: swl_moe_supported with hidden % 64 == 0 and inter % 64 == 0 (a k step is 64 codes). Host only.
+ *   swl_moe_quantise_rows: codes[r, :] = RNE_e4m3(clamp(fp32(rows[r, :]) * inv[r], -448, 448)) for num_rows contiguous rows
+ *     of row_len elements of dtype (row_len % 16 == 0, else SWL_ERR_UNSUPPORTED; rows and codes 16-byte aligned); inv is
+ *     fp32(1 / scale), computed by the caller. num_rows == 0: SWL_OK, nothing launched.
+ *   swl_moe_up_gate_silu_fp8, swl_moe_down_fp8: the 16-bit twins' arguments plus the scales behind the weights, the same
+ *     checks with the same codes, the same tables and the same grids. The codes are dequantised in registers (exact), the
+ *     products accumulate in fp32 and the finished sum is multiplied ONCE by scale[row]: before the rounding to T for up and
+ *     gate, as the last fp32 operation for y. A row's bits depend on that row's activations, experts and weights only.
+ *   swl_moe_up_gate_silu_fp8_wide, swl_moe_down_fp8_wide: their row-tile form (row_tiles in {2, 4}, as the 16-bit wide
+ *     entries take it; swl_moe_wide_row_tiles chooses): the SAME BITS as the two entries above. */
+int swl_moe_fp8_supported(int32_t hidden, int32_t inter, int32_t num_experts, int32_t top_k, int32_t dtype);
+int swl_moe_quantise_rows(void *codes, const void *rows, const float *inv, int64_t num_rows, int32_t row_len, int32_t dtype,
+                          swl_stream_t stream);
+int swl_moe_up_gate_silu_fp8(void *act, const void *x, const void *expert_up_gate, const float *up_gate_scale,
+                             const int32_t *tile_rows, const int32_t *tile_experts, int32_t max_tiles, int32_t num_tokens,
+                             int32_t top_k, int32_t hidden, int32_t inter, int32_t num_experts, int64_t x_row_stride,
+                             int32_t dtype, swl_stream_t stream);
+int swl_moe_down_fp8(float *y, const void *act, const void *expert_down, const float *down_scale, const int32_t *tile_rows,
+                     const int32_t *tile_experts, int32_t max_tiles, int32_t num_tokens, int32_t top_k, int32_t hidden,
+                     int32_t inter, int32_t num_experts, int32_t dtype, swl_stream_t stream);
+int swl_moe_up_gate_silu_fp8_wide(void *act, const void *x, const void *expert_up_gate, const float *up_gate_scale,
+                                  const int32_t *tile_rows, const int32_t *tile_experts, int32_t max_tiles,
+                                  int32_t num_tokens, int32_t top_k, int32_t hidden, int32_t inter, int32_t num_experts,
+                                  int64_t x_row_stride, int32_t row_tiles, int32_t dtype, swl_stream_t stream);
+int swl_moe_down_fp8_wide(float *y, const void *act, const void *expert_down, const float *down_scale,
+                          const int32_t *tile_rows, const int32_t *tile_experts, int32_t max_tiles, int32_t num_tokens,
+                          int32_t top_k, int32_t hidden, int32_t inter, int32_t num_experts, int32_t row_tiles, int32_t dtype,
+                          swl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

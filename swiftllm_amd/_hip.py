@@ -170,6 +170,15 @@ _SPECIAL = {
     "swl_moe_wide_row_tiles": ([_I32, _I32, _I32, _I32, _I32], _I32),
     "swl_moe_up_gate_silu_wide": ([_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
     "swl_moe_down_wide": ([_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P], _I32),
+    # ... and on FP8 (e4m3) expert weights: the loader's row quantiser and both forms of the two GEMMs, each with the fp32
+    # per-row scales behind the codes (csrc/moe_fp8.hip, csrc/moe_fp8_wide.hip; tests/test_moe_fp8_host.py)
+    "swl_moe_fp8_supported": ([_I32, _I32, _I32, _I32, _I32], _I32),
+    "swl_moe_quantise_rows": ([_P, _P, _P, _I64, _I32, _I32, _P], _I32),
+    "swl_moe_up_gate_silu_fp8": ([_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _P], _I32),
+    "swl_moe_down_fp8": ([_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P], _I32),
+    "swl_moe_up_gate_silu_fp8_wide": ([_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P],
+                                      _I32),
+    "swl_moe_down_fp8_wide": ([_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

@@ -40,15 +40,21 @@ SOURCES = [
     "lora.hip",
     "moe.hip",
     "moe_wide.hip",
+    "moe_fp8.hip",
+    "moe_fp8_wide.hip",
     "decode_engine.hip",
 ]
-HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "decode_attn.h", "prefill_tile.h", "fp8_kv.h", "kv_store.h", "gemm_host.h", "moe_common.h", "logits_keys.h", "logits_bits.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
+HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "decode_attn.h", "prefill_tile.h", "fp8_kv.h", "kv_store.h", "gemm_host.h", "moe_common.h", "moe_fp8.h", "logits_keys.h", "logits_bits.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
 LIB = os.path.join(HERE, "libswiftllm_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 ARCH = "gfx950"
 # -ffp-contract=off: the reference's rounding points (fp16 mul, then fp16 add) must not be fused.
 CXXFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
             "-Wno-unused-function"]
+# Per-source additions. The FP8 expert units are built without packed (two-wide) fp32 VALU instructions: their scale
+# multiplies and epilogues are single fp32 operations by contract.
+SOURCE_FLAGS = {src: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+                for src in ("moe_fp8.hip", "moe_fp8_wide.hip")}
 
 
 def _hipcc() -> str:
@@ -87,11 +93,11 @@ def _build(hipcc, OBJ_DIR, LIB, extra, force, jobs, verbose, swap) -> str:
         obj = os.path.join(OBJ_DIR, src.replace(".hip", ".o"))
         objs.append(obj)
         if force or not _newer(obj, [src_path] + hdrs):
-            todo.append((src_path, obj))
+            todo.append((src_path, obj, SOURCE_FLAGS.get(src, [])))
 
     def compile_one(item):
-        src_path, obj = item
-        cmd = [hipcc, *CXXFLAGS, *extra, f"-I{HERE}", "-c", src_path, "-o", obj]
+        src_path, obj, src_flags = item
+        cmd = [hipcc, *CXXFLAGS, *src_flags, *extra, f"-I{HERE}", "-c", src_path, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src_path}:\n{r.stderr}")

@@ -87,6 +87,12 @@ class EngineConfig:
     # same in every setting; forcing 2 / 4 is for tests and measurements (with few rows per expert it is slower). Ignored for
     # dense models.
     moe_wide_tiles: int = -1
+    # Element type of a mixture-of-experts model's two expert stacks. "auto": the activation dtype — every step launches what
+    # it always did. "fp8_e4m3": OCP e4m3fn codes with one fp32 scale per output row, quantised from the 16-bit checkpoint at
+    # load (csrc/moe_fp8.h); the expert GEMMs dequantise in registers (csrc/moe_fp8.hip, csrc/moe_fp8_wide.hip), so the
+    # stacks take half the HBM and a step streams half the expert bytes. The router, attention and lm_head stay 16-bit.
+    # Refused at load for a dense model.
+    moe_weight_dtype: str = "auto"
     # Guided decoding (swiftllm_amd/guided, csrc/guided.hip): rows of the device pool of per-state
     # token bitmasks, one row (ceil(vocab / 32) int32 words: 16 KiB at Llama-3's vocabulary) per DFA state of a resident
     # guide. 0 (default): off — no pool, no new code path, and a guided request is answered with an error. > 0: load_weights
@@ -143,6 +149,7 @@ class EngineConfig:
     KV_CACHE_DTYPES = ("auto", "fp8_e4m3")
     LORA_RANKS = (8, 16, 32, 64)
     MOE_WIDE_TILES = (-1, 0, 2, 4)
+    MOE_WEIGHT_DTYPES = ("auto", "fp8_e4m3")
 
     def __post_init__(self):
         # The reference takes block_size as a Triton constexpr (paged_attn.py:27) and its CLI default is 16
@@ -167,6 +174,8 @@ class EngineConfig:
         if int(self.moe_wide_tiles) not in self.MOE_WIDE_TILES:
             raise ValueError(f"moe_wide_tiles must be one of {list(self.MOE_WIDE_TILES)} (-1 = choose per step, 0 = 16-row "
                              f"kernels only), got {self.moe_wide_tiles}")
+        if self.moe_weight_dtype not in self.MOE_WEIGHT_DTYPES:
+            raise ValueError(f"moe_weight_dtype must be one of {list(self.MOE_WEIGHT_DTYPES)}, got {self.moe_weight_dtype!r}")
         if int(self.max_lora_rank) not in self.LORA_RANKS:
             raise ValueError(f"max_lora_rank must be one of {list(self.LORA_RANKS)}, got {self.max_lora_rank}")
         if self.lora_modules:
@@ -242,6 +251,9 @@ class EngineConfig:
         g.add_argument("--no-skinny-gemm", dest="use_skinny_gemm", action="store_false")
         g.add_argument("--kv-cache-dtype", type=str, default="auto", choices=list(EngineConfig.KV_CACHE_DTYPES),
                        help="Element type of the KV pools: auto = the activation dtype, fp8_e4m3 = 1 byte per element")
+        g.add_argument("--moe-weight-dtype", type=str, default="auto", choices=list(EngineConfig.MOE_WEIGHT_DTYPES),
+                       help="Element type of a mixture-of-experts model's expert stacks: auto = the activation dtype, "
+                            "fp8_e4m3 = 1 byte per element + one fp32 scale per output row, quantised at load")
         g.add_argument("--speculative-ngram", type=int, default=0,
                        help="Prompt-lookup speculative decoding: n-gram drafts per sequence per step (0 = off)")
         g.add_argument("--speculative-max-batch", type=int, default=8,

@@ -89,6 +89,11 @@ def spawn_replicas(num: int, base_port: int, passthrough: List[str]) -> List[sub
     return procs
 
 
+def moe_passthrough(moe_weight_dtype) -> List[str]:
+    """The replicas' flag for the router's --moe-weight-dtype (None: not given, nothing passed on)."""
+    return [] if moe_weight_dtype is None else ["--moe-weight-dtype", moe_weight_dtype]
+
+
 def lora_passthrough(max_loras, max_lora_rank, loras) -> List[str]:
     """The replicas' flags for the router's LoRA options; refuses what every replica would refuse, before any is spawned."""
     if loras and not max_loras:
@@ -137,6 +142,8 @@ def main():
     # checked here, before eight replicas load their weights, and handed on to every one of them
     ap.add_argument("--kv-cache-dtype", default=None, choices=["auto", "fp8_e4m3"],
                     help="element type of every replica's KV pools (api_server --kv-cache-dtype)")
+    ap.add_argument("--moe-weight-dtype", default=None, choices=["auto", "fp8_e4m3"],
+                    help="element type of every replica's expert stacks (api_server --moe-weight-dtype)")
     # multi-LoRA serving: every replica loads the same adapters (a request's "lora" field is relayed like every field)
     ap.add_argument("--max-loras", type=int, default=None, help="adapter slots of every replica (api_server --max-loras)")
     ap.add_argument("--max-lora-rank", type=int, default=None, choices=[8, 16, 32, 64])
@@ -153,6 +160,7 @@ def main():
         passthrough = list(passthrough) + ["--guided-max-states", str(args.guided_max_states)]
     if args.kv_cache_dtype is not None:
         passthrough = list(passthrough) + ["--kv-cache-dtype", args.kv_cache_dtype]
+    passthrough = list(passthrough) + moe_passthrough(args.moe_weight_dtype)
     passthrough = list(passthrough) + lora_passthrough(args.max_loras, args.max_lora_rank, args.lora)
     procs = spawn_replicas(args.num_replicas, args.port, passthrough)
     router = ReplicaRouter([f"http://127.0.0.1:{args.port + 1 + i}" for i in range(args.num_replicas)])

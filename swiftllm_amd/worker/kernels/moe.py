@@ -16,6 +16,11 @@ Prompt-sized steps: csrc/moe_wide.hip holds a second form of the two expert GEMM
 `row_tiles` (2 or 4) consecutive 16-row tiles of one expert with one pass over a block of its weights. It reads the same
 tile tables and writes the same bits, so `moe_ffn` picks the form per token block from `wide_row_tiles` (host arithmetic on
 (tokens, k, E, H, I): capture and replay agree) and a token's output does not depend on the choice. Still six launches.
+
+FP8 expert weights (EngineConfig.moe_weight_dtype = "fp8_e4m3"; csrc/moe_fp8.h states the contract): the two stacks hold one
+e4m3fn code per element and come with one fp32 scale per output row (`up_gate_scale` [E, 2 I], `down_scale` [E, H]).
+`quantise_rows` is the loader's kernel; `moe_up_gate_silu` / `moe_down` / `moe_ffn` take the scales and call the FP8 entries
+(both forms, the same tables, the same grids, the same six launches) whenever the stacks are 8-bit.
 """
 import torch
 
@@ -27,12 +32,51 @@ LOGITS_F32 = 2      # SWL_MOE_LOGITS_F32
 MAX_EXPERTS = 256
 MAX_TOP_K = 16
 WIDE_ROW_TILES = (2, 4)     # what swl_moe_*_wide take
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
 
 
 def supported(hidden: int, inter: int, num_experts: int, top_k: int, dtype: torch.dtype = torch.bfloat16) -> bool:
     """Whether the expert GEMMs take the geometry (host arithmetic only): hidden % 64 == 0, inter % 32 == 0, at most 256
     experts, top-k at most 16 and at most the expert count."""
     return bool(_hip.load().swl_moe_supported(int(hidden), int(inter), int(num_experts), int(top_k), _hip.dtype_code(dtype)))
+
+
+def fp8_supported(hidden: int, inter: int, num_experts: int, top_k: int, dtype: torch.dtype = torch.bfloat16) -> bool:
+    """Whether the FP8 expert GEMMs take the geometry: `supported` with hidden % 64 == 0 and inter % 64 == 0."""
+    return bool(_hip.load().swl_moe_fp8_supported(int(hidden), int(inter), int(num_experts), int(top_k),
+                                                  _hip.dtype_code(dtype)))
+
+
+def row_scales(w: torch.Tensor):
+    """(scale, inv) fp32 [rows] of a 16-bit [rows, K] tensor, on its device: scale = max |w_row| / 448 (a zero row: 1),
+    inv = 1 / scale. The row maxima are exact wherever they are taken; the two divisions are done on the HOST (IEEE
+    division, one rounding each — a device's division need not be), which is what makes the codes reproducible there."""
+    amax = w.abs().amax(dim=1).float().cpu()
+    scale = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    return scale.to(w.device), (1.0 / scale).to(w.device)
+
+
+def quantise_rows(w: torch.Tensor, inv: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
+    """codes[r] = e4m3(clamp(fp32(w[r]) * inv[r], -448, 448)): w [rows, K] float16 / bfloat16, K % 16 == 0, inv fp32 [rows],
+    codes [rows, K] float8_e4m3fn (a contiguous slice of a stack), written in place."""
+    _hip.require_gpu_tensor(w, "w")
+    rows, k = w.shape
+    assert w.is_contiguous() and codes.is_contiguous() and tuple(codes.shape) == (rows, k) and codes.dtype == FP8
+    assert inv.dtype == torch.float32 and inv.is_contiguous() and inv.numel() == rows
+    _hip.call("swl_moe_quantise_rows", _hip.ptr(codes), _hip.ptr(w), _hip.ptr(inv), rows, k, _hip.dtype_code(w.dtype),
+              _hip.stream())
+    return codes
+
+
+def _fp8_scale(stack: torch.Tensor, scale, name: str) -> tuple:
+    """() for a 16-bit stack; (pointer of its row scales,) for an FP8 one."""
+    if stack.dtype != FP8:
+        assert scale is None, f"{name} is for FP8 stacks"
+        return ()
+    assert scale is not None and scale.dtype == torch.float32 and scale.is_contiguous(), f"FP8 stacks need {name}"
+    assert tuple(scale.shape) == tuple(stack.shape[:2]) and scale.device == stack.device
+    return (_hip.ptr(scale),)
 
 
 def max_pairs() -> int:
@@ -83,12 +127,13 @@ def moe_align(topk_ids: torch.Tensor, num_experts: int):
 
 
 def moe_up_gate_silu(x: torch.Tensor, expert_up_gate: torch.Tensor, tile_rows, tile_experts, top_k: int,
-                     act: torch.Tensor = None, row_tiles: int = 0) -> torch.Tensor:
+                     act: torch.Tensor = None, row_tiles: int = 0, up_gate_scale: torch.Tensor = None) -> torch.Tensor:
     """x [T, H], expert_up_gate [E, 2 I, H] ([up ; gate] per expert) -> act [T k, I] = up * silu(gate) of every pair.
-    `row_tiles` > 0: the wide form (same bits)."""
+    `row_tiles` > 0: the wide form (same bits). An FP8 stack comes with `up_gate_scale` fp32 [E, 2 I]."""
     _hip.require_gpu_tensor(x, "x")
     e, two_i, h = expert_up_gate.shape
-    assert x.dim() == 2 and x.shape[1] == h and x.stride(1) == 1 and x.dtype == expert_up_gate.dtype
+    scale = _fp8_scale(expert_up_gate, up_gate_scale, "up_gate_scale")
+    assert x.dim() == 2 and x.shape[1] == h and x.stride(1) == 1 and (scale or x.dtype == expert_up_gate.dtype)
     assert expert_up_gate.is_contiguous() and two_i % 2 == 0
     t, inter = x.shape[0], two_i // 2
     if act is None:
@@ -96,19 +141,21 @@ def moe_up_gate_silu(x: torch.Tensor, expert_up_gate: torch.Tensor, tile_rows, t
     assert act.is_contiguous() and tuple(act.shape) == (t * top_k, inter) and act.dtype == x.dtype
     assert tile_rows.numel() == tile_experts.numel() * TILE_ROWS
     wide = (int(row_tiles),) if row_tiles > 0 else ()
-    _hip.call("swl_moe_up_gate_silu_wide" if wide else "swl_moe_up_gate_silu", _hip.ptr(act), _hip.ptr(x),
-              _hip.ptr(expert_up_gate), _hip.ptr(tile_rows), _hip.ptr(tile_experts), tile_experts.numel(), t, int(top_k), h,
-              inter, e, x.stride(0), *wide, _hip.dtype_code(x.dtype), _hip.stream())
+    name = "swl_moe_up_gate_silu" + ("_fp8" if scale else "") + ("_wide" if wide else "")
+    _hip.call(name, _hip.ptr(act), _hip.ptr(x), _hip.ptr(expert_up_gate), *scale, _hip.ptr(tile_rows),
+              _hip.ptr(tile_experts), tile_experts.numel(), t, int(top_k), h, inter, e, x.stride(0), *wide,
+              _hip.dtype_code(x.dtype), _hip.stream())
     return act
 
 
 def moe_down(act: torch.Tensor, expert_down: torch.Tensor, tile_rows, tile_experts, top_k: int,
-             y: torch.Tensor = None, row_tiles: int = 0) -> torch.Tensor:
+             y: torch.Tensor = None, row_tiles: int = 0, down_scale: torch.Tensor = None) -> torch.Tensor:
     """act [T k, I], expert_down [E, H, I] -> y fp32 [T k, H]: every pair's down projection, unrounded. `row_tiles` > 0:
-    the wide form (same bits)."""
+    the wide form (same bits). An FP8 stack comes with `down_scale` fp32 [E, H]."""
     _hip.require_gpu_tensor(act, "act")
     e, h, inter = expert_down.shape
-    assert act.dim() == 2 and act.shape[1] == inter and act.is_contiguous() and act.dtype == expert_down.dtype
+    scale = _fp8_scale(expert_down, down_scale, "down_scale")
+    assert act.dim() == 2 and act.shape[1] == inter and act.is_contiguous() and (scale or act.dtype == expert_down.dtype)
     assert expert_down.is_contiguous() and act.shape[0] % top_k == 0
     pairs = act.shape[0]
     if y is None:
@@ -116,9 +163,10 @@ def moe_down(act: torch.Tensor, expert_down: torch.Tensor, tile_rows, tile_exper
     assert y.is_contiguous() and tuple(y.shape) == (pairs, h) and y.dtype == torch.float32
     assert tile_rows.numel() == tile_experts.numel() * TILE_ROWS
     wide = (int(row_tiles),) if row_tiles > 0 else ()
-    _hip.call("swl_moe_down_wide" if wide else "swl_moe_down", _hip.ptr(y), _hip.ptr(act), _hip.ptr(expert_down),
-              _hip.ptr(tile_rows), _hip.ptr(tile_experts), tile_experts.numel(), pairs // top_k, int(top_k), h, inter, e,
-              *wide, _hip.dtype_code(act.dtype), _hip.stream())
+    name = "swl_moe_down" + ("_fp8" if scale else "") + ("_wide" if wide else "")
+    _hip.call(name, _hip.ptr(y), _hip.ptr(act), _hip.ptr(expert_down), *scale, _hip.ptr(tile_rows), _hip.ptr(tile_experts),
+              tile_experts.numel(), pairs // top_k, int(top_k), h, inter, e, *wide, _hip.dtype_code(act.dtype),
+              _hip.stream())
     return y
 
 
@@ -136,11 +184,13 @@ def moe_combine(y: torch.Tensor, topk_w: torch.Tensor, out: torch.Tensor) -> tor
 
 
 def moe_ffn(x: torch.Tensor, router: torch.Tensor, expert_up_gate: torch.Tensor, expert_down: torch.Tensor, top_k: int,
-            norm_topk_prob: bool, skinny: bool = False, tap=None, layer_id: int = 0, wide_tiles: int = -1) -> torch.Tensor:
+            norm_topk_prob: bool, skinny: bool = False, tap=None, layer_id: int = 0, wide_tiles: int = -1,
+            up_gate_scale: torch.Tensor = None, down_scale: torch.Tensor = None) -> torch.Tensor:
     """The FFN of a mixture-of-experts layer on the normalised activations x [T, H]: a new [T, H] tensor. `tap` (tests): a
     list that receives (layer_id, topk_ids.cpu(), topk_w.cpu()) — a host copy, so a tapped step is never graph-captured.
     `wide_tiles`: -1 = `wide_row_tiles` decides the form of the expert GEMMs per token block, 0 = always the 16-row
-    kernels, 2 / 4 = always the wide ones with that many row tiles (the bits are the same either way)."""
+    kernels, 2 / 4 = always the wide ones with that many row tiles (the bits are the same either way). FP8 stacks come with
+    `up_gate_scale` / `down_scale` and take the FP8 entries of both forms."""
     if wide_tiles not in (-1, 0) + WIDE_ROW_TILES:
         raise ValueError(f"wide_tiles must be -1 (choose), 0 (16-row) or one of {list(WIDE_ROW_TILES)}, got {wide_tiles}")
     t = x.shape[0]
@@ -161,8 +211,8 @@ def moe_ffn(x: torch.Tensor, router: torch.Tensor, expert_up_gate: torch.Tensor,
         if act is None or act.shape[0] != n * top_k:        # (a step's blocks share one workspace; the last may be shorter)
             act = y = None
         form = wide_row_tiles(n, top_k, e, h, inter) if wide_tiles < 0 else wide_tiles
-        act = moe_up_gate_silu(xs, expert_up_gate, rows, experts, top_k, act, form)
-        y = moe_down(act, expert_down, rows, experts, top_k, y, form)
+        act = moe_up_gate_silu(xs, expert_up_gate, rows, experts, top_k, act, form, up_gate_scale)
+        y = moe_down(act, expert_down, rows, experts, top_k, y, form, down_scale)
         moe_combine(y, w, out[t0:t0 + n])
         if tap is not None:
             tapped.append((ids, w))

@@ -91,6 +91,16 @@ class LlamaModel:
             if int(getattr(engine_config, "max_loras", 0) or 0) > 0:
                 raise ValueError(f"max_loras > 0 cannot serve this {cfg.model_type} model: adapters on mixture-of-experts "
                                  "layers (their experts have no adapter update) are not built")
+        # FP8 expert weights (EngineConfig.moe_weight_dtype = "fp8_e4m3"; csrc/moe_fp8.h): the expert stacks only
+        self.moe_fp8 = getattr(engine_config, "moe_weight_dtype", "auto") == "fp8_e4m3"
+        if self.moe_fp8:
+            if not cfg.is_moe:
+                raise ValueError(f"moe_weight_dtype='fp8_e4m3' cannot serve this {cfg.model_type} model: it has no "
+                                 "mixture-of-experts layers, and FP8 weights are built for the expert stacks only")
+            if cfg.hidden_size % 64 or cfg.moe_inter_dim % 64:
+                raise ValueError(f"moe_weight_dtype='fp8_e4m3' cannot serve this {cfg.model_type} model: hidden_size "
+                                 f"{cfg.hidden_size}, expert intermediate size {cfg.moe_inter_dim}; the FP8 expert GEMMs "
+                                 "(csrc/moe_fp8.hip) walk 64 codes a step and take multiples of 64 for both")
         # element type of the KV pools: the activation dtype, or e4m3fn (EngineConfig.kv_cache_dtype = "fp8_e4m3")
         self.kv_fp8 = getattr(engine_config, "kv_cache_dtype", "auto") == "fp8_e4m3"
         self.kv_dtype = torch.float8_e4m3fn if self.kv_fp8 else self.dtype
@@ -177,7 +187,8 @@ class LlamaModel:
         _require_hip_device()
         self.weight = load_weights(self.model_config, self.dtype, self.engine_config.model_path,
                                    self.engine_config.use_dummy, device=self.device,
-                                   fuse_qkv=getattr(self.engine_config, "fuse_qkv", False))
+                                   fuse_qkv=getattr(self.engine_config, "fuse_qkv", False),
+                                   moe_weight_dtype="fp8_e4m3" if self.moe_fp8 else "auto")
         self.repack_decode_weights()
         self._tune_routes()
         self._init_to_get_rotary()

@@ -112,10 +112,12 @@ class LlamaTransformerLayerWeight:
     (and qkv_proj = [q ; k ; v] when fused). Qwen3: q_norm, k_norm [head_dim]. Qwen2: q_bias, k_bias, v_bias — with the
     fused projection they are three slices of one qkv_bias = [q ; k ; v]."""
 
-    def __init__(self, layer_id: int, model_config, dtype: torch.dtype):
+    def __init__(self, layer_id: int, model_config, dtype: torch.dtype, moe_fp8: bool = False):
         self.layer_id = layer_id
         self.model_config = model_config
         self.dtype = dtype
+        # FP8 expert weights (csrc/moe_fp8.h): the two stacks are e4m3fn codes, with one fp32 scale per output row
+        self.moe_fp8 = bool(moe_fp8)
         self.qkv_proj = None
         self.q_norm = self.k_norm = None
         self.qkv_bias = self.q_bias = self.k_bias = self.v_bias = None
@@ -124,12 +126,38 @@ class LlamaTransformerLayerWeight:
         # (up_gate_proj / down_proj are NOT pre-set here: a dense layer's attributes keep the order they always had, which
         # is the order callers walk vars(layer) in when they re-initialise the weights from one seeded generator)
         self.router = self.expert_up_gate = self.expert_down = None
+        self.expert_up_gate_scale = self.expert_down_scale = None      # fp32 [E, 2 I] / [E, H]: FP8 stacks only
 
     def alloc_experts(self, device: torch.device):
         cfg = self.model_config
         e, h, inter = cfg.num_experts, cfg.hidden_size, cfg.moe_inter_dim
-        self.expert_up_gate = torch.empty((e, 2 * inter, h), dtype=self.dtype, device=device)
-        self.expert_down = torch.empty((e, h, inter), dtype=self.dtype, device=device)
+        dtype = torch.float8_e4m3fn if self.moe_fp8 else self.dtype
+        self.expert_up_gate = torch.empty((e, 2 * inter, h), dtype=dtype, device=device)
+        self.expert_down = torch.empty((e, h, inter), dtype=dtype, device=device)
+        if self.moe_fp8:
+            self.expert_up_gate_scale = torch.ones((e, 2 * inter), dtype=torch.float32, device=device)
+            self.expert_down_scale = torch.ones((e, h), dtype=torch.float32, device=device)
+
+    def load_experts(self, getter: Getter, device: torch.device):
+        """Every expert goes to its place inside the stacks: no second copy of the expert weights at any time. FP8: an
+        expert's tensor is uploaded in 16 bits, its row scales are taken with torch and the quantiser writes its codes
+        straight into the byte stack (kernels/moe.py: row_scales, quantise_rows)."""
+        self.alloc_experts(device)
+        for spec, attr, row in expert_weight_specs(self.model_config, self.layer_id):
+            t = getter(spec)
+            assert isinstance(t, torch.Tensor), f"Weight {spec.key} is not a tensor"
+            assert tuple(t.shape) == tuple(spec.shape), \
+                f"Shape of weight {spec.key} does not match: {tuple(t.shape)} vs {spec.shape}"
+            stack = getattr(self, attr)
+            place = stack.view(-1, stack.shape[-1])[row:row + spec.shape[0]]
+            if not self.moe_fp8:
+                place.copy_(t)
+                continue
+            from .kernels.moe import quantise_rows, row_scales
+            t = t.to(device=device, dtype=self.dtype).contiguous()
+            scale, inv = row_scales(t)
+            getattr(self, attr + "_scale").view(-1)[row:row + spec.shape[0]].copy_(scale)
+            quantise_rows(t, inv, place)
 
     def slice_qkv_bias(self):
         """q_bias / k_bias / v_bias as views of the assembled qkv_bias (what the kernel receives)."""
@@ -140,15 +168,7 @@ class LlamaTransformerLayerWeight:
     def load(self, getter: Getter, device: torch.device, fuse_qkv: bool):
         _fill(self, layer_weight_specs(self.model_config, self.layer_id), getter, self.dtype, device)
         if getattr(self.model_config, "num_experts", 0):
-            # every expert goes to its place inside the stacks: no second copy of the expert weights at any time
-            self.alloc_experts(device)
-            for spec, attr, row in expert_weight_specs(self.model_config, self.layer_id):
-                t = getter(spec)
-                assert isinstance(t, torch.Tensor), f"Weight {spec.key} is not a tensor"
-                assert tuple(t.shape) == tuple(spec.shape), \
-                    f"Shape of weight {spec.key} does not match: {tuple(t.shape)} vs {spec.shape}"
-                stack = getattr(self, attr)
-                stack.view(-1, stack.shape[-1])[row:row + spec.shape[0]].copy_(t)
+            self.load_experts(getter, device)
         else:
             self.up_gate_proj = torch.cat((self.up_proj, self.gate_proj), dim=0).contiguous()
             del self.up_proj, self.gate_proj
@@ -163,11 +183,12 @@ class LlamaTransformerLayerWeight:
 class LlamaWeight:
     """All weights of the model: wte, lm_head, final_norm and `layers`."""
 
-    def __init__(self, model_config, dtype: torch.dtype, model_version: str = "llama"):
+    def __init__(self, model_config, dtype: torch.dtype, model_version: str = "llama", moe_fp8: bool = False):
         self.model_config = model_config
         self.dtype = dtype
         self.model_version = model_version
-        self.layers = [LlamaTransformerLayerWeight(i, model_config, dtype)
+        self.moe_fp8 = bool(moe_fp8)
+        self.layers = [LlamaTransformerLayerWeight(i, model_config, dtype, moe_fp8)
                        for i in range(model_config.num_layers)]
 
     def load(self, getter: Getter, device: torch.device, fuse_qkv: bool = False):
@@ -296,7 +317,9 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
             t = dest(specs[attr].shape)
             setattr(layer, attr, t)
             plan.append((specs[attr].key, specs[attr].shape, t, 0))
-        if moe:                                             # every expert at its final offset inside the two stacks
+        if moe and weight.moe_fp8:
+            pass                                            # (quantised per expert behind the stream: load_weights)
+        elif moe:                                           # every expert at its final offset inside the two stacks
             layer.alloc_experts(device)
             for spec, attr, row in expert_weight_specs(cfg, layer.layer_id):
                 plan.append((spec.key, spec.shape, getattr(layer, attr), row))
@@ -425,16 +448,18 @@ def detect_model_version(model_path: str) -> str:
 
 def load_weights(model_config, dtype: torch.dtype, model_path: str, use_dummy: bool = False,
                  model_version: str = "auto", device="cuda", fuse_qkv: bool = False,
-                 streaming: bool = True) -> LlamaWeight:
+                 streaming: bool = True, moe_weight_dtype: str = "auto") -> LlamaWeight:
     """Read (or synthesise) every weight of the model onto `device` in `dtype`. `streaming=False` forces the
-    reference's tensor-by-tensor safetensors path."""
+    reference's tensor-by-tensor safetensors path. `moe_weight_dtype="fp8_e4m3"` (mixture-of-experts models): the expert
+    stacks are quantised per output row as they load (csrc/moe_fp8.h); everything else stays `dtype`."""
     device = torch.device(device)
+    moe_fp8 = moe_weight_dtype == "fp8_e4m3"
     if model_version == "auto":
         if getattr(model_config, "model_type", "llama") != "llama":
             model_version = "llama3.2" if model_config.tie_word_embeddings else "llama"
         else:
             model_version = detect_model_version(model_path)
-    weight = LlamaWeight(model_config, dtype, model_version)
+    weight = LlamaWeight(model_config, dtype, model_version, moe_fp8)
     if use_dummy:
         getter = _dummy_getter(dtype, device)
     else:
@@ -444,8 +469,12 @@ def load_weights(model_config, dtype: torch.dtype, model_path: str, use_dummy: b
             assert os.path.exists(index_path) or len(st_files) == 1, \
                 "model.safetensors.index.json not found, but there are multiple .safetensors files"
             if _stream_safetensors(weight, model_path, st_files, device, fuse_qkv):
+                if moe_fp8:                                 # the experts: one 16-bit tensor at a time, quantised into place
+                    getter = _safetensors_getter(model_path, st_files, device)
+                    for layer in weight.layers:
+                        layer.load_experts(getter, device)
                 return weight
-            weight = LlamaWeight(model_config, dtype, model_version)     # start over on the per-tensor path
+            weight = LlamaWeight(model_config, dtype, model_version, moe_fp8)    # start over on the per-tensor path
         getter = (_safetensors_getter(model_path, st_files, device) if st_files
                   else _torch_bin_getter(model_path, device))
     weight.load(getter, device, fuse_qkv)

@@ -22,6 +22,12 @@ wide:<geometry>  The two forms of the expert GEMMs side by side (same weights an
     the chooser picks (`chosen`), and the torch loop in the same run. The forms' outputs are compared bit for bit first.
 step  A whole decode step at Qwen3-30B-A3B dimensions (48 layers, dummy weights, bfloat16, 1024-token contexts) at batch
     1 / 8 / 32: host wall time per forward() on graph replay.
+fp8:<geometry>  The 16-bit and the FP8 (e4m3, csrc/moe_fp8.hip) FFN of one layer in ONE run, alternating, on the same inputs
+    (the FP8 stacks are the 16-bit ones quantised per row as the loader does) at T = 1, 8, 32, 128 and 1024 (the wide form
+    where the chooser takes it): us of the whole FFN per dtype, the distinct active experts, TB/s over THEIR bytes (3 I H x
+    2 or x 1 bytes, the scales' 4 (2 I + H) on top), `fp8_over_16` (medians) and `ranges_ok`: the FP8 range does not lie
+    above the 16-bit range of the same run. The ideal is half the expert bytes; everything else in the FFN is unchanged.
+step_fp8  `step` for both expert dtypes in one process, the 16-bit model first.
 Each kernel figure is the median of `--repeats` runs of `--iters` back-to-back launches between two device events (a tenth
 of the iterations from 1024 tokens on), with the range [min, max].
 """
@@ -46,7 +52,7 @@ QWEN3_30B_A3B = dict(model_type="qwen3_moe", hidden_act="silu", hidden_size=2048
                      head_dim=128, num_experts=128, num_experts_per_tok=8, norm_topk_prob=True, decoder_sparse_step=1,
                      mlp_only_layers=[], vocab_size=151936, max_position_embeddings=40960, rms_norm_eps=1e-6,
                      rope_theta=1000000.0, tie_word_embeddings=False)
-SECTION_TIMEOUT_S = {"ffn": 300, "wide": 420, "step": 420}
+SECTION_TIMEOUT_S = {"ffn": 300, "wide": 420, "step": 420, "fp8": 300, "step_fp8": 840}
 
 
 def _timed(fn, iters, repeats):
@@ -164,7 +170,51 @@ def wide_section(name, iters, repeats):
     return out
 
 
-def step_section():
+def fp8_section(name, iters, repeats):
+    from swiftllm_amd.worker.kernels import moe as M
+    H, I, E, k = GEOMETRIES[name]
+    dt, dev = torch.bfloat16, "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    u = lambda *shape: torch.empty(shape, dtype=dt, device=dev).uniform_(-1e-3, 1e-3, generator=g)     # noqa: E731
+    router, stacks16 = u(E, H), (u(E, 2 * I, H), u(E, H, I))
+    stacks8, scales = [], []
+    for w in stacks16:
+        scale, inv = M.row_scales(w.view(-1, w.shape[-1]))
+        stacks8.append(M.quantise_rows(w.view(-1, w.shape[-1]), inv, torch.empty(w.shape, dtype=M.FP8, device=dev).view(
+            -1, w.shape[-1])).view(w.shape))
+        scales.append(scale.view(w.shape[:2]))
+    forms = {"bf16": (lambda x: M.moe_ffn(x, router, *stacks16, k, True), 3 * I * H * 2),
+             "fp8": (lambda x: M.moe_ffn(x, router, *stacks8, k, True, up_gate_scale=scales[0], down_scale=scales[1]),
+                     3 * I * H + 4 * (2 * I + H))}
+    out = {}
+    for T in (1, 8, 32, 128, 1024):
+        n = iters if T < 1024 else max(2, iters // 10)
+        x = torch.randn((T, H), device=dev, generator=g).to(dt)
+        tap = []
+        M.moe_ffn(x, router, *stacks16, k, True, tap=tap)
+        active = int(torch.unique(tap[0][1]).numel())
+        runs = {f: [] for f in forms}
+        for _ in range(repeats):                            # alternating: both dtypes see the same neighbours on the machine
+            for f, (fn, _) in forms.items():
+                runs[f] += _timed(lambda: fn(x), n, 1)
+        res = {"active_experts": active, "wide_row_tiles": M.wide_row_tiles(T, k, E, H, I)}
+        for f, (_, expert_bytes) in forms.items():
+            res[f] = dict(_summary(runs[f]), tb_s=round(active * expert_bytes / statistics.median(runs[f]) / 1e6, 3))
+        res["fp8_over_16"] = round(res["fp8"]["median_us"] / res["bf16"]["median_us"], 3)
+        res["ranges_ok"] = res["fp8"]["min_us"] <= res["bf16"]["max_us"]
+        out[f"fp8_{name}_t{T}"] = res
+    return out
+
+
+def step_section(moe_weight_dtypes=("auto",)):
+    out = {}
+    for mwd in moe_weight_dtypes:
+        res = _steps(mwd)
+        out.update(res if mwd == "auto" else {f"{mwd}_{key}": v for key, v in res.items()})
+    return out
+
+
+def _steps(moe_weight_dtype):
     from swiftllm_amd import EngineConfig, LlamaModel
     S, steps, out = 1024, 32, {}
     path = tempfile.mkdtemp(prefix="swl_moe_micro_")
@@ -174,7 +224,7 @@ def step_section():
     batch_max = 32
     ec = EngineConfig(model_path=path, use_dummy=True, block_size=16, gpu_mem_utilization=0.97, num_cpu_blocks=0,
                       max_seqs_in_block_table=batch_max + 64, max_blocks_per_seq=max_len // 16 + 8, max_batch_size=batch_max,
-                      max_tokens_in_batch=4096, dtype="bfloat16", use_hip_graph=True)
+                      max_tokens_in_batch=4096, dtype="bfloat16", use_hip_graph=True, moe_weight_dtype=moe_weight_dtype)
     model = LlamaModel(ec)
     model.load_weights()
     model.init_kvcache_and_swap(batch_max * (max_len // 16 + 2) + 64)
@@ -212,7 +262,9 @@ def main():
         assert torch.cuda.is_available(), "needs a HIP device"
         kind, _, name = a.child.partition(":")
         res = (ffn_section(name, a.iters, a.repeats) if kind == "ffn" else
-               wide_section(name, a.iters, a.repeats) if kind == "wide" else step_section())
+               wide_section(name, a.iters, a.repeats) if kind == "wide" else
+               fp8_section(name, a.iters, a.repeats) if kind == "fp8" else
+               step_section(("auto", "fp8_e4m3")) if kind == "step_fp8" else step_section())
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     merged = {"iters": a.iters, "repeats": a.repeats}
