@@ -266,8 +266,18 @@ __global__ __launch_bounds__(NWV * 64, NWV == 2 ? 1 : 2) void gemm_skinny_ring_k
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool is_gate = MODE == kGemmSiluGate && wave >= HWV;
-    const int col0 = MODE == kGemmSiluGate ? (blockIdx.x * HWV + (wave % HWV)) * 32
-                                           : (blockIdx.x * NWV + wave) * 32;
+    // SPREAD (packed W, four-wave SiLU-gate forms): wave j of workgroup b owns `up` tile b + j * gridDim.x instead of tile
+    // b * HWV + j — the runs of W a workgroup streams at the same time then lie a quarter of the matrix apart instead of
+    // exactly K * 64 bytes (a power of two for the usual K). Stream only, at the Llama-3-8B up/gate shape
+    // (tools/probe/weight_stream_probe.hip, profiles/weight_stream_pattern_probe.jsonl): 36.8 -> 35.1 us; in the decode step
+    // 39.9 -> 38.3 us (profiles/weight_stream_kernel_trace_{parent,new}.md). The four-wave partial form (down_proj) gained
+    // 0.5 us in the probe and LOST 0.3 us in the step, three traces out of three; the three-wave qkv form loses in the probe;
+    // lm_head (direct) was not measured: all three keep neighbouring tiles.
+    // Every tile is computed exactly as before, by another wave: same bits.
+    constexpr bool SPREAD = PACKED && NWV == kGemmWaves && MODE == kGemmSiluGate;
+    const int owned = MODE == kGemmSiluGate ? wave % HWV : wave; // which of the workgroup's (up) tiles is this wave's
+    const int col0 = (SPREAD ? blockIdx.x + owned * static_cast<int>(gridDim.x)
+                             : blockIdx.x * (MODE == kGemmSiluGate ? HWV : NWV) + owned) * 32;
     const bool tile_ok = col0 < N; // barriers below: a wave without a tile still stages x and syncs
     const int n0 = tile_ok ? col0 + (is_gate ? N : 0) : 0;
     const int ksplit = blockIdx.y;
