@@ -852,6 +852,41 @@ int swl_moe_down_fp8_wide(float *y, const void *act, const void *expert_down, co
                           int32_t top_k, int32_t hidden, int32_t inter, int32_t num_experts, int32_t row_tiles, int32_t dtype,
                           swl_stream_t stream);
 
+/* ---- block-scaled FP8 (e4m3) expert weights: pre-quantised checkpoints served with their own codes and scales
+ * (csrc/moe_fp8_block.hip, csrc/moe_fp8_block_wide.hip; the storage contract and the chain: csrc/moe_fp8_block.h) --------------
+ * The codes are stored as above; the scales are one fp32 per 128 x 128 block, as the checkpoints' weight_scale_inv tensors
+ * hold them: up_gate_bscale [num_experts, 2 * ceil(inter / 128), ceil(hidden / 128)] (up's row blocks, then gate's) and
+ * down_bscale [num_experts, ceil(hidden / 128), ceil(inter / 128)]; a weight means fp(code) * bscale[row / 128][k / 128].
+ *   swl_moe_fp8_block_supported: swl_moe_fp8_supported's geometry (hidden % 64 == 0 and inter % 64 == 0). Host only.
+ *   swl_moe_up_gate_silu_fp8_block, swl_moe_down_fp8_block: the per-row FP8 entries' arguments with the block scales and
+ *     their block counts behind the weights (row_blocks / k_blocks = ceil(inter / 128) / ceil(hidden / 128) for up and gate,
+ *     ceil(hidden / 128) / ceil(inter / 128) for down; anything else: SWL_ERR_BAD_ARG), the same checks with the same
+ *     codes, the same tables and the same grids. Every 64-wide k step's fp32 partial is built from a zero accumulator and
+ *     folded into the running sum with ONE fmaf by its block's scale; no multiply follows the sum. A row's bits depend on
+ *     that row's activations, experts and weights only.
+ *   swl_moe_up_gate_silu_fp8_block_wide, swl_moe_down_fp8_block_wide: their row-tile form: the SAME BITS as the two entries above.
+ *     row_tiles is 2 (4 and every other positive value: SWL_ERR_UNSUPPORTED — four tiles of running sums and partials do not
+ *     fit a wave's registers); where swl_moe_wide_row_tiles answers 4 the caller passes 2. */
+int swl_moe_fp8_block_supported(int32_t hidden, int32_t inter, int32_t num_experts, int32_t top_k, int32_t dtype);
+int swl_moe_up_gate_silu_fp8_block(void *act, const void *x, const void *expert_up_gate, const float *up_gate_bscale,
+                                   int32_t row_blocks, int32_t k_blocks, const int32_t *tile_rows,
+                                   const int32_t *tile_experts, int32_t max_tiles, int32_t num_tokens, int32_t top_k,
+                                   int32_t hidden, int32_t inter, int32_t num_experts, int64_t x_row_stride, int32_t dtype,
+                                   swl_stream_t stream);
+int swl_moe_down_fp8_block(float *y, const void *act, const void *expert_down, const float *down_bscale, int32_t row_blocks,
+                           int32_t k_blocks, const int32_t *tile_rows, const int32_t *tile_experts, int32_t max_tiles,
+                           int32_t num_tokens, int32_t top_k, int32_t hidden, int32_t inter, int32_t num_experts,
+                           int32_t dtype, swl_stream_t stream);
+int swl_moe_up_gate_silu_fp8_block_wide(void *act, const void *x, const void *expert_up_gate, const float *up_gate_bscale,
+                                        int32_t row_blocks, int32_t k_blocks, const int32_t *tile_rows,
+                                        const int32_t *tile_experts, int32_t max_tiles, int32_t num_tokens, int32_t top_k,
+                                        int32_t hidden, int32_t inter, int32_t num_experts, int64_t x_row_stride,
+                                        int32_t row_tiles, int32_t dtype, swl_stream_t stream);
+int swl_moe_down_fp8_block_wide(float *y, const void *act, const void *expert_down, const float *down_bscale,
+                                int32_t row_blocks, int32_t k_blocks, const int32_t *tile_rows, const int32_t *tile_experts,
+                                int32_t max_tiles, int32_t num_tokens, int32_t top_k, int32_t hidden, int32_t inter,
+                                int32_t num_experts, int32_t row_tiles, int32_t dtype, swl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,16 @@ _SPECIAL = {
     "swl_moe_up_gate_silu_fp8_wide": ([_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P],
                                       _I32),
     "swl_moe_down_fp8_wide": ([_P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P], _I32),
+    # ... and on block-scaled FP8 checkpoints (one fp32 scale per 128 x 128 block, with its two block counts, behind the
+    # codes; csrc/moe_fp8_block.hip, csrc/moe_fp8_block_wide.hip; tests/test_moe_fp8_block_host.py)
+    "swl_moe_fp8_block_supported": ([_I32, _I32, _I32, _I32, _I32], _I32),
+    "swl_moe_up_gate_silu_fp8_block": ([_P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32,
+                                        _P], _I32),
+    "swl_moe_down_fp8_block": ([_P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P], _I32),
+    "swl_moe_up_gate_silu_fp8_block_wide": ([_P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I64,
+                                             _I32, _I32, _P], _I32),
+    "swl_moe_down_fp8_block_wide": ([_P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
+                                    _I32),
 }
 
 _lock = threading.Lock()

@@ -19,6 +19,7 @@ MOE_FAMILY = {"qwen3_moe": "qwen3", "mixtral": "mistral"}
 # what csrc/moe.hip takes: one wave routes a token (4 experts a lane), one lane holds a slot
 MOE_MAX_EXPERTS = 256
 MOE_MAX_TOP_K = 16
+FP8_BLOCK = 128     # rows and columns one weight_scale_inv of a block-scaled FP8 checkpoint covers
 # the attention kernels' tiles: q heads per kv head, and head_dim
 GROUP_SIZES = (1, 2, 4, 8)
 HEAD_DIMS = (32, 64, 128)
@@ -61,6 +62,11 @@ class LlamaModelConfig:
             self._init_family(model_config)
         if model_type in MOE_FAMILY:
             self._init_moe(model_config)
+        # a pre-quantised checkpoint (quantization_config): only block-scaled FP8 — e4m3 codes with one fp32
+        # weight_scale_inv per 128 x 128 block (csrc/moe_fp8_block.h) — is served, with its own codes and scales
+        self.fp8_block = False
+        if model_config.get("quantization_config"):
+            self._init_quantisation(model_config["quantization_config"])
         self.q_size = self.num_q_heads * self.head_dim
 
     @property
@@ -98,6 +104,31 @@ class LlamaModelConfig:
             raise ValueError(f"{kind}: hidden_size {self.hidden_size}, expert intermediate size {self.moe_inter_dim}; the expert "
                              "GEMMs are built for hidden_size % 64 == 0 and an intermediate size % 32 == 0 (16-column blocks "
                              "within a 65535-block grid)")
+
+    def _init_quantisation(self, q: dict):
+        """quantization_config: the block-scaled FP8 layout of transformers' fine-grained FP8 quantiser, or a refusal."""
+        kind = self.model_type
+        method, fmt, block = q.get("quant_method"), q.get("fmt", "e4m3"), q.get("weight_block_size")
+        if method != "fp8":
+            raise ValueError(f"{kind}: quantization_config asks for quant_method {method!r}; of the pre-quantised formats only "
+                             "block-scaled FP8 (quant_method 'fp8') is built (no compressed-tensors, GPTQ, AWQ or "
+                             "bitsandbytes checkpoints)")
+        if fmt != "e4m3":
+            raise ValueError(f"{kind}: quantization_config asks for fmt {fmt!r}; the FP8 expert GEMMs dequantise e4m3 codes only")
+        if block is None or list(block) != [FP8_BLOCK, FP8_BLOCK]:
+            raise ValueError(f"{kind}: quantization_config has weight_block_size {block}; the kernels are built for one scale "
+                             f"per [{FP8_BLOCK}, {FP8_BLOCK}] block (per-tensor FP8 checkpoints and other block sizes are not)")
+        if q.get("activation_scheme", "dynamic") != "dynamic":
+            raise ValueError(f"{kind}: quantization_config has activation_scheme {q['activation_scheme']!r}: stored input "
+                             "scales belong to FP8 activations, which are not built (activations stay 16-bit)")
+        if not self.is_moe:
+            raise ValueError(f"{kind}: a quantised dense model (no experts); block-scaled FP8 weights are built for the "
+                             "expert stacks of mixture-of-experts models only")
+        if self.hidden_size % 64 or self.moe_inter_dim % 64:
+            raise ValueError(f"{kind}: hidden_size {self.hidden_size}, expert intermediate size {self.moe_inter_dim}; the "
+                             "block-scaled FP8 expert GEMMs (swl_moe_fp8_block_supported) walk 64 codes a step and take "
+                             "multiples of 64 for both")
+        self.fp8_block = True
 
     def _init_family(self, c: dict):
         """Mistral, Qwen2 and Qwen3: the fields Llama's parsing above does not read, and the refusals."""

@@ -21,6 +21,12 @@ FP8 expert weights (EngineConfig.moe_weight_dtype = "fp8_e4m3"; csrc/moe_fp8.h s
 e4m3fn code per element and come with one fp32 scale per output row (`up_gate_scale` [E, 2 I], `down_scale` [E, H]).
 `quantise_rows` is the loader's kernel; `moe_up_gate_silu` / `moe_down` / `moe_ffn` take the scales and call the FP8 entries
 (both forms, the same tables, the same grids, the same six launches) whenever the stacks are 8-bit.
+
+Block-scaled FP8 checkpoints (csrc/moe_fp8_block.h): the stacks hold the checkpoint's own codes and come with its own scales,
+one fp32 per 128 x 128 block — `up_gate_bscale` [E, 2 ceil(I / 128), ceil(H / 128)] (up's row blocks, then gate's) and
+`down_bscale` [E, ceil(H / 128), ceil(I / 128)]. The same three functions take them in place of the row scales and call the
+block entries. Their row-tile form is built for 2 tiles only (4 do not fit a wave's registers): a `row_tiles` of 4 runs the
+2-tile kernels, which write the same bits.
 """
 import torch
 
@@ -34,6 +40,8 @@ MAX_TOP_K = 16
 WIDE_ROW_TILES = (2, 4)     # what swl_moe_*_wide take
 FP8 = torch.float8_e4m3fn
 FP8_MAX = 448.0
+BLOCK = 128         # rows and k one scale of a block-scaled FP8 checkpoint covers
+BLOCK_WIDE_ROW_TILES = 2    # what swl_moe_*_fp8_block_wide take
 
 
 def supported(hidden: int, inter: int, num_experts: int, top_k: int, dtype: torch.dtype = torch.bfloat16) -> bool:
@@ -46,6 +54,12 @@ def fp8_supported(hidden: int, inter: int, num_experts: int, top_k: int, dtype: 
     """Whether the FP8 expert GEMMs take the geometry: `supported` with hidden % 64 == 0 and inter % 64 == 0."""
     return bool(_hip.load().swl_moe_fp8_supported(int(hidden), int(inter), int(num_experts), int(top_k),
                                                   _hip.dtype_code(dtype)))
+
+
+def fp8_block_supported(hidden: int, inter: int, num_experts: int, top_k: int, dtype: torch.dtype = torch.bfloat16) -> bool:
+    """Whether the block-scaled FP8 expert GEMMs take the geometry: that of `fp8_supported`."""
+    return bool(_hip.load().swl_moe_fp8_block_supported(int(hidden), int(inter), int(num_experts), int(top_k),
+                                                        _hip.dtype_code(dtype)))
 
 
 def row_scales(w: torch.Tensor):
@@ -77,6 +91,21 @@ def _fp8_scale(stack: torch.Tensor, scale, name: str) -> tuple:
     assert scale is not None and scale.dtype == torch.float32 and scale.is_contiguous(), f"FP8 stacks need {name}"
     assert tuple(scale.shape) == tuple(stack.shape[:2]) and scale.device == stack.device
     return (_hip.ptr(scale),)
+
+
+def block_scales_shape(rows: int, k: int) -> tuple:
+    """(row blocks, k blocks) of a [rows, k] projection's block scales: a checkpoint's weight_scale_inv shape."""
+    return (rows + BLOCK - 1) // BLOCK, (k + BLOCK - 1) // BLOCK
+
+
+def _fp8_block_scale(stack: torch.Tensor, bscale: torch.Tensor, halves: int, name: str) -> tuple:
+    """(pointer, row blocks, k blocks) of the block scales of an FP8 stack [E, halves * rows, k]."""
+    e, rows, k = stack.shape
+    rb, kb = block_scales_shape(rows // halves, k)
+    assert stack.dtype == FP8, f"{name} is for FP8 stacks"
+    assert bscale.dtype == torch.float32 and bscale.is_contiguous() and bscale.device == stack.device
+    assert tuple(bscale.shape) == (e, halves * rb, kb), f"{name} must be {(e, halves * rb, kb)}, got {tuple(bscale.shape)}"
+    return _hip.ptr(bscale), rb, kb
 
 
 def max_pairs() -> int:
@@ -127,12 +156,20 @@ def moe_align(topk_ids: torch.Tensor, num_experts: int):
 
 
 def moe_up_gate_silu(x: torch.Tensor, expert_up_gate: torch.Tensor, tile_rows, tile_experts, top_k: int,
-                     act: torch.Tensor = None, row_tiles: int = 0, up_gate_scale: torch.Tensor = None) -> torch.Tensor:
+                     act: torch.Tensor = None, row_tiles: int = 0, up_gate_scale: torch.Tensor = None,
+                     up_gate_bscale: torch.Tensor = None) -> torch.Tensor:
     """x [T, H], expert_up_gate [E, 2 I, H] ([up ; gate] per expert) -> act [T k, I] = up * silu(gate) of every pair.
-    `row_tiles` > 0: the wide form (same bits). An FP8 stack comes with `up_gate_scale` fp32 [E, 2 I]."""
+    `row_tiles` > 0: the wide form (same bits). An FP8 stack comes with `up_gate_scale` fp32 [E, 2 I], or — a block-scaled
+    checkpoint's — with `up_gate_bscale` fp32 [E, 2 ceil(I / 128), ceil(H / 128)]."""
     _hip.require_gpu_tensor(x, "x")
     e, two_i, h = expert_up_gate.shape
-    scale = _fp8_scale(expert_up_gate, up_gate_scale, "up_gate_scale")
+    block = up_gate_bscale is not None
+    if block:
+        assert up_gate_scale is None, "one kind of scales"
+        scale = _fp8_block_scale(expert_up_gate, up_gate_bscale, 2, "up_gate_bscale")
+        row_tiles = min(int(row_tiles), BLOCK_WIDE_ROW_TILES)
+    else:
+        scale = _fp8_scale(expert_up_gate, up_gate_scale, "up_gate_scale")
     assert x.dim() == 2 and x.shape[1] == h and x.stride(1) == 1 and (scale or x.dtype == expert_up_gate.dtype)
     assert expert_up_gate.is_contiguous() and two_i % 2 == 0
     t, inter = x.shape[0], two_i // 2
@@ -141,7 +178,7 @@ def moe_up_gate_silu(x: torch.Tensor, expert_up_gate: torch.Tensor, tile_rows, t
     assert act.is_contiguous() and tuple(act.shape) == (t * top_k, inter) and act.dtype == x.dtype
     assert tile_rows.numel() == tile_experts.numel() * TILE_ROWS
     wide = (int(row_tiles),) if row_tiles > 0 else ()
-    name = "swl_moe_up_gate_silu" + ("_fp8" if scale else "") + ("_wide" if wide else "")
+    name = "swl_moe_up_gate_silu" + ("_fp8" if scale else "") + ("_block" if block else "") + ("_wide" if wide else "")
     _hip.call(name, _hip.ptr(act), _hip.ptr(x), _hip.ptr(expert_up_gate), *scale, _hip.ptr(tile_rows),
               _hip.ptr(tile_experts), tile_experts.numel(), t, int(top_k), h, inter, e, x.stride(0), *wide,
               _hip.dtype_code(x.dtype), _hip.stream())
@@ -149,12 +186,20 @@ def moe_up_gate_silu(x: torch.Tensor, expert_up_gate: torch.Tensor, tile_rows, t
 
 
 def moe_down(act: torch.Tensor, expert_down: torch.Tensor, tile_rows, tile_experts, top_k: int,
-             y: torch.Tensor = None, row_tiles: int = 0, down_scale: torch.Tensor = None) -> torch.Tensor:
+             y: torch.Tensor = None, row_tiles: int = 0, down_scale: torch.Tensor = None,
+             down_bscale: torch.Tensor = None) -> torch.Tensor:
     """act [T k, I], expert_down [E, H, I] -> y fp32 [T k, H]: every pair's down projection, unrounded. `row_tiles` > 0:
-    the wide form (same bits). An FP8 stack comes with `down_scale` fp32 [E, H]."""
+    the wide form (same bits). An FP8 stack comes with `down_scale` fp32 [E, H], or — a block-scaled checkpoint's — with
+    `down_bscale` fp32 [E, ceil(H / 128), ceil(I / 128)]."""
     _hip.require_gpu_tensor(act, "act")
     e, h, inter = expert_down.shape
-    scale = _fp8_scale(expert_down, down_scale, "down_scale")
+    block = down_bscale is not None
+    if block:
+        assert down_scale is None, "one kind of scales"
+        scale = _fp8_block_scale(expert_down, down_bscale, 1, "down_bscale")
+        row_tiles = min(int(row_tiles), BLOCK_WIDE_ROW_TILES)
+    else:
+        scale = _fp8_scale(expert_down, down_scale, "down_scale")
     assert act.dim() == 2 and act.shape[1] == inter and act.is_contiguous() and (scale or act.dtype == expert_down.dtype)
     assert expert_down.is_contiguous() and act.shape[0] % top_k == 0
     pairs = act.shape[0]
@@ -163,7 +208,7 @@ def moe_down(act: torch.Tensor, expert_down: torch.Tensor, tile_rows, tile_exper
     assert y.is_contiguous() and tuple(y.shape) == (pairs, h) and y.dtype == torch.float32
     assert tile_rows.numel() == tile_experts.numel() * TILE_ROWS
     wide = (int(row_tiles),) if row_tiles > 0 else ()
-    name = "swl_moe_down" + ("_fp8" if scale else "") + ("_wide" if wide else "")
+    name = "swl_moe_down" + ("_fp8" if scale else "") + ("_block" if block else "") + ("_wide" if wide else "")
     _hip.call(name, _hip.ptr(y), _hip.ptr(act), _hip.ptr(expert_down), *scale, _hip.ptr(tile_rows), _hip.ptr(tile_experts),
               tile_experts.numel(), pairs // top_k, int(top_k), h, inter, e, *wide, _hip.dtype_code(act.dtype),
               _hip.stream())
@@ -185,12 +230,14 @@ def moe_combine(y: torch.Tensor, topk_w: torch.Tensor, out: torch.Tensor) -> tor
 
 def moe_ffn(x: torch.Tensor, router: torch.Tensor, expert_up_gate: torch.Tensor, expert_down: torch.Tensor, top_k: int,
             norm_topk_prob: bool, skinny: bool = False, tap=None, layer_id: int = 0, wide_tiles: int = -1,
-            up_gate_scale: torch.Tensor = None, down_scale: torch.Tensor = None) -> torch.Tensor:
+            up_gate_scale: torch.Tensor = None, down_scale: torch.Tensor = None, up_gate_bscale: torch.Tensor = None,
+            down_bscale: torch.Tensor = None) -> torch.Tensor:
     """The FFN of a mixture-of-experts layer on the normalised activations x [T, H]: a new [T, H] tensor. `tap` (tests): a
     list that receives (layer_id, topk_ids.cpu(), topk_w.cpu()) — a host copy, so a tapped step is never graph-captured.
     `wide_tiles`: -1 = `wide_row_tiles` decides the form of the expert GEMMs per token block, 0 = always the 16-row
     kernels, 2 / 4 = always the wide ones with that many row tiles (the bits are the same either way). FP8 stacks come with
-    `up_gate_scale` / `down_scale` and take the FP8 entries of both forms."""
+    `up_gate_scale` / `down_scale` (per row) or `up_gate_bscale` / `down_bscale` (per 128 x 128 block) and take the FP8
+    entries of both forms."""
     if wide_tiles not in (-1, 0) + WIDE_ROW_TILES:
         raise ValueError(f"wide_tiles must be -1 (choose), 0 (16-row) or one of {list(WIDE_ROW_TILES)}, got {wide_tiles}")
     t = x.shape[0]
@@ -211,8 +258,8 @@ def moe_ffn(x: torch.Tensor, router: torch.Tensor, expert_up_gate: torch.Tensor,
         if act is None or act.shape[0] != n * top_k:        # (a step's blocks share one workspace; the last may be shorter)
             act = y = None
         form = wide_row_tiles(n, top_k, e, h, inter) if wide_tiles < 0 else wide_tiles
-        act = moe_up_gate_silu(xs, expert_up_gate, rows, experts, top_k, act, form, up_gate_scale)
-        y = moe_down(act, expert_down, rows, experts, top_k, y, form, down_scale)
+        act = moe_up_gate_silu(xs, expert_up_gate, rows, experts, top_k, act, form, up_gate_scale, up_gate_bscale)
+        y = moe_down(act, expert_down, rows, experts, top_k, y, form, down_scale, down_bscale)
         moe_combine(y, w, out[t0:t0 + n])
         if tap is not None:
             tapped.append((ids, w))

@@ -447,7 +447,8 @@ class LlamaTransformerLayer:
             return moe_ffn(act, w.router, w.expert_up_gate, w.expert_down, cfg.num_experts_per_tok, cfg.norm_topk_prob,
                            self.skinny, tap=self.moe_tap, layer_id=self.layer_id,
                            wide_tiles=int(self.engine_config.moe_wide_tiles),
-                           up_gate_scale=w.expert_up_gate_scale, down_scale=w.expert_down_scale)
+                           up_gate_scale=w.expert_up_gate_scale, down_scale=w.expert_down_scale,
+                           up_gate_bscale=w.expert_up_gate_bscale, down_bscale=w.expert_down_bscale)
         if route.down is Down.ROWS:
             linear_rows_add(act, w.down_proj, residual_buf)
             return RawResidual(residual_buf)

@@ -92,7 +92,9 @@ class LlamaModel:
                 raise ValueError(f"max_loras > 0 cannot serve this {cfg.model_type} model: adapters on mixture-of-experts "
                                  "layers (their experts have no adapter update) are not built")
         # FP8 expert weights (EngineConfig.moe_weight_dtype = "fp8_e4m3"; csrc/moe_fp8.h): the expert stacks only
-        self.moe_fp8 = getattr(engine_config, "moe_weight_dtype", "auto") == "fp8_e4m3"
+        # (a block-scaled FP8 checkpoint — model_config.fp8_block, csrc/moe_fp8_block.h — is served with its own codes and
+        # scales under "auto" and under "fp8_e4m3" alike: nothing is quantised at load)
+        self.moe_fp8 = getattr(engine_config, "moe_weight_dtype", "auto") == "fp8_e4m3" and not cfg.fp8_block
         if self.moe_fp8:
             if not cfg.is_moe:
                 raise ValueError(f"moe_weight_dtype='fp8_e4m3' cannot serve this {cfg.model_type} model: it has no "

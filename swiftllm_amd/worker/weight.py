@@ -71,6 +71,43 @@ def expert_weight_specs(cfg, layer_id: int) -> List[tuple]:
     return out
 
 
+FP8 = torch.float8_e4m3fn
+FP8_BLOCK = 128
+
+
+def scale_spec(spec: WeightSpec) -> WeightSpec:
+    """The weight_scale_inv a block-scaled FP8 checkpoint stores next to a quantised `X.weight`: fp32, one per 128 x 128
+    block."""
+    assert spec.key.endswith(".weight") and len(spec.shape) == 2, spec.key
+    blocks = tuple((n + FP8_BLOCK - 1) // FP8_BLOCK for n in spec.shape)
+    return WeightSpec(spec.attr, spec.key[:-len(".weight")] + ".weight_scale_inv", blocks)
+
+
+def expert_scale_specs(cfg, layer_id: int) -> List[tuple]:
+    """Per expert tensor of expert_weight_specs, in its order: (the scale's WeightSpec, scale stack attribute, first row
+    inside that stack). expert_up_gate_bscale [E, 2 RB_I, KB_H] holds up's row blocks, then gate's (rows e * 2 RB_I and
+    e * 2 RB_I + RB_I); expert_down_bscale [E, RB_H, KB_I] (rows e * RB_H). csrc/moe_fp8_block.h."""
+    h, inter = cfg.hidden_size, cfg.moe_inter_dim
+    rb_i, rb_h = (inter + FP8_BLOCK - 1) // FP8_BLOCK, (h + FP8_BLOCK - 1) // FP8_BLOCK
+    out = []
+    for spec, attr, row in expert_weight_specs(cfg, layer_id):
+        if attr == "expert_up_gate":
+            e, off = divmod(row, 2 * inter)
+            out.append((scale_spec(spec), "expert_up_gate_bscale", e * 2 * rb_i + (rb_i if off else 0)))
+        else:
+            out.append((scale_spec(spec), "expert_down_bscale", (row // h) * rb_h))
+    return out
+
+
+def dequantise_blocks(codes: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """round_T(fp32(code) * scale[row // 128][col // 128]): one fp32 multiply, one rounding to `dtype`, in plain torch. What
+    a block-scaled FP8 checkpoint's NON-expert tensors (q/k/v/o_proj, a quantised router) become at load."""
+    rows, cols = codes.shape
+    assert codes.dtype == FP8 and scale.dtype == torch.float32, (codes.dtype, scale.dtype)
+    s = scale.to(codes.device).repeat_interleave(FP8_BLOCK, 0)[:rows].repeat_interleave(FP8_BLOCK, 1)[:, :cols]
+    return (codes.float() * s).to(dtype)
+
+
 def layer_family_specs(cfg, layer_id: int) -> List[WeightSpec]:
     """The per-layer tensors Llama does not have: Qwen3's per-head q/k RMSNorm weights, Qwen2's q/k/v_proj biases. They
     are vectors — not projection_tensors(), never packed."""
@@ -104,7 +141,21 @@ def _fill(obj, specs: List[WeightSpec], getter: Getter, dtype: torch.dtype, devi
         assert isinstance(t, torch.Tensor), f"Weight {spec.key} is not a tensor"
         assert tuple(t.shape) == tuple(spec.shape), \
             f"Shape of weight {spec.key} does not match: {tuple(t.shape)} vs {spec.shape}"
+        if t.dtype == FP8:                                  # a quantised tensor: with its scales, or not at all
+            t = dequantise_blocks(t.to(device), _scale_of(getter, spec), dtype)
         setattr(obj, spec.attr, t.to(device=device, dtype=dtype).contiguous())
+
+
+def _scale_of(getter: Getter, spec: WeightSpec) -> torch.Tensor:
+    """The weight_scale_inv of an FP8 tensor; raises when the checkpoint has none (codes are never cast without scales)."""
+    want = scale_spec(spec)
+    try:
+        scale = getter(want)
+    except Exception as e:      # (a missing key: KeyError from an index, the file reader's own error without one)
+        raise AssertionError(f"Weight {spec.key} is FP8 codes, but the checkpoint has no {want.key}") from e
+    assert tuple(scale.shape) == want.shape and scale.dtype == torch.float32, \
+        f"Scales {want.key} do not match: {tuple(scale.shape)} {scale.dtype} vs {want.shape} float32"
+    return scale
 
 
 class LlamaTransformerLayerWeight:
@@ -118,6 +169,9 @@ class LlamaTransformerLayerWeight:
         self.dtype = dtype
         # FP8 expert weights (csrc/moe_fp8.h): the two stacks are e4m3fn codes, with one fp32 scale per output row
         self.moe_fp8 = bool(moe_fp8)
+        # a block-scaled FP8 checkpoint (csrc/moe_fp8_block.h): the stacks are the checkpoint's codes, with its own scales
+        self.moe_fp8_block = bool(getattr(model_config, "fp8_block", False))
+        assert not (self.moe_fp8 and self.moe_fp8_block), "a block-scaled checkpoint is not re-quantised per row"
         self.qkv_proj = None
         self.q_norm = self.k_norm = None
         self.qkv_bias = self.q_bias = self.k_bias = self.v_bias = None
@@ -127,13 +181,19 @@ class LlamaTransformerLayerWeight:
         # is the order callers walk vars(layer) in when they re-initialise the weights from one seeded generator)
         self.router = self.expert_up_gate = self.expert_down = None
         self.expert_up_gate_scale = self.expert_down_scale = None      # fp32 [E, 2 I] / [E, H]: FP8 stacks only
+        # fp32 [E, 2 ceil(I / 128), ceil(H / 128)] / [E, ceil(H / 128), ceil(I / 128)]: block-scaled FP8 stacks only
+        self.expert_up_gate_bscale = self.expert_down_bscale = None
 
     def alloc_experts(self, device: torch.device):
         cfg = self.model_config
         e, h, inter = cfg.num_experts, cfg.hidden_size, cfg.moe_inter_dim
-        dtype = torch.float8_e4m3fn if self.moe_fp8 else self.dtype
+        dtype = FP8 if self.moe_fp8 or self.moe_fp8_block else self.dtype
         self.expert_up_gate = torch.empty((e, 2 * inter, h), dtype=dtype, device=device)
         self.expert_down = torch.empty((e, h, inter), dtype=dtype, device=device)
+        if self.moe_fp8_block:
+            rb_i, rb_h = (inter + FP8_BLOCK - 1) // FP8_BLOCK, (h + FP8_BLOCK - 1) // FP8_BLOCK
+            self.expert_up_gate_bscale = torch.ones((e, 2 * rb_i, rb_h), dtype=torch.float32, device=device)
+            self.expert_down_bscale = torch.ones((e, rb_h, rb_i), dtype=torch.float32, device=device)
         if self.moe_fp8:
             self.expert_up_gate_scale = torch.ones((e, 2 * inter), dtype=torch.float32, device=device)
             self.expert_down_scale = torch.ones((e, h), dtype=torch.float32, device=device)
@@ -141,15 +201,26 @@ class LlamaTransformerLayerWeight:
     def load_experts(self, getter: Getter, device: torch.device):
         """Every expert goes to its place inside the stacks: no second copy of the expert weights at any time. FP8: an
         expert's tensor is uploaded in 16 bits, its row scales are taken with torch and the quantiser writes its codes
-        straight into the byte stack (kernels/moe.py: row_scales, quantise_rows)."""
+        straight into the byte stack (kernels/moe.py: row_scales, quantise_rows). A block-scaled FP8 checkpoint: the
+        codes go byte for byte into the stack and each weight_scale_inv into its rows of the scale stack — no 16-bit
+        transient, no quantiser launch."""
         self.alloc_experts(device)
-        for spec, attr, row in expert_weight_specs(self.model_config, self.layer_id):
+        scales = expert_scale_specs(self.model_config, self.layer_id) if self.moe_fp8_block else None
+        for i, (spec, attr, row) in enumerate(expert_weight_specs(self.model_config, self.layer_id)):
             t = getter(spec)
             assert isinstance(t, torch.Tensor), f"Weight {spec.key} is not a tensor"
             assert tuple(t.shape) == tuple(spec.shape), \
                 f"Shape of weight {spec.key} does not match: {tuple(t.shape)} vs {spec.shape}"
             stack = getattr(self, attr)
             place = stack.view(-1, stack.shape[-1])[row:row + spec.shape[0]]
+            if self.moe_fp8_block:
+                assert t.dtype == FP8, f"Weight {spec.key} of a block-scaled FP8 checkpoint is {t.dtype}, not FP8 codes"
+                place.view(torch.uint8).copy_(t.view(torch.uint8))
+                sspec, sattr, srow = scales[i]
+                sstack = getattr(self, sattr)
+                sstack.view(-1, sstack.shape[-1])[srow:srow + sspec.shape[0]].copy_(_scale_of(getter, spec))
+                continue
+            assert t.dtype != FP8, f"Weight {spec.key} is FP8 codes, but config.json has no quantization_config"
             if not self.moe_fp8:
                 place.copy_(t)
                 continue
@@ -211,8 +282,12 @@ class LlamaWeight:
 
 
 # ---- checkpoint readers --------------------------------------------------------------------------
-def _dummy_getter(dtype: torch.dtype, device: torch.device) -> Getter:
+def _dummy_getter(dtype: torch.dtype, device: torch.device, fp8_experts: bool = False) -> Getter:
     def get(spec: WeightSpec) -> torch.Tensor:
+        if spec.key.endswith(".weight_scale_inv"):          # (a block-scaled FP8 model's experts: codes ~ U(-1, 1) / 1000)
+            return torch.full(spec.shape, 0.001, dtype=torch.float32, device=device)
+        if fp8_experts and ".experts." in spec.key:
+            return torch.empty(spec.shape, dtype=dtype, device=device).uniform_(-1.0, 1.0).to(FP8)
         return torch.empty(spec.shape, dtype=dtype, device=device).uniform_(-0.001, 0.001)
     return get
 
@@ -265,7 +340,7 @@ def _torch_bin_getter(model_path: str, device: torch.device) -> Getter:
 # FINAL position inside the destination tensor — the fused [q;k;v] and [up;gate] matrices are assembled in
 # place, no cat — with an async copy on a side stream. Falls back to the per-tensor path for anything unusual
 # (dtype conversion needed, non-safetensors checkpoints).
-_ST_DTYPES = {"F16": torch.float16, "BF16": torch.bfloat16, "F32": torch.float32}
+_ST_DTYPES = {"F16": torch.float16, "BF16": torch.bfloat16, "F32": torch.float32, "F8_E4M3": FP8}
 _STAGE_BYTES = 64 << 20
 _STAGE_BUFFERS = 8
 
@@ -319,6 +394,12 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
             plan.append((specs[attr].key, specs[attr].shape, t, 0))
         if moe and weight.moe_fp8:
             pass                                            # (quantised per expert behind the stream: load_weights)
+        elif moe and layer.moe_fp8_block:                   # the checkpoint's codes and scales, each at its final offset
+            layer.alloc_experts(device)
+            for (spec, attr, row), (sspec, sattr, srow) in zip(expert_weight_specs(cfg, layer.layer_id),
+                                                               expert_scale_specs(cfg, layer.layer_id)):
+                plan.append((spec.key, spec.shape, getattr(layer, attr), row))
+                plan.append((sspec.key, sspec.shape, getattr(layer, sattr), srow))
         elif moe:                                           # every expert at its final offset inside the two stacks
             layer.alloc_experts(device)
             for spec, attr, row in expert_weight_specs(cfg, layer.layer_id):
@@ -353,14 +434,27 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
                     setattr(layer, attr, t)
                     plan.append((specs[attr].key, specs[attr].shape, t, 0))
 
-    # validate before moving a byte
-    esize = torch.empty((), dtype=dtype).element_size()
-    for key, shape, _, _ in plan:
+    # validate before moving a byte. A tensor of FP8 codes bound for a 16-bit destination (a block-scaled FP8 checkpoint's
+    # q/k/v/o_proj, a quantised router) is dequantised with its scales behind the stream, never cast.
+    deferred, streamed = [], []
+    for item in plan:
+        key, shape, t, _ = item
         assert key in table, f"Weight {key} not found in the checkpoint"
         _, st_dtype, st_shape, b, e = table[key]
         assert tuple(st_shape) == tuple(shape), f"Shape of weight {key} does not match: {tuple(st_shape)} vs {shape}"
-        if _ST_DTYPES.get(st_dtype) != dtype or e - b != esize * int(np.prod(shape)):
+        if _ST_DTYPES.get(st_dtype) == FP8 and t.dtype != FP8:
+            deferred.append(item)
+        elif _ST_DTYPES.get(st_dtype) != t.dtype or e - b != t.element_size() * int(np.prod(shape)):
             return False    # needs a dtype conversion: per-tensor path
+        else:
+            streamed.append(item)
+    plan = streamed
+
+    def dequantise_deferred():
+        getter = _safetensors_getter(model_path, files, device)
+        for key, shape, t, row in deferred:
+            spec = WeightSpec("", key, tuple(shape))
+            t[row:row + shape[0]].copy_(dequantise_blocks(getter(spec), _scale_of(getter, spec), t.dtype))
 
     maps = {}
     def src_bytes(path):
@@ -372,7 +466,7 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
     chunks = []
     for key, shape, t, row in plan:
         path, _, _, b, e = table[key]
-        row_bytes = esize * (int(np.prod(shape[1:])) if len(shape) > 1 else 1)
+        row_bytes = t.element_size() * (int(np.prod(shape[1:])) if len(shape) > 1 else 1)
         dst = t.view(torch.uint8).view(-1)
         off = row * row_bytes
         for c in range(0, e - b, _STAGE_BYTES):
@@ -382,6 +476,7 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
     if device.type != "cuda":
         for path, b, n, dst, off in chunks:
             dst[off:off + n] = torch.from_numpy(np.array(src_bytes(path)[b:b + n], copy=True))
+        dequantise_deferred()
         return True
 
     stage = [torch.empty(_STAGE_BYTES, dtype=torch.uint8).pin_memory() for _ in range(_STAGE_BUFFERS)]
@@ -416,6 +511,7 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
             free_at[slot] = ev
             submit(slot)
     copy_stream.synchronize()
+    dequantise_deferred()
     return True
 
 
@@ -451,9 +547,11 @@ def load_weights(model_config, dtype: torch.dtype, model_path: str, use_dummy: b
                  streaming: bool = True, moe_weight_dtype: str = "auto") -> LlamaWeight:
     """Read (or synthesise) every weight of the model onto `device` in `dtype`. `streaming=False` forces the
     reference's tensor-by-tensor safetensors path. `moe_weight_dtype="fp8_e4m3"` (mixture-of-experts models): the expert
-    stacks are quantised per output row as they load (csrc/moe_fp8.h); everything else stays `dtype`."""
+    stacks are quantised per output row as they load (csrc/moe_fp8.h); everything else stays `dtype`. A block-scaled FP8
+    checkpoint (model_config.fp8_block; csrc/moe_fp8_block.h) is served with its own codes and scales under either value:
+    the expert codes and scales go to their stacks as they are, every other quantised tensor is dequantised once to `dtype`."""
     device = torch.device(device)
-    moe_fp8 = moe_weight_dtype == "fp8_e4m3"
+    moe_fp8 = moe_weight_dtype == "fp8_e4m3" and not getattr(model_config, "fp8_block", False)
     if model_version == "auto":
         if getattr(model_config, "model_type", "llama") != "llama":
             model_version = "llama3.2" if model_config.tie_word_embeddings else "llama"
@@ -461,7 +559,7 @@ def load_weights(model_config, dtype: torch.dtype, model_path: str, use_dummy: b
             model_version = detect_model_version(model_path)
     weight = LlamaWeight(model_config, dtype, model_version, moe_fp8)
     if use_dummy:
-        getter = _dummy_getter(dtype, device)
+        getter = _dummy_getter(dtype, device, bool(getattr(model_config, "fp8_block", False)))
     else:
         st_files = sorted(n for n in os.listdir(model_path) if n.endswith(".safetensors"))
         if st_files and streaming:

@@ -27,6 +27,11 @@ fp8:<geometry>  The 16-bit and the FP8 (e4m3, csrc/moe_fp8.hip) FFN of one layer
     where the chooser takes it): us of the whole FFN per dtype, the distinct active experts, TB/s over THEIR bytes (3 I H x
     2 or x 1 bytes, the scales' 4 (2 I + H) on top), `fp8_over_16` (medians) and `ranges_ok`: the FP8 range does not lie
     above the 16-bit range of the same run. The ideal is half the expert bytes; everything else in the FFN is unchanged.
+fp8_block:<geometry>  `fp8` with a third form in the same alternation: the block-scaled FP8 FFN (csrc/moe_fp8_block.hip; the
+    16-bit stacks quantised per 128 x 128 block with torch, as the published checkpoints are). Per T: us of bf16, per-row FP8
+    (`fp8`) and block FP8 (`fp8_block`: the form the chooser takes; from 128 tokens on also `fp8_block_rt0` / `fp8_block_rt2`,
+    the 16-row and the 2-tile form forced), `block_over_row` (medians) and `within_row_range`: the block median does not lie
+    above the per-row maximum of the same run by more than the per-row range.
 step_fp8  `step` for both expert dtypes in one process, the 16-bit model first.
 Each kernel figure is the median of `--repeats` runs of `--iters` back-to-back launches between two device events (a tenth
 of the iterations from 1024 tokens on), with the range [min, max].
@@ -52,7 +57,7 @@ QWEN3_30B_A3B = dict(model_type="qwen3_moe", hidden_act="silu", hidden_size=2048
                      head_dim=128, num_experts=128, num_experts_per_tok=8, norm_topk_prob=True, decoder_sparse_step=1,
                      mlp_only_layers=[], vocab_size=151936, max_position_embeddings=40960, rms_norm_eps=1e-6,
                      rope_theta=1000000.0, tie_word_embeddings=False)
-SECTION_TIMEOUT_S = {"ffn": 300, "wide": 420, "step": 420, "fp8": 300, "step_fp8": 840}
+SECTION_TIMEOUT_S = {"ffn": 300, "wide": 420, "step": 420, "fp8": 300, "fp8_block": 420, "step_fp8": 840}
 
 
 def _timed(fn, iters, repeats):
@@ -170,7 +175,18 @@ def wide_section(name, iters, repeats):
     return out
 
 
-def fp8_section(name, iters, repeats):
+def _block_quantise(w, halves):
+    """[E, halves * rows, k] 16-bit -> (codes, block scales [E, halves * ceil(rows / 128), ceil(k / 128)]), in plain torch."""
+    E, rows, k = w.shape[0], w.shape[1] // halves, w.shape[2]
+    rb, kb = -(-rows // 128), -(-k // 128)
+    p = torch.zeros((E, halves, rb * 128, kb * 128), dtype=torch.float32, device=w.device)
+    p[:, :, :rows, :k] = w.view(E, halves, rows, k).float()
+    scale = p.view(E, halves, rb, 128, kb, 128).abs().amax(dim=(3, 5)).clamp(min=1e-12) / 448.0
+    codes = (p.view(E, halves, rb, 128, kb, 128) / scale[:, :, :, None, :, None]).view(E, halves, rb * 128, kb * 128)
+    return codes[:, :, :rows, :k].to(torch.float8_e4m3fn).reshape(w.shape).contiguous(), scale.view(E, halves * rb, kb).contiguous()
+
+
+def fp8_section(name, iters, repeats, block=False):
     from swiftllm_amd.worker.kernels import moe as M
     H, I, E, k = GEOMETRIES[name]
     dt, dev = torch.bfloat16, "cuda"
@@ -186,6 +202,11 @@ def fp8_section(name, iters, repeats):
     forms = {"bf16": (lambda x: M.moe_ffn(x, router, *stacks16, k, True), 3 * I * H * 2),
              "fp8": (lambda x: M.moe_ffn(x, router, *stacks8, k, True, up_gate_scale=scales[0], down_scale=scales[1]),
                      3 * I * H + 4 * (2 * I + H))}
+    if block:
+        (ug8, ug_s), (dn8, dn_s) = _block_quantise(stacks16[0], 2), _block_quantise(stacks16[1], 1)
+        ffn_b = lambda x, wt=-1: M.moe_ffn(x, router, ug8, dn8, k, True, wide_tiles=wt, up_gate_bscale=ug_s,     # noqa: E731
+                                           down_bscale=dn_s)
+        forms["fp8_block"] = (ffn_b, 3 * I * H + 4 * (ug_s[0].numel() + dn_s[0].numel()))
     out = {}
     for T in (1, 8, 32, 128, 1024):
         n = iters if T < 1024 else max(2, iters // 10)
@@ -193,6 +214,9 @@ def fp8_section(name, iters, repeats):
         tap = []
         M.moe_ffn(x, router, *stacks16, k, True, tap=tap)
         active = int(torch.unique(tap[0][1]).numel())
+        if block and T >= 128:                              # both forms of the block kernels, forced
+            forms["fp8_block_rt0"] = (lambda x: ffn_b(x, 0), forms["fp8_block"][1])
+            forms["fp8_block_rt2"] = (lambda x: ffn_b(x, 2), forms["fp8_block"][1])
         runs = {f: [] for f in forms}
         for _ in range(repeats):                            # alternating: both dtypes see the same neighbours on the machine
             for f, (fn, _) in forms.items():
@@ -202,7 +226,11 @@ def fp8_section(name, iters, repeats):
             res[f] = dict(_summary(runs[f]), tb_s=round(active * expert_bytes / statistics.median(runs[f]) / 1e6, 3))
         res["fp8_over_16"] = round(res["fp8"]["median_us"] / res["bf16"]["median_us"], 3)
         res["ranges_ok"] = res["fp8"]["min_us"] <= res["bf16"]["max_us"]
-        out[f"fp8_{name}_t{T}"] = res
+        if block:
+            res["block_over_row"] = round(res["fp8_block"]["median_us"] / res["fp8"]["median_us"], 3)
+            res["within_row_range"] = (res["fp8_block"]["median_us"] - res["fp8"]["median_us"]
+                                       <= res["fp8"]["max_us"] - res["fp8"]["min_us"])
+        out[f"fp8{'_block' if block else ''}_{name}_t{T}"] = res
     return out
 
 
@@ -264,6 +292,7 @@ def main():
         res = (ffn_section(name, a.iters, a.repeats) if kind == "ffn" else
                wide_section(name, a.iters, a.repeats) if kind == "wide" else
                fp8_section(name, a.iters, a.repeats) if kind == "fp8" else
+               fp8_section(name, a.iters, a.repeats, block=True) if kind == "fp8_block" else
                step_section(("auto", "fp8_e4m3")) if kind == "step_fp8" else step_section())
         print("RESULT " + json.dumps(res), flush=True)
         return 0
