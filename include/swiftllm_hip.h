@@ -887,6 +887,35 @@ int swl_moe_down_fp8_block_wide(float *y, const void *act, const void *expert_do
                                 int32_t max_tiles, int32_t num_tokens, int32_t top_k, int32_t hidden, int32_t inter,
                                 int32_t num_experts, int32_t row_tiles, int32_t dtype, swl_stream_t stream);
 
+/* ---- block-scaled FP8 (e4m3) DENSE projections: the q/k/v, o, up/gate and down weights of a pre-quantised dense checkpoint,
+ * served with their own codes and scales (csrc/gemm_fp8_block.hip; the storage contract, the work split and the chain of one
+ * output element: csrc/gemm_fp8_block.h) -------------------------------------------------------------------------------------
+ * codes [N, K] e4m3fn bytes, N = seg0 + seg1 + seg2 rows of at most three row-wise concatenated segments (unused ones 0,
+ * behind the used ones), each a multiple of 16; K % 64 == 0 (anything else: SWL_ERR_UNSUPPORTED). bscale fp32
+ * [scale_rows, k_blocks] with scale_rows = sum of ceil(seg / 128) — every segment keeps its own scale rows — and
+ * k_blocks = ceil(K / 128) (anything else: SWL_ERR_BAD_ARG). x and the outputs are `dtype`; outputs are contiguous.
+ *   swl_gemm_fp8_block_supported: n % 16 == 0, k % 64 == 0, dtype f16 / bf16. Host only.
+ *   swl_gemm_fp8_block_choose_splits: the k slices the GEMMs cut (n output columns, k) into: a function of (n, k) alone, a
+ *     power of two <= 8 and <= ceil(k / 128); 0 for a shape that is not taken. Host only.
+ *   swl_gemm_fp8_block: y[num_tokens, N] = x . W^T, 1 <= num_tokens <= 64 (more: SWL_ERR_UNSUPPORTED). k_splits 0: the chooser's;
+ *     else a power of two <= 8 and <= k_blocks. With k_splits > 1 the workspace (16-byte aligned) holds
+ *     k_splits * num_tokens * N floats and a finishing kernel follows on the stream. No host synchronisation, no atomics. A
+ *     row's bits depend on that row of x and the weights only; a (shape, split) is run-to-run deterministic.
+ *   swl_gemm_fp8_block_silu_gate: act[num_tokens, inter] = up *_T silu(gate) over codes [2 inter, K] = [up ; gate]
+ *     (segments inter, inter); the workspace holds k_splits * num_tokens * 2 inter floats.
+ *   swl_fp8_block_dequant: out[N, K] = T(fp32(code) *_fp32 scale), one launch, for steps of more than 64 tokens. */
+int swl_gemm_fp8_block_supported(int32_t n, int32_t k, int32_t dtype);
+int swl_gemm_fp8_block_choose_splits(int32_t n, int32_t k);
+int swl_gemm_fp8_block(void *y, const void *x, const void *codes, const float *bscale, void *workspace,
+                       int64_t workspace_bytes, int32_t num_tokens, int32_t seg0, int32_t seg1, int32_t seg2, int32_t k,
+                       int32_t scale_rows, int32_t k_blocks, int64_t x_row_stride, int32_t k_splits, int32_t dtype,
+                       swl_stream_t stream);
+int swl_gemm_fp8_block_silu_gate(void *act, const void *x, const void *codes, const float *bscale, void *workspace,
+                                 int64_t workspace_bytes, int32_t num_tokens, int32_t inter, int32_t k, int32_t scale_rows,
+                                 int32_t k_blocks, int64_t x_row_stride, int32_t k_splits, int32_t dtype, swl_stream_t stream);
+int swl_fp8_block_dequant(void *out, const void *codes, const float *bscale, int32_t seg0, int32_t seg1, int32_t seg2,
+                          int32_t k, int32_t scale_rows, int32_t k_blocks, int32_t dtype, swl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,13 @@ _SPECIAL = {
                                              _I32, _I32, _P], _I32),
     "swl_moe_down_fp8_block_wide": ([_P, _P, _P, _P, _I32, _I32, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P],
                                     _I32),
+    # Block-scaled FP8 DENSE projections (csrc/gemm_fp8_block.hip; the contract: csrc/gemm_fp8_block.h; their own tests:
+    # tests/test_gemm_fp8_block_host.py): host arithmetic, the two weight-streaming GEMMs and the dequantiser
+    "swl_gemm_fp8_block_supported": ([_I32, _I32, _I32], _I32),
+    "swl_gemm_fp8_block_choose_splits": ([_I32, _I32], _I32),
+    "swl_gemm_fp8_block": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
+    "swl_gemm_fp8_block_silu_gate": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
+    "swl_fp8_block_dequant": ([_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

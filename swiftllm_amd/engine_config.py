@@ -93,6 +93,12 @@ class EngineConfig:
     # stacks take half the HBM and a step streams half the expert bytes. The router, attention and lm_head stay 16-bit.
     # Refused at load for a dense model.
     moe_weight_dtype: str = "auto"
+    # A DENSE block-scaled FP8 checkpoint (quantization_config: quant_method fp8, weight_block_size [128, 128]; Qwen3-8B-FP8
+    # and what the same quantiser wrote for Llama, Mistral, Qwen2.5). "auto": such a checkpoint is refused. "fp8_block": every
+    # layer's q/k/v, o, up/gate and down projections stay the checkpoint's own e4m3 codes and scales — one copy, no 16-bit
+    # twin — and every step runs the FP8 layer body (csrc/gemm_fp8_block.h). Refused for a 16-bit
+    # checkpoint, a mixture-of-experts model, with tuning={'decode_engine': True} and with max_loras > 0.
+    dense_weight_dtype: str = "auto"
     # Guided decoding (swiftllm_amd/guided, csrc/guided.hip): rows of the device pool of per-state
     # token bitmasks, one row (ceil(vocab / 32) int32 words: 16 KiB at Llama-3's vocabulary) per DFA state of a resident
     # guide. 0 (default): off — no pool, no new code path, and a guided request is answered with an error. > 0: load_weights
@@ -150,6 +156,7 @@ class EngineConfig:
     LORA_RANKS = (8, 16, 32, 64)
     MOE_WIDE_TILES = (-1, 0, 2, 4)
     MOE_WEIGHT_DTYPES = ("auto", "fp8_e4m3")
+    DENSE_WEIGHT_DTYPES = ("auto", "fp8_block")
 
     def __post_init__(self):
         # The reference takes block_size as a Triton constexpr (paged_attn.py:27) and its CLI default is 16
@@ -176,6 +183,8 @@ class EngineConfig:
                              f"kernels only), got {self.moe_wide_tiles}")
         if self.moe_weight_dtype not in self.MOE_WEIGHT_DTYPES:
             raise ValueError(f"moe_weight_dtype must be one of {list(self.MOE_WEIGHT_DTYPES)}, got {self.moe_weight_dtype!r}")
+        if self.dense_weight_dtype not in self.DENSE_WEIGHT_DTYPES:
+            raise ValueError(f"dense_weight_dtype must be one of {list(self.DENSE_WEIGHT_DTYPES)}, got {self.dense_weight_dtype!r}")
         if int(self.max_lora_rank) not in self.LORA_RANKS:
             raise ValueError(f"max_lora_rank must be one of {list(self.LORA_RANKS)}, got {self.max_lora_rank}")
         if self.lora_modules:
@@ -213,6 +222,12 @@ class EngineConfig:
         if int(self.max_loras) > 0 and self.decode_engine:
             raise ValueError("max_loras > 0 cannot be combined with tuning={'decode_engine': True}: the persistent "
                              "one-sequence decode step has no adapter path")
+        if self.dense_weight_dtype == "fp8_block" and self.decode_engine:
+            raise ValueError("dense_weight_dtype='fp8_block' cannot be combined with tuning={'decode_engine': True}: the "
+                             "persistent one-sequence decode step streams 16-bit weights only")
+        if self.dense_weight_dtype == "fp8_block" and int(self.max_loras) > 0:
+            raise ValueError("dense_weight_dtype='fp8_block' cannot be combined with max_loras > 0: the LoRA layer path "
+                             "multiplies 16-bit base weights only")
         if int(self.speculative_ngram) > 0 and self.kv_cache_dtype == "fp8_e4m3":
             raise ValueError("speculative_ngram > 0 cannot be combined with kv_cache_dtype='fp8_e4m3': the verify "
                              "attention kernel reads 16-bit KV pools only")
@@ -254,6 +269,9 @@ class EngineConfig:
         g.add_argument("--moe-weight-dtype", type=str, default="auto", choices=list(EngineConfig.MOE_WEIGHT_DTYPES),
                        help="Element type of a mixture-of-experts model's expert stacks: auto = the activation dtype, "
                             "fp8_e4m3 = 1 byte per element + one fp32 scale per output row, quantised at load")
+        g.add_argument("--dense-weight-dtype", type=str, default="auto", choices=list(EngineConfig.DENSE_WEIGHT_DTYPES),
+                       help="A dense block-scaled FP8 checkpoint: auto = refused, fp8_block = served from its own e4m3 codes "
+                            "and 128 x 128 block scales")
         g.add_argument("--speculative-ngram", type=int, default=0,
                        help="Prompt-lookup speculative decoding: n-gram drafts per sequence per step (0 = off)")
         g.add_argument("--speculative-max-batch", type=int, default=8,

@@ -29,7 +29,9 @@ class LlamaModelConfig:
     """LLaMA 1/2/3, Mistral, Qwen2 / Qwen2.5, dense Qwen3, Qwen3-MoE and Mixtral configuration. Attribute names follow the reference so
     layer/kernel code and user scripts that poke at `model.model_config` keep working."""
 
-    def __init__(self, model_config: dict):
+    def __init__(self, model_config: dict, dense_fp8: bool = False):
+        """`dense_fp8` (EngineConfig.dense_weight_dtype = "fp8_block"): accept a DENSE block-scaled FP8 checkpoint and serve
+        its layer projections from their own codes and scales (csrc/gemm_fp8_block.h); off, such a checkpoint is refused."""
         model_type = model_config["model_type"]
         if model_type in MOE_TYPES and model_type not in MOE_FAMILY:
             raise ValueError(f"model_type {model_type!r} is a mixture-of-experts variant with a shared expert next to the "
@@ -65,9 +67,14 @@ class LlamaModelConfig:
         # a pre-quantised checkpoint (quantization_config): only block-scaled FP8 — e4m3 codes with one fp32
         # weight_scale_inv per 128 x 128 block (csrc/moe_fp8_block.h) — is served, with its own codes and scales
         self.fp8_block = False
-        if model_config.get("quantization_config"):
-            self._init_quantisation(model_config["quantization_config"])
         self.q_size = self.num_q_heads * self.head_dim
+        if model_config.get("quantization_config"):
+            self._init_quantisation(model_config["quantization_config"], bool(dense_fp8))
+        elif dense_fp8:
+            raise ValueError(f"{model_type}: dense_weight_dtype 'fp8_block' serves a block-scaled FP8 checkpoint's own codes; "
+                             "this checkpoint has no quantization_config (16-bit checkpoints are not quantised at load)")
+        # a dense model whose layer projections are block-scaled FP8 codes (fp8_block is set with it)
+        self.dense_fp8 = bool(dense_fp8)
 
     @property
     def is_moe(self) -> bool:
@@ -105,7 +112,7 @@ class LlamaModelConfig:
                              "GEMMs are built for hidden_size % 64 == 0 and an intermediate size % 32 == 0 (16-column blocks "
                              "within a 65535-block grid)")
 
-    def _init_quantisation(self, q: dict):
+    def _init_quantisation(self, q: dict, dense_fp8: bool = False):
         """quantization_config: the block-scaled FP8 layout of transformers' fine-grained FP8 quantiser, or a refusal."""
         kind = self.model_type
         method, fmt, block = q.get("quant_method"), q.get("fmt", "e4m3"), q.get("weight_block_size")
@@ -121,9 +128,24 @@ class LlamaModelConfig:
         if q.get("activation_scheme", "dynamic") != "dynamic":
             raise ValueError(f"{kind}: quantization_config has activation_scheme {q['activation_scheme']!r}: stored input "
                              "scales belong to FP8 activations, which are not built (activations stay 16-bit)")
+        if self.is_moe and dense_fp8:
+            raise ValueError(f"{kind}: dense_weight_dtype 'fp8_block' is for dense models; a mixture-of-experts checkpoint "
+                             "is served with FP8 expert stacks under 'auto', its attention projections dequantised at load")
         if not self.is_moe:
-            raise ValueError(f"{kind}: a quantised dense model (no experts); block-scaled FP8 weights are built for the "
-                             "expert stacks of mixture-of-experts models only")
+            if not dense_fp8:
+                raise ValueError(f"{kind}: a quantised dense model (no experts); without dense_weight_dtype='fp8_block' "
+                                 "(--dense-weight-dtype fp8_block) block-scaled FP8 weights are served for the expert stacks "
+                                 "of mixture-of-experts models only")
+            kv = self.num_kv_heads * self.head_dim
+            if self.hidden_size % 64 or self.ffn_inter_dim % 64 or self.q_size % 64:
+                raise ValueError(f"{kind}: hidden_size {self.hidden_size}, intermediate_size {self.ffn_inter_dim}, q_size "
+                                 f"{self.q_size}; the block-scaled FP8 projections (swl_gemm_fp8_block_supported) walk 64 "
+                                 "codes a step and take multiples of 64 for all three")
+            if kv % 16:
+                raise ValueError(f"{kind}: num_kv_heads * head_dim = {kv}; the block-scaled FP8 projections take segments "
+                                 "that are multiples of 16 rows")
+            self.fp8_block = True
+            return
         if self.hidden_size % 64 or self.moe_inter_dim % 64:
             raise ValueError(f"{kind}: hidden_size {self.hidden_size}, expert intermediate size {self.moe_inter_dim}; the "
                              "block-scaled FP8 expert GEMMs (swl_moe_fp8_block_supported) walk 64 codes a step and take "
@@ -174,6 +196,6 @@ class LlamaModelConfig:
         return 2 * self.num_layers * self.num_kv_heads * self.head_dim * dtype.itemsize
 
     @staticmethod
-    def load_from_model_path(model_path: str) -> "LlamaModelConfig":
+    def load_from_model_path(model_path: str, dense_fp8: bool = False) -> "LlamaModelConfig":
         with open(os.path.join(model_path, "config.json"), "r", encoding="utf-8") as f:
-            return LlamaModelConfig(json.load(f))
+            return LlamaModelConfig(json.load(f), dense_fp8=dense_fp8)

@@ -144,6 +144,8 @@ def main():
                     help="element type of every replica's KV pools (api_server --kv-cache-dtype)")
     ap.add_argument("--moe-weight-dtype", default=None, choices=["auto", "fp8_e4m3"],
                     help="element type of every replica's expert stacks (api_server --moe-weight-dtype)")
+    ap.add_argument("--dense-weight-dtype", default=None, choices=["auto", "fp8_block"],
+                    help="every replica serves a dense block-scaled FP8 checkpoint (api_server --dense-weight-dtype)")
     # multi-LoRA serving: every replica loads the same adapters (a request's "lora" field is relayed like every field)
     ap.add_argument("--max-loras", type=int, default=None, help="adapter slots of every replica (api_server --max-loras)")
     ap.add_argument("--max-lora-rank", type=int, default=None, choices=[8, 16, 32, 64])
@@ -161,6 +163,8 @@ def main():
     if args.kv_cache_dtype is not None:
         passthrough = list(passthrough) + ["--kv-cache-dtype", args.kv_cache_dtype]
     passthrough = list(passthrough) + moe_passthrough(args.moe_weight_dtype)
+    if args.dense_weight_dtype is not None:
+        passthrough = list(passthrough) + ["--dense-weight-dtype", args.dense_weight_dtype]
     passthrough = list(passthrough) + lora_passthrough(args.max_loras, args.max_lora_rank, args.lora)
     procs = spawn_replicas(args.num_replicas, args.port, passthrough)
     router = ReplicaRouter([f"http://127.0.0.1:{args.port + 1 + i}" for i in range(args.num_replicas)])

@@ -27,6 +27,7 @@ Launches per layer by route (pure decode of m sequences unless said; default swi
 | PLAIN, PLAIN, QKV.ROTARY_THEN_STORE | plain_qkv, a prompt row (or the switches above off) | add_norm, q/k/v, prep, store, attention, o, add_norm, up_gate (+ silu), down |
 | SPLITK_FUSED (or PLAIN), MOE      | a mixture-of-experts layer (Qwen3-MoE, Mixtral)  | ... o, add_norm, router, route, align, up_gate_silu, down, combine (prompt steps: the six MoE launches per block of tokens) |
 | lora                              | some row names an adapter                        | the plain sequence with the adapter update after every projection |
+| dense_fp8                         | a dense block-scaled FP8 model, every step       | add_norm, qkv (FP8), rotary or prep, store, attention, o (FP8), add_norm, up_gate + SiLU (FP8), down (FP8): 9 (+ a finishing launch per projection whose K is split; more than 64 rows: dequantise + the library GEMM per projection) |
 
 "prep" is the one launch between the projections and the store: bias + per-head QK-norm + rotary (swl_qk_prep_rotary) for
 a model with a q/k/v bias or a QK-norm, swl_rotary for one that only decouples q_size from hidden (Mistral-Nemo).
@@ -54,6 +55,7 @@ from ..kernels.prefill_attn import prefill_attention, prefill_attention_paged
 from ..kernels.paged_attn import paged_attention, paged_attention_from_qkv_splitk, paged_attention_verify
 from ..kernels.silu_and_mul import silu_and_mul_inplace
 from ..kernels.lora import lora_apply
+from ..kernels.linear_fp8 import linear_fp8_block, linear_silu_gate_fp8_block
 from ..kernels.moe import moe_ffn
 
 # Where the row-owned projections win on MI355X (tools/gemm_rows_micro.py --layer, tools/rows_kernel_us.py): every
@@ -119,6 +121,7 @@ class LayerRoute(NamedTuple):
     o_ffn: OFfn
     down: Down
     lora: bool                  # the LoRA body: plain operators, an adapter update after every projection
+    dense_fp8: bool = False     # the block-scaled FP8 body: plain operators over the FP8 projections (kernels/linear_fp8.py)
 
 
 class StepFacts(NamedTuple):
@@ -155,10 +158,12 @@ class LayerFacts(NamedTuple):
     plain_qkv: bool = False
     # a mixture-of-experts FFN: the FFN norm ends in a tensor, the experts (kernels/moe.py) return one
     moe: bool = False
+    # a dense model whose projections are block-scaled FP8 codes (csrc/gemm_fp8_block.h): every step takes the FP8 body
+    dense_fp8: bool = False
 
 
 def layer_facts(engine_config, dtype, hidden: int, num_q_heads: int, head_dim: int, shapes: dict, packed, lib,
-                plain_qkv: bool = False, moe: bool = False) -> LayerFacts:
+                plain_qkv: bool = False, moe: bool = False, dense_fp8: bool = False) -> LayerFacts:
     """`shapes`: (N, K) of "qkv" (absent without the fused projection), "o", "up_gate", "down"; `packed`: the names that
     carry a packed twin; `lib`: the loaded library, asked for its host arithmetic only (split counts, shape support)."""
     def takes(name):            # the weight-streaming GEMMs take the shape
@@ -189,7 +194,7 @@ def layer_facts(engine_config, dtype, hidden: int, num_q_heads: int, head_dim: i
               and up_n % 128 == 0 and up_k % 128 == 0 and up_k <= _TINY_MAX_KC and splits("o", True) > 1 and splits("down", True) > 1),
         merge=("o" in packed and head_dim % 8 == 0 and shapes["o"][1] == num_q_heads * head_dim
                and splits("o", True) > 1 and chunked("o", splits("o", True))),
-        plain_qkv=bool(plain_qkv), moe=bool(moe))
+        plain_qkv=bool(plain_qkv), moe=bool(moe), dense_fp8=bool(dense_fp8))
 
 
 def decide_route(f: LayerFacts, s: StepFacts) -> LayerRoute:
@@ -198,8 +203,10 @@ def decide_route(f: LayerFacts, s: StepFacts) -> LayerRoute:
     attention = Attn.DECODE if not s.prefill else Attn.VERIFY if s.verify else Attn.PAGED if s.chunked else Attn.FRESH
     # rotary + KV store can be one launch; the projections' slabs can go to fused consumers; ... to the attention prologue
     # (a LoRA step takes none of the fused forms: they consume a projection's output before a delta could be added)
-    rope_store = not (s.lora or s.ignore_kvcache or f.kv_fp8 or f.plain_qkv) and s.positions and f.tuning.fuse_rope_kvstore
-    fast = f.skinny and not (s.lora or s.prefill) and s.m > 0 and f.tuning.fuse_splitk_consumers
+    # (... and neither does the FP8 body: its projections return whole tensors)
+    rope_store = (not (s.lora or s.ignore_kvcache or f.kv_fp8 or f.plain_qkv or f.dense_fp8) and s.positions
+                  and f.tuning.fuse_rope_kvstore)
+    fast = f.skinny and not (s.lora or s.prefill or f.dense_fp8) and s.m > 0 and f.tuning.fuse_splitk_consumers
     slab_attn = (fast and rope_store and f.fused_qkv and f.tuning.fuse_rope_into_attention and f.head_dim in (32, 64, 128)
                  and s.m <= 256)      # (batches the slab-producing GEMMs serve)
     # the 1/rms of a norm can be left to the consumer of the normalised activations: bfloat16, <= 32 sequences
@@ -238,7 +245,7 @@ def decide_route(f: LayerFacts, s: StepFacts) -> LayerRoute:
         o_ffn, down = OFfn.SPLITK_DEFERRED if defer and f.o_splits > 1 and f.fly_ffn else OFfn.SPLITK_FUSED, Down.SPLITK
     else:
         o_ffn, down = OFfn.PLAIN, Down.PLAIN
-    return LayerRoute(attn_norm, qkv, attention, piggyback, tiny and s.split and f.merge, o_ffn, down, s.lora)
+    return LayerRoute(attn_norm, qkv, attention, piggyback, tiny and s.split and f.merge, o_ffn, down, s.lora, f.dense_fp8)
 
 
 _INPUT = {torch.Tensor: Input.TENSOR, SplitKPartials: Input.SLABS, RawResidual: Input.RAW}
@@ -260,16 +267,17 @@ class LlamaTransformerLayer:
         the packed twins of the weights are rebuilt (LlamaModel.repack_decode_weights)."""
         cfg, w = self.model_config, self.weight
         self.moe = getattr(w, "expert_up_gate", None) is not None
+        self.dense_fp8 = bool(getattr(w, "dense_fp8", False))
         named = dict(qkv=w.qkv_proj, o=w.o_proj, up_gate=getattr(w, "up_gate_proj", None), down=getattr(w, "down_proj", None))
         # bias + QK-norm + rotary in one launch where the model has either (Qwen2 / Qwen3); otherwise swl_rotary
         self.qk_prep = getattr(w, "q_norm", None) is not None or getattr(w, "q_bias", None) is not None
-        self.facts = layer_facts(self.engine_config, w.o_proj.dtype, cfg.hidden_size, cfg.num_q_heads, cfg.head_dim,
+        self.facts = layer_facts(self.engine_config, w.attn_norm.dtype if self.dense_fp8 else w.o_proj.dtype, cfg.hidden_size, cfg.num_q_heads, cfg.head_dim,
                                  {**{name: tuple(t.shape) for name, t in named.items() if t is not None},
                                     **(dict(up_gate=tuple(w.expert_up_gate.shape[1:]), down=tuple(w.expert_down.shape[1:]))
                                        if self.moe else {})},
                                  {name for name, t in named.items() if getattr(t, "_swl_packed", None) is not None},
                                  _hip.load(), plain_qkv=self.qk_prep or cfg.num_q_heads * cfg.head_dim != cfg.hidden_size,
-                                 moe=self.moe)
+                                 moe=self.moe, dense_fp8=self.dense_fp8)
         self._routes = {}           # StepFacts -> LayerRoute
 
     def route(self, input_embds, st) -> LayerRoute:
@@ -319,6 +327,8 @@ class LlamaTransformerLayer:
         route = self.route(input_embds, infer_state)
         if route.lora:
             return self._forward_lora(route, input_embds, residual_buf, k_cache, v_cache, block_table, infer_state)
+        if route.dense_fp8:
+            return self._forward_dense_fp8(route, input_embds, residual_buf, k_cache, v_cache, block_table, infer_state)
         attn_out = self._norm_qkv_attention(route, input_embds, residual_buf, k_cache, v_cache, block_table, infer_state)
         return self._down_proj(route, self._o_proj_ffn(route, attn_out, residual_buf, infer_state), residual_buf)
 
@@ -495,3 +505,22 @@ class LlamaTransformerLayer:
         down = linear(act, w.down_proj, sk)
         lora_apply(act, down, groups.down_proj, batch)
         return down
+
+    def _forward_dense_fp8(self, route, x, residual_buf, k_cache, v_cache, block_table, st):
+        """The layer of a dense block-scaled FP8 model: norm, qkv, rotary (or bias + QK-norm + rotary), KV store, attention,
+        o, norm, up/gate + SiLU, down — every projection on the checkpoint's own codes (kernels/linear_fp8.py: the FP8 kernel
+        up to 64 rows, dequantise + the library GEMM beyond). Plain tensors in and out; no fused form runs here."""
+        cfg, ecfg, w = self.model_config, self.engine_config, self.weight
+        kv = cfg.num_kv_heads * cfg.head_dim
+        fused_add_rmsnorm_inplace(x, residual_buf, w.attn_norm, cfg.rms_norm_eps)
+        q, k, v = self._split_qkv(linear_fp8_block(x, w.qkv_proj, w.qkv_bscale, (cfg.q_size, kv, kv)))
+        self._rotary(q, k, v, st)
+        if route.qkv is QKV.ROTARY_THEN_STORE:
+            store_kvcache(k, v, k_cache, v_cache, block_table, cfg, ecfg, st, self.layer_id)
+        x = self._attn_out_like(x)
+        self._attention(route, q, k, v, x.view(-1, cfg.num_q_heads, cfg.head_dim), k_cache, v_cache, block_table, st)
+        q = k = v = None
+        attn_out = linear_fp8_block(x, w.o_proj, w.o_bscale, (cfg.hidden_size,))
+        fused_add_rmsnorm_inplace(attn_out, residual_buf, w.ffn_norm, cfg.rms_norm_eps)
+        act = linear_silu_gate_fp8_block(attn_out, w.up_gate_proj, w.up_gate_bscale, cfg.ffn_inter_dim)
+        return linear_fp8_block(act, w.down_proj, w.down_bscale, (cfg.hidden_size,))

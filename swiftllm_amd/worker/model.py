@@ -73,7 +73,10 @@ class LlamaModel:
     @torch.inference_mode()
     def __init__(self, engine_config: EngineConfig):
         self.engine_config = engine_config
-        self.model_config = LlamaModelConfig.load_from_model_path(engine_config.model_path)
+        # a dense block-scaled FP8 checkpoint is served from its own codes (EngineConfig.dense_weight_dtype = "fp8_block";
+        # csrc/gemm_fp8_block.h); the config refuses what that mode does not serve
+        self.dense_fp8 = getattr(engine_config, "dense_weight_dtype", "auto") == "fp8_block"
+        self.model_config = LlamaModelConfig.load_from_model_path(engine_config.model_path, dense_fp8=self.dense_fp8)
         self.dtype = _DTYPES[getattr(engine_config, "dtype", "float16")]
         self.device = torch.device("cuda")
         cfg = self.model_config
@@ -191,6 +194,13 @@ class LlamaModel:
                                    self.engine_config.use_dummy, device=self.device,
                                    fuse_qkv=getattr(self.engine_config, "fuse_qkv", False),
                                    moe_weight_dtype="fp8_e4m3" if self.moe_fp8 else "auto")
+        if self.dense_fp8:
+            # steps of more than 64 tokens multiply a 16-bit image of one projection at a time: ONE scratch tensor, sized for
+            # the largest projection, allocated here so that profile_num_blocks counts it
+            from .kernels.linear_fp8 import reserve_scratch
+            lw = self.weight.layers[0]
+            reserve_scratch(lw.o_proj.device, self.dtype,
+                            max(t.numel() for t in (lw.qkv_proj, lw.o_proj, lw.up_gate_proj, lw.down_proj)))
         self.repack_decode_weights()
         self._tune_routes()
         self._init_to_get_rotary()

@@ -99,6 +99,29 @@ def expert_scale_specs(cfg, layer_id: int) -> List[tuple]:
     return out
 
 
+# A dense block-scaled FP8 model (model_config.dense_fp8; csrc/gemm_fp8_block.h): the layer projections as the FP8 kernels
+# take them — (attribute of the codes, attribute of the scales, the checkpoint tensors concatenated row-wise: its segments)
+DENSE_FP8_PROJECTIONS = (("qkv_proj", "qkv_bscale", ("q_proj", "k_proj", "v_proj")), ("o_proj", "o_bscale", ("o_proj",)),
+                         ("up_gate_proj", "up_gate_bscale", ("up_proj", "gate_proj")), ("down_proj", "down_bscale", ("down_proj",)))
+
+
+def dense_fp8_plan(cfg, layer_id: int) -> List[tuple]:
+    """Per projection of DENSE_FP8_PROJECTIONS: (codes attribute, scales attribute, codes shape, scales shape, [(the
+    tensor's WeightSpec, its first row, its scales' WeightSpec, their first scale row)]). Every segment keeps its own scale
+    rows: segment s starts at the sum of ceil(rows / 128) of the segments before it."""
+    specs = {s.attr: s for s in layer_weight_specs(cfg, layer_id)}
+    out = []
+    for attr, sattr, parts in DENSE_FP8_PROJECTIONS:
+        row = srow = 0
+        placed = []
+        for part in parts:
+            spec, sspec = specs[part], scale_spec(specs[part])
+            placed.append((spec, row, sspec, srow))
+            row, srow = row + spec.shape[0], srow + sspec.shape[0]
+        out.append((attr, sattr, (row, specs[parts[0]].shape[1]), (srow, scale_spec(specs[parts[0]]).shape[1]), placed))
+    return out
+
+
 def dequantise_blocks(codes: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     """round_T(fp32(code) * scale[row // 128][col // 128]): one fp32 multiply, one rounding to `dtype`, in plain torch. What
     a block-scaled FP8 checkpoint's NON-expert tensors (q/k/v/o_proj, a quantised router) become at load."""
@@ -171,6 +194,10 @@ class LlamaTransformerLayerWeight:
         self.moe_fp8 = bool(moe_fp8)
         # a block-scaled FP8 checkpoint (csrc/moe_fp8_block.h): the stacks are the checkpoint's codes, with its own scales
         self.moe_fp8_block = bool(getattr(model_config, "fp8_block", False))
+        # ... of a DENSE model served with dense_weight_dtype "fp8_block" (csrc/gemm_fp8_block.h): qkv_proj, o_proj, up_gate_proj
+        # and down_proj are the checkpoint's codes, each with its scales (DENSE_FP8_PROJECTIONS)
+        self.dense_fp8 = bool(getattr(model_config, "dense_fp8", False))
+        self.moe_fp8_block = self.moe_fp8_block and not self.dense_fp8
         assert not (self.moe_fp8 and self.moe_fp8_block), "a block-scaled checkpoint is not re-quantised per row"
         self.qkv_proj = None
         self.q_norm = self.k_norm = None
@@ -183,6 +210,29 @@ class LlamaTransformerLayerWeight:
         self.expert_up_gate_scale = self.expert_down_scale = None      # fp32 [E, 2 I] / [E, H]: FP8 stacks only
         # fp32 [E, 2 ceil(I / 128), ceil(H / 128)] / [E, ceil(H / 128), ceil(I / 128)]: block-scaled FP8 stacks only
         self.expert_up_gate_bscale = self.expert_down_bscale = None
+        # fp32 [sum of ceil(segment rows / 128), ceil(K / 128)]: a dense block-scaled FP8 model only
+        self.qkv_bscale = self.o_bscale = self.up_gate_bscale = self.down_bscale = None
+
+    def alloc_dense_fp8(self, device: torch.device) -> List[tuple]:
+        """The code and scale tensors of the four projections; returns dense_fp8_plan."""
+        plan = dense_fp8_plan(self.model_config, self.layer_id)
+        for attr, sattr, shape, sshape, _ in plan:
+            setattr(self, attr, torch.empty(shape, dtype=FP8, device=device))
+            setattr(self, sattr, torch.empty(sshape, dtype=torch.float32, device=device))
+        return plan
+
+    def load_dense_fp8(self, getter: Getter, device: torch.device):
+        """The codes go byte for byte to their rows of the fused tensors, each weight_scale_inv to its scale rows."""
+        for attr, sattr, _, _, placed in self.alloc_dense_fp8(device):
+            codes, scales = getattr(self, attr), getattr(self, sattr)
+            for spec, row, sspec, srow in placed:
+                t = getter(spec)
+                assert isinstance(t, torch.Tensor) and tuple(t.shape) == tuple(spec.shape), \
+                    f"Shape of weight {spec.key} does not match: {tuple(getattr(t, 'shape', ()))} vs {spec.shape}"
+                assert t.dtype == FP8, (f"Weight {spec.key} of a block-scaled FP8 checkpoint is {t.dtype}, not FP8 codes with a "
+                                        f"{sspec.key}")
+                codes[row:row + spec.shape[0]].view(torch.uint8).copy_(t.view(torch.uint8))
+                scales[srow:srow + sspec.shape[0]].copy_(_scale_of(getter, spec))
 
     def alloc_experts(self, device: torch.device):
         cfg = self.model_config
@@ -237,6 +287,14 @@ class LlamaTransformerLayerWeight:
         self.q_bias, self.k_bias, self.v_bias = self.qkv_bias[:qs], self.qkv_bias[qs:qs + kv], self.qkv_bias[qs + kv:]
 
     def load(self, getter: Getter, device: torch.device, fuse_qkv: bool):
+        if self.dense_fp8:
+            _fill(self, [s for s in layer_weight_specs(self.model_config, self.layer_id) if not s.attr.endswith("_proj")],
+                  getter, self.dtype, device)
+            self.load_dense_fp8(getter, device)
+            if self.q_bias is not None:
+                self.qkv_bias = torch.cat((self.q_bias, self.k_bias, self.v_bias), dim=0).contiguous()
+                self.slice_qkv_bias()
+            return
         _fill(self, layer_weight_specs(self.model_config, self.layer_id), getter, self.dtype, device)
         if getattr(self.model_config, "num_experts", 0):
             self.load_experts(getter, device)
@@ -278,15 +336,15 @@ class LlamaWeight:
         for layer in self.layers:
             out += [getattr(layer, a, None) for a in ("qkv_proj", "q_proj", "k_proj", "v_proj", "o_proj",
                                                       "up_gate_proj", "down_proj")]
-        return [t for t in out if t is not None]
+        return [t for t in out if t is not None and t.dtype != FP8]     # (block-scaled FP8 codes have no packed twin)
 
 
 # ---- checkpoint readers --------------------------------------------------------------------------
-def _dummy_getter(dtype: torch.dtype, device: torch.device, fp8_experts: bool = False) -> Getter:
+def _dummy_getter(dtype: torch.dtype, device: torch.device, fp8_experts: bool = False, fp8_dense: bool = False) -> Getter:
     def get(spec: WeightSpec) -> torch.Tensor:
         if spec.key.endswith(".weight_scale_inv"):          # (a block-scaled FP8 model's experts: codes ~ U(-1, 1) / 1000)
             return torch.full(spec.shape, 0.001, dtype=torch.float32, device=device)
-        if fp8_experts and ".experts." in spec.key:
+        if (fp8_experts and ".experts." in spec.key) or (fp8_dense and spec.key.endswith("_proj.weight")):
             return torch.empty(spec.shape, dtype=dtype, device=device).uniform_(-1.0, 1.0).to(FP8)
         return torch.empty(spec.shape, dtype=dtype, device=device).uniform_(-0.001, 0.001)
     return get
@@ -388,6 +446,23 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
     for layer in weight.layers:
         specs = {s.attr: s for s in layer_weight_specs(cfg, layer.layer_id)}
         moe = "router" in specs
+        if layer.dense_fp8:
+            # a dense block-scaled FP8 layer: the four projections' codes and scales, each at its final rows of the fused
+            # tensors, and the 16-bit rest — norms, Qwen3's QK-norms, Qwen2's biases fused as the FP8 layer body takes them
+            for attr, sattr, _, _, placed in layer.alloc_dense_fp8(device):
+                for spec, row, sspec, srow in placed:
+                    plan.append((spec.key, spec.shape, getattr(layer, attr), row))
+                    plan.append((sspec.key, sspec.shape, getattr(layer, sattr), srow))
+            for attr in ("attn_norm", "ffn_norm", "q_norm", "k_norm"):
+                if attr in specs:
+                    setattr(layer, attr, dest(specs[attr].shape))
+                    plan.append((specs[attr].key, specs[attr].shape, getattr(layer, attr), 0))
+            if "q_bias" in specs:
+                layer.qkv_bias = dest((qs + 2 * kv,))
+                layer.slice_qkv_bias()
+                for attr, row in (("q_bias", 0), ("k_bias", qs), ("v_bias", qs + kv)):
+                    plan.append((specs[attr].key, specs[attr].shape, layer.qkv_bias, row))
+            continue
         for attr in ("attn_norm", "o_proj", "ffn_norm", "router" if moe else "down_proj"):
             t = dest(specs[attr].shape)
             setattr(layer, attr, t)
@@ -559,7 +634,8 @@ def load_weights(model_config, dtype: torch.dtype, model_path: str, use_dummy: b
             model_version = detect_model_version(model_path)
     weight = LlamaWeight(model_config, dtype, model_version, moe_fp8)
     if use_dummy:
-        getter = _dummy_getter(dtype, device, bool(getattr(model_config, "fp8_block", False)))
+        getter = _dummy_getter(dtype, device, bool(getattr(model_config, "fp8_block", False)),
+                               bool(getattr(model_config, "dense_fp8", False)))
     else:
         st_files = sorted(n for n in os.listdir(model_path) if n.endswith(".safetensors"))
         if st_files and streaming:
