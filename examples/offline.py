@@ -31,6 +31,8 @@ def main():
                     help="mixture-of-experts models: fp8_e4m3 quantises the expert stacks per output row at load")
     ap.add_argument("--dense-weight-dtype", default="auto", choices=["auto", "fp8_block"],
                     help="dense block-scaled FP8 checkpoints: fp8_block serves the checkpoint's own codes and scales")
+    ap.add_argument("--dense-fp8-wide", action="store_true",
+                    help="with --dense-weight-dtype fp8_block: steps of 65..192 tokens run the wide FP8 kernels")
     ap.add_argument("--speculative-ngram", type=int, default=0,
                     help="prompt-lookup speculative decoding: n-gram drafts per sequence per step (0 = off)")
     ap.add_argument("--max-loras", type=int, default=0, help="multi-LoRA serving: adapter slots (0 = off)")
@@ -51,6 +53,7 @@ def main():
                                 max_blocks_per_seq=2048, max_batch_size=16, max_tokens_in_batch=2048 * 16,
                                 dtype=args.dtype, use_hip_graph=True, kv_cache_dtype=args.kv_cache_dtype,
                                 moe_weight_dtype=args.moe_weight_dtype, dense_weight_dtype=args.dense_weight_dtype,
+                                dense_fp8_wide=args.dense_fp8_wide,
                                 speculative_ngram=args.speculative_ngram, max_loras=args.max_loras,
                                 max_lora_rank=args.max_lora_rank, lora_modules=args.lora,
                                 guided_max_states=1024 if args.guided_regex is not None else 0)

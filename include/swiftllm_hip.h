@@ -916,6 +916,24 @@ int swl_gemm_fp8_block_silu_gate(void *act, const void *x, const void *codes, co
 int swl_fp8_block_dequant(void *out, const void *codes, const float *bscale, int32_t seg0, int32_t seg1, int32_t seg2,
                           int32_t k, int32_t scale_rows, int32_t k_blocks, int32_t dtype, swl_stream_t stream);
 
+/* ---- the same projections for steps of up to 256 tokens (csrc/gemm_fp8_block_wide.hip): the storage contract, the chain of
+ * one output element, the argument lists and every refusal of the two entries above, with 1 <= num_tokens <= 256 (more:
+ * SWL_ERR_UNSUPPORTED). With the same k_splits a row's bits are those swl_gemm_fp8_block / _silu_gate write for that row.
+ *   swl_gemm_fp8_block_wide_choose_splits: what k_splits 0 means for these two entries. n is the number of WEIGHT rows the
+ *     launch streams (N; 2 inter for the SiLU-gate entry); a function of (n, k) alone, a power of two <= 8 and
+ *     <= ceil(k / 128); 0 for a shape that is not taken. Host only.
+ *   swl_gemm_fp8_block_wide: y[num_tokens, N] = x . W^T; workspace: k_splits * num_tokens * N floats when k_splits > 1.
+ *   swl_gemm_fp8_block_wide_silu_gate: act[num_tokens, inter] = up *_T silu(gate); k_splits * num_tokens * 2 inter floats. */
+int swl_gemm_fp8_block_wide_choose_splits(int32_t n, int32_t k);
+int swl_gemm_fp8_block_wide(void *y, const void *x, const void *codes, const float *bscale, void *workspace,
+                            int64_t workspace_bytes, int32_t num_tokens, int32_t seg0, int32_t seg1, int32_t seg2, int32_t k,
+                            int32_t scale_rows, int32_t k_blocks, int64_t x_row_stride, int32_t k_splits, int32_t dtype,
+                            swl_stream_t stream);
+int swl_gemm_fp8_block_wide_silu_gate(void *act, const void *x, const void *codes, const float *bscale, void *workspace,
+                                      int64_t workspace_bytes, int32_t num_tokens, int32_t inter, int32_t k,
+                                      int32_t scale_rows, int32_t k_blocks, int64_t x_row_stride, int32_t k_splits,
+                                      int32_t dtype, swl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

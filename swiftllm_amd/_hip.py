@@ -196,6 +196,10 @@ _SPECIAL = {
     "swl_gemm_fp8_block": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
     "swl_gemm_fp8_block_silu_gate": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
     "swl_fp8_block_dequant": ([_P, _P, _P, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _P], _I32),
+    # ... and their 65..256-token forms (csrc/gemm_fp8_block_wide.hip; tests/test_gemm_fp8_block_wide_host.py)
+    "swl_gemm_fp8_block_wide_choose_splits": ([_I32, _I32], _I32),
+    "swl_gemm_fp8_block_wide": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
+    "swl_gemm_fp8_block_wide_silu_gate": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

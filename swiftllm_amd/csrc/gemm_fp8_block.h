@@ -47,6 +47,7 @@
 // position or the other rows — and a launch of a given (shape, split) is run-to-run deterministic (no atomics).
 #pragma once
 
+#include "gemm_host.h"
 #include "moe_fp8_block.h"
 
 namespace swl {
@@ -91,6 +92,50 @@ inline bool gemm_fp8_segments_ok(const Fp8Segments &s) {
         ended |= s.rows[i] == 0;
     }
     return s.rows[0] > 0;
+}
+
+// The finishing kernel of a split launch: four neighbouring columns a thread, the slabs added in slice order.
+template <typename T, bool SILU>
+__global__ __launch_bounds__(256) void gemm_fp8_block_finish_kernel(T *__restrict__ out, const float *__restrict__ slabs, int ks,
+                                                                    int M, int n_out, int n_w) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int per_row = n_out / 4;
+    if (i >= static_cast<int64_t>(M) * per_row) return;
+    const int row = static_cast<int>(i / per_row), col = 4 * static_cast<int>(i % per_row);
+    const float *p = slabs + static_cast<int64_t>(row) * n_w + col;
+    const int64_t slab = static_cast<int64_t>(M) * n_w;
+    float4_t a = *reinterpret_cast<const float4_t *>(p), g = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (SILU) g = *reinterpret_cast<const float4_t *>(p + n_out);
+    for (int j = 1; j < ks; ++j) {
+        a += *reinterpret_cast<const float4_t *>(p + j * slab);
+        if constexpr (SILU) g += *reinterpret_cast<const float4_t *>(p + j * slab + n_out);
+    }
+    typedef T T4 __attribute__((ext_vector_type(4)));
+    T4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = SILU ? fp8_block_up_gate_act<T>(a[e], g[e]) : to_t<T>(a[e]);
+    *reinterpret_cast<T4 *>(out + static_cast<int64_t>(row) * n_out + col) = o;
+}
+
+// ---- host: what the entries of gemm_fp8_block.hip and gemm_fp8_block_wide.hip check alike ----
+inline bool splits_ok(int ks, int k) { return ks >= 1 && ks <= kGemmFp8MaxSplits && !(ks & (ks - 1)) && ks <= moe_fp8_blocks(k); }
+
+// What both GEMM entries check alike, in this order: counts (M == 0 leaves with SWL_OK), operands, shape, strides,
+// alignment (gemm_host.h), then the scale table's block counts, the split and the workspace. `a.N` is the number of output
+// columns, `n_w` of weight rows, `chosen` what the ENTRY'S OWN chooser answers for the shape (used where k_splits is 0).
+inline bool fp8_gemm_settled(const GemmArgs &a, const float *bscale, const Fp8Segments &seg, int n_w, int scale_rows,
+                             int k_blocks, int chosen, int &ks, int &rc) {
+    if ((rc = check_gemm_counts(a)) != SWL_OK || a.M == 0) return true;
+    if ((rc = check_gemm_operands(a)) != SWL_OK) return true;
+    if (!bscale) return rc = SWL_ERR_BAD_ARG, true;
+    if (a.M > a.max_m || !gemm_fp8_geometry_ok(a.K) || !gemm_fp8_segments_ok(seg)) return rc = SWL_ERR_UNSUPPORTED, true;
+    if ((rc = check_gemm_strides(a)) != SWL_OK || (rc = check_gemm_alignment(a)) != SWL_OK) return true;
+    if (scale_rows != fp8_segments_scale_rows(seg) || k_blocks != moe_fp8_blocks(a.K)) return rc = SWL_ERR_BAD_ARG, true;
+    ks = a.k_splits ? a.k_splits : chosen;
+    if (!splits_ok(ks, a.K)) return rc = SWL_ERR_BAD_ARG, true;
+    if (ks > 1 && (!a.workspace || a.workspace_bytes < static_cast<size_t>(ks) * a.M * n_w * sizeof(float)))
+        return rc = SWL_ERR_BAD_ARG, true;
+    return false;
 }
 
 } // namespace swl

@@ -10,7 +10,6 @@
 // With k_splits > 1 the streaming kernel writes fp32 slabs [k_splits][M][weight rows] into the caller's workspace and
 // gemm_fp8_block_finish_kernel, launched behind it on the same stream, adds them in slice order and runs the epilogue.
 #include "gemm_fp8_block.h"
-#include "gemm_host.h"
 
 namespace swl {
 
@@ -169,29 +168,6 @@ __global__ __launch_bounds__(kThreads) void gemm_fp8_block_kernel(T *__restrict_
         }
 }
 
-// The finishing kernel of a split launch: four neighbouring columns a thread, the slabs added in slice order.
-template <typename T, bool SILU>
-__global__ __launch_bounds__(256) void gemm_fp8_block_finish_kernel(T *__restrict__ out, const float *__restrict__ slabs, int ks,
-                                                                    int M, int n_out, int n_w) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    const int per_row = n_out / 4;
-    if (i >= static_cast<int64_t>(M) * per_row) return;
-    const int row = static_cast<int>(i / per_row), col = 4 * static_cast<int>(i % per_row);
-    const float *p = slabs + static_cast<int64_t>(row) * n_w + col;
-    const int64_t slab = static_cast<int64_t>(M) * n_w;
-    float4_t a = *reinterpret_cast<const float4_t *>(p), g = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (SILU) g = *reinterpret_cast<const float4_t *>(p + n_out);
-    for (int j = 1; j < ks; ++j) {
-        a += *reinterpret_cast<const float4_t *>(p + j * slab);
-        if constexpr (SILU) g += *reinterpret_cast<const float4_t *>(p + j * slab + n_out);
-    }
-    typedef T T4 __attribute__((ext_vector_type(4)));
-    T4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = SILU ? fp8_block_up_gate_act<T>(a[e], g[e]) : to_t<T>(a[e]);
-    *reinterpret_cast<T4 *>(out + static_cast<int64_t>(row) * n_out + col) = o;
-}
-
 // out[N, K] = T(fp32(code) *_fp32 scale): 8 codes a lane, so a wave's store instruction writes 1 KiB of one row's
 // contiguous bytes (K % 64 == 0: a wave never straddles rows unevenly, a lane never straddles a k block).
 template <typename T>
@@ -212,26 +188,6 @@ __global__ __launch_bounds__(256) void fp8_block_dequant_kernel(T *__restrict__ 
 }
 
 // ---- host ----
-inline bool splits_ok(int ks, int k) { return ks >= 1 && ks <= kGemmFp8MaxSplits && !(ks & (ks - 1)) && ks <= moe_fp8_blocks(k); }
-
-// What both GEMM entries check alike, in this order: counts (M == 0 leaves with SWL_OK), operands, shape, strides,
-// alignment (gemm_host.h), then the scale table's block counts, the split and the workspace. `a.N` is the number of output
-// columns, `n_w` of weight rows.
-inline bool fp8_gemm_settled(const GemmArgs &a, const float *bscale, const Fp8Segments &seg, int n_w, int scale_rows,
-                             int k_blocks, int &ks, int &rc) {
-    if ((rc = check_gemm_counts(a)) != SWL_OK || a.M == 0) return true;
-    if ((rc = check_gemm_operands(a)) != SWL_OK) return true;
-    if (!bscale) return rc = SWL_ERR_BAD_ARG, true;
-    if (a.M > a.max_m || !gemm_fp8_geometry_ok(a.K) || !gemm_fp8_segments_ok(seg)) return rc = SWL_ERR_UNSUPPORTED, true;
-    if ((rc = check_gemm_strides(a)) != SWL_OK || (rc = check_gemm_alignment(a)) != SWL_OK) return true;
-    if (scale_rows != fp8_segments_scale_rows(seg) || k_blocks != moe_fp8_blocks(a.K)) return rc = SWL_ERR_BAD_ARG, true;
-    ks = a.k_splits ? a.k_splits : swl_gemm_fp8_block_choose_splits(a.N, a.K);
-    if (!splits_ok(ks, a.K)) return rc = SWL_ERR_BAD_ARG, true;
-    if (ks > 1 && (!a.workspace || a.workspace_bytes < static_cast<size_t>(ks) * a.M * n_w * sizeof(float)))
-        return rc = SWL_ERR_BAD_ARG, true;
-    return false;
-}
-
 template <typename T, int NB>
 void launch_fp8_gemm(const GemmArgs &a, const float *bscale, const Fp8Segments &seg, int nb_stride, int ks, hipStream_t stream) {
     const dim3 grid((a.N / 16 + kGemmFp8Waves - 1) / kGemmFp8Waves, ks);
@@ -283,7 +239,7 @@ extern "C" int swl_gemm_fp8_block(void *y, const void *x, const void *codes, con
     swl::GemmArgs a{y, x, codes, workspace, static_cast<size_t>(workspace_bytes), num_tokens, n, k, x_row_stride, n, k_splits,
                     swl::kGemmFp8MaxM, swl::kFp8KStep};
     int ks = 0, rc = SWL_OK;
-    if (swl::fp8_gemm_settled(a, bscale, seg, n, scale_rows, k_blocks, ks, rc)) return rc;
+    if (swl::fp8_gemm_settled(a, bscale, seg, n, scale_rows, k_blocks, swl_gemm_fp8_block_choose_splits(n, k), ks, rc)) return rc;
     SWL_DISPATCH_DTYPE(dtype, T, { swl::launch_fp8_gemm<T, 1>(a, bscale, seg, 0, ks, static_cast<hipStream_t>(stream)); });
     return swl::check_launch();
 }
@@ -297,7 +253,7 @@ extern "C" int swl_gemm_fp8_block_silu_gate(void *act, const void *x, const void
     swl::GemmArgs a{act, x, codes, workspace, static_cast<size_t>(workspace_bytes), num_tokens, inter, k, x_row_stride, inter,
                     k_splits, swl::kGemmFp8MaxM, swl::kFp8KStep};
     int ks = 0, rc = SWL_OK;
-    if (swl::fp8_gemm_settled(a, bscale, seg, 2 * inter, scale_rows, k_blocks, ks, rc)) return rc;
+    if (swl::fp8_gemm_settled(a, bscale, seg, 2 * inter, scale_rows, k_blocks, swl_gemm_fp8_block_choose_splits(inter, k), ks, rc)) return rc;
     SWL_DISPATCH_DTYPE(dtype, T, { swl::launch_fp8_gemm<T, 2>(a, bscale, seg, inter, ks, static_cast<hipStream_t>(stream)); });
     return swl::check_launch();
 }

@@ -99,6 +99,10 @@ class EngineConfig:
     # twin — and every step runs the FP8 layer body (csrc/gemm_fp8_block.h). Refused for a 16-bit
     # checkpoint, a mixture-of-experts model, with tuning={'decode_engine': True} and with max_loras > 0.
     dense_weight_dtype: str = "auto"
+    # With dense_weight_dtype "fp8_block": steps of 65..192 tokens run the wide FP8 weight-streaming kernels
+    # (csrc/gemm_fp8_block_wide.hip) in place of dequantise + the library GEMM. False (default): every step launches what it
+    # always did. Refused without dense_weight_dtype "fp8_block".
+    dense_fp8_wide: bool = False
     # Guided decoding (swiftllm_amd/guided, csrc/guided.hip): rows of the device pool of per-state
     # token bitmasks, one row (ceil(vocab / 32) int32 words: 16 KiB at Llama-3's vocabulary) per DFA state of a resident
     # guide. 0 (default): off — no pool, no new code path, and a guided request is answered with an error. > 0: load_weights
@@ -222,6 +226,9 @@ class EngineConfig:
         if int(self.max_loras) > 0 and self.decode_engine:
             raise ValueError("max_loras > 0 cannot be combined with tuning={'decode_engine': True}: the persistent "
                              "one-sequence decode step has no adapter path")
+        if self.dense_fp8_wide and self.dense_weight_dtype != "fp8_block":
+            raise ValueError("dense_fp8_wide=True needs dense_weight_dtype='fp8_block': the wide FP8 kernels multiply a "
+                             "block-scaled FP8 checkpoint's codes, and no other model holds any")
         if self.dense_weight_dtype == "fp8_block" and self.decode_engine:
             raise ValueError("dense_weight_dtype='fp8_block' cannot be combined with tuning={'decode_engine': True}: the "
                              "persistent one-sequence decode step streams 16-bit weights only")
@@ -272,6 +279,9 @@ class EngineConfig:
         g.add_argument("--dense-weight-dtype", type=str, default="auto", choices=list(EngineConfig.DENSE_WEIGHT_DTYPES),
                        help="A dense block-scaled FP8 checkpoint: auto = refused, fp8_block = served from its own e4m3 codes "
                             "and 128 x 128 block scales")
+        g.add_argument("--dense-fp8-wide", action="store_true",
+                       help="With --dense-weight-dtype fp8_block: steps of 65..192 tokens run the wide FP8 kernels instead "
+                            "of dequantise + the library GEMM")
         g.add_argument("--speculative-ngram", type=int, default=0,
                        help="Prompt-lookup speculative decoding: n-gram drafts per sequence per step (0 = off)")
         g.add_argument("--speculative-max-batch", type=int, default=8,

@@ -146,6 +146,8 @@ def main():
                     help="element type of every replica's expert stacks (api_server --moe-weight-dtype)")
     ap.add_argument("--dense-weight-dtype", default=None, choices=["auto", "fp8_block"],
                     help="every replica serves a dense block-scaled FP8 checkpoint (api_server --dense-weight-dtype)")
+    ap.add_argument("--dense-fp8-wide", action="store_true",
+                    help="every replica runs the wide FP8 kernels at 65..192 tokens (api_server --dense-fp8-wide)")
     # multi-LoRA serving: every replica loads the same adapters (a request's "lora" field is relayed like every field)
     ap.add_argument("--max-loras", type=int, default=None, help="adapter slots of every replica (api_server --max-loras)")
     ap.add_argument("--max-lora-rank", type=int, default=None, choices=[8, 16, 32, 64])
@@ -165,6 +167,8 @@ def main():
     passthrough = list(passthrough) + moe_passthrough(args.moe_weight_dtype)
     if args.dense_weight_dtype is not None:
         passthrough = list(passthrough) + ["--dense-weight-dtype", args.dense_weight_dtype]
+    if args.dense_fp8_wide:
+        passthrough = list(passthrough) + ["--dense-fp8-wide"]
     passthrough = list(passthrough) + lora_passthrough(args.max_loras, args.max_lora_rank, args.lora)
     procs = spawn_replicas(args.num_replicas, args.port, passthrough)
     router = ReplicaRouter([f"http://127.0.0.1:{args.port + 1 + i}" for i in range(args.num_replicas)])

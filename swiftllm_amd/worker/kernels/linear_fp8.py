@@ -7,6 +7,9 @@ ceil(K / 128)] and `segments`, the row counts of the tensors it concatenates —
                               projection is dequantised into ONE scratch tensor (sized for the largest projection asked for so
                               far, fixed address) and the existing `linear` multiplies it (hipBLASLt). 64 is the kernel's
                               limit, not a tuned crossover.
+                              `wide=True` (the model passes it up to WIDE_ROUTED_MAX_M rows under
+                              EngineConfig.dense_fp8_wide): 65..256 rows run the wide weight-streaming FP8 kernel
+                              (csrc/gemm_fp8_block_wide.hip) instead; a row's bits are then the 64-row kernel's at the same split.
   linear_silu_gate_fp8_block  up * silu(gate) over [up ; gate] codes, no [M, 2 I] intermediate up to 64 rows; beyond, the
                               dequantising route and swl_silu_mul.
   dequantise_fp8_block        out[N, K] = T(fp32(code) * scale), bit-equal to worker/weight.py: dequantise_blocks.
@@ -21,6 +24,8 @@ from .silu_and_mul import silu_and_mul_inplace
 FP8 = torch.float8_e4m3fn
 BLOCK = 128
 MAX_M = 64          # swl_gemm_fp8_block: four token tiles
+WIDE_MAX_M = 256    # swl_gemm_fp8_block_wide: sixteen token tiles; what `wide=True` sends to it (the C entry's limit)
+WIDE_ROUTED_MAX_M = 192     # what EngineConfig.dense_fp8_wide routes to it: at 256 rows up/gate loses to the dequantising route
 MAX_SPLITS = 8
 _scratch = {}       # (device, dtype) -> the 16-bit image of the projection being multiplied by the dequantising route
 _retired = []       # outgrown ones stay allocated: captured hipGraphs may still replay against them
@@ -40,6 +45,11 @@ def supported(n: int, k: int, dtype: torch.dtype = torch.bfloat16) -> bool:
 
 def choose_splits(n_out: int, k: int) -> int:
     return int(_hip.load().swl_gemm_fp8_block_choose_splits(int(n_out), int(k)))
+
+
+def choose_splits_wide(weight_rows: int, k: int) -> int:
+    """The wide kernels' split for a launch that streams `weight_rows` rows of codes (N; 2 I for the SiLU-gate form)."""
+    return int(_hip.load().swl_gemm_fp8_block_wide_choose_splits(int(weight_rows), int(k)))
 
 
 def max_splits(k: int) -> int:
@@ -102,33 +112,36 @@ def dequantised(codes: torch.Tensor, bscale: torch.Tensor, segments, dtype: torc
     return dequantise_fp8_block(codes, bscale, segments, out)
 
 
-def linear_fp8_block(x: torch.Tensor, codes: torch.Tensor, bscale: torch.Tensor, segments, k_splits: int = 0) -> torch.Tensor:
+def linear_fp8_block(x: torch.Tensor, codes: torch.Tensor, bscale: torch.Tensor, segments, k_splits: int = 0,
+                     wide: bool = False) -> torch.Tensor:
     seg, n, k = _check(x, codes, bscale, segments)
     m = x.shape[0]
-    if m > MAX_M:
+    use_wide = wide and MAX_M < m <= WIDE_MAX_M
+    if m > MAX_M and not use_wide:
         return linear(x, dequantised(codes, bscale, segments, x.dtype))
     out = torch.empty((m, n), dtype=x.dtype, device=x.device)
-    ks = k_splits or choose_splits(n, k)
+    ks = k_splits or (choose_splits_wide(n, k) if use_wide else choose_splits(n, k))
     ws = _workspace(x.device, ks * m * n * 4) if ks > 1 and m else None
-    _hip.call("swl_gemm_fp8_block", _hip.ptr(out), _hip.ptr(x), _hip.ptr(codes), _hip.ptr(bscale), _hip.ptr(ws),
-              ws.numel() * 4 if ws is not None else 0, m, *seg, k, bscale.shape[0], bscale.shape[1], _row_stride(x), k_splits,
+    _hip.call("swl_gemm_fp8_block_wide" if use_wide else "swl_gemm_fp8_block", _hip.ptr(out), _hip.ptr(x), _hip.ptr(codes),
+              _hip.ptr(bscale), _hip.ptr(ws), ws.numel() * 4 if ws is not None else 0, m, *seg, k, bscale.shape[0], bscale.shape[1], _row_stride(x), k_splits,
               _hip.dtype_code(x.dtype), _hip.stream())
     return out
 
 
 def linear_silu_gate_fp8_block(x: torch.Tensor, codes: torch.Tensor, bscale: torch.Tensor, inter: int,
-                               k_splits: int = 0) -> torch.Tensor:
+                               k_splits: int = 0, wide: bool = False) -> torch.Tensor:
     inter = int(inter)
     _, n, k = _check(x, codes, bscale, (inter, inter))
     m = x.shape[0]
-    if m > MAX_M:
+    use_wide = wide and MAX_M < m <= WIDE_MAX_M
+    if m > MAX_M and not use_wide:
         up_gate = linear(x, dequantised(codes, bscale, (inter, inter), x.dtype))
         silu_and_mul_inplace(up_gate)
         return up_gate[:, :inter]
     act = torch.empty((m, inter), dtype=x.dtype, device=x.device)
-    ks = k_splits or choose_splits(inter, k)
+    ks = k_splits or (choose_splits_wide(n, k) if use_wide else choose_splits(inter, k))
     ws = _workspace(x.device, ks * m * n * 4) if ks > 1 and m else None
-    _hip.call("swl_gemm_fp8_block_silu_gate", _hip.ptr(act), _hip.ptr(x), _hip.ptr(codes), _hip.ptr(bscale), _hip.ptr(ws),
-              ws.numel() * 4 if ws is not None else 0, m, inter, k, bscale.shape[0], bscale.shape[1], _row_stride(x), k_splits,
+    _hip.call("swl_gemm_fp8_block_wide_silu_gate" if use_wide else "swl_gemm_fp8_block_silu_gate", _hip.ptr(act),
+              _hip.ptr(x), _hip.ptr(codes), _hip.ptr(bscale), _hip.ptr(ws), ws.numel() * 4 if ws is not None else 0, m, inter, k, bscale.shape[0], bscale.shape[1], _row_stride(x), k_splits,
               _hip.dtype_code(x.dtype), _hip.stream())
     return act

@@ -27,7 +27,7 @@ Launches per layer by route (pure decode of m sequences unless said; default swi
 | PLAIN, PLAIN, QKV.ROTARY_THEN_STORE | plain_qkv, a prompt row (or the switches above off) | add_norm, q/k/v, prep, store, attention, o, add_norm, up_gate (+ silu), down |
 | SPLITK_FUSED (or PLAIN), MOE      | a mixture-of-experts layer (Qwen3-MoE, Mixtral)  | ... o, add_norm, router, route, align, up_gate_silu, down, combine (prompt steps: the six MoE launches per block of tokens) |
 | lora                              | some row names an adapter                        | the plain sequence with the adapter update after every projection |
-| dense_fp8                         | a dense block-scaled FP8 model, every step       | add_norm, qkv (FP8), rotary or prep, store, attention, o (FP8), add_norm, up_gate + SiLU (FP8), down (FP8): 9 (+ a finishing launch per projection whose K is split; more than 64 rows: dequantise + the library GEMM per projection) |
+| dense_fp8                         | a dense block-scaled FP8 model, every step       | add_norm, qkv (FP8), rotary or prep, store, attention, o (FP8), add_norm, up_gate + SiLU (FP8), down (FP8): 9 (+ a finishing launch per projection whose K is split; more than 64 rows: dequantise + the library GEMM per projection — or, with dense_fp8_wide, the wide FP8 kernel up to 192 rows) |
 
 "prep" is the one launch between the projections and the store: bias + per-head QK-norm + rotary (swl_qk_prep_rotary) for
 a model with a q/k/v bias or a QK-norm, swl_rotary for one that only decouples q_size from hidden (Mistral-Nemo).
@@ -55,7 +55,7 @@ from ..kernels.prefill_attn import prefill_attention, prefill_attention_paged
 from ..kernels.paged_attn import paged_attention, paged_attention_from_qkv_splitk, paged_attention_verify
 from ..kernels.silu_and_mul import silu_and_mul_inplace
 from ..kernels.lora import lora_apply
-from ..kernels.linear_fp8 import linear_fp8_block, linear_silu_gate_fp8_block
+from ..kernels.linear_fp8 import WIDE_ROUTED_MAX_M, linear_fp8_block, linear_silu_gate_fp8_block
 from ..kernels.moe import moe_ffn
 
 # Where the row-owned projections win on MI355X (tools/gemm_rows_micro.py --layer, tools/rows_kernel_us.py): every
@@ -509,18 +509,20 @@ class LlamaTransformerLayer:
     def _forward_dense_fp8(self, route, x, residual_buf, k_cache, v_cache, block_table, st):
         """The layer of a dense block-scaled FP8 model: norm, qkv, rotary (or bias + QK-norm + rotary), KV store, attention,
         o, norm, up/gate + SiLU, down — every projection on the checkpoint's own codes (kernels/linear_fp8.py: the FP8 kernel
-        up to 64 rows, dequantise + the library GEMM beyond). Plain tensors in and out; no fused form runs here."""
+        up to 64 rows, dequantise + the library GEMM beyond; with EngineConfig.dense_fp8_wide the wide FP8 kernel up to
+        WIDE_ROUTED_MAX_M rows, the largest measured step at which all four projections beat that route). Plain tensors in and out; no fused form runs here."""
         cfg, ecfg, w = self.model_config, self.engine_config, self.weight
+        wide = ecfg.dense_fp8_wide and x.shape[0] <= WIDE_ROUTED_MAX_M
         kv = cfg.num_kv_heads * cfg.head_dim
         fused_add_rmsnorm_inplace(x, residual_buf, w.attn_norm, cfg.rms_norm_eps)
-        q, k, v = self._split_qkv(linear_fp8_block(x, w.qkv_proj, w.qkv_bscale, (cfg.q_size, kv, kv)))
+        q, k, v = self._split_qkv(linear_fp8_block(x, w.qkv_proj, w.qkv_bscale, (cfg.q_size, kv, kv), wide=wide))
         self._rotary(q, k, v, st)
         if route.qkv is QKV.ROTARY_THEN_STORE:
             store_kvcache(k, v, k_cache, v_cache, block_table, cfg, ecfg, st, self.layer_id)
         x = self._attn_out_like(x)
         self._attention(route, q, k, v, x.view(-1, cfg.num_q_heads, cfg.head_dim), k_cache, v_cache, block_table, st)
         q = k = v = None
-        attn_out = linear_fp8_block(x, w.o_proj, w.o_bscale, (cfg.hidden_size,))
+        attn_out = linear_fp8_block(x, w.o_proj, w.o_bscale, (cfg.hidden_size,), wide=wide)
         fused_add_rmsnorm_inplace(attn_out, residual_buf, w.ffn_norm, cfg.rms_norm_eps)
-        act = linear_silu_gate_fp8_block(attn_out, w.up_gate_proj, w.up_gate_bscale, cfg.ffn_inter_dim)
-        return linear_fp8_block(act, w.down_proj, w.down_bscale, (cfg.hidden_size,))
+        act = linear_silu_gate_fp8_block(attn_out, w.up_gate_proj, w.up_gate_bscale, cfg.ffn_inter_dim, wide=wide)
+        return linear_fp8_block(act, w.down_proj, w.down_bscale, (cfg.hidden_size,), wide=wide)

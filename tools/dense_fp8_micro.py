@@ -2,6 +2,7 @@
 the same shapes. Nothing here is asserted anywhere.
 
     python tools/dense_fp8_micro.py [--iters 200] [--repeats 5] [--sections gemm,step] [--out profiles/dense_fp8_micro.json]
+                                    [--ms 65,128,192,256] [--batches 128,256]
 
 Run without --child it starts one fresh child process per section, each under its own `timeout -k 10`, and stops at the first
 that fails (nothing more is started on the GPU after a fault or a time limit).
@@ -10,9 +11,13 @@ gemm  Llama-3-8B's four projections — qkv (6144, 4096), o (4096, 4096), up/gat
       with dummy weights in bfloat16 at M = 1, 8, 32, 64: us of the FP8 GEMM (`fp8`) and of the existing 16-bit route on a
       packed weight (`bf16`: linear(skinny=True) / linear_silu_gate), alternating in one process; TB/s of codes for `fp8`;
       `fp8_over_16` (medians; the ideal is 0.5). At M = 64 and 128 also the dequantise + library GEMM route (`dequant`).
+      Above 64 rows (--ms 65,128,192,256) also the wide FP8 kernel (`wide`, csrc/gemm_fp8_block_wide.hip: what
+      EngineConfig.dense_fp8_wide runs in place of `dequant`), with `wide_over_dequant`, `wide_over_16` and whether the
+      wide kernel's range of repeats lies wholly below the dequantising route's (`wide_wins`).
 step  A whole decode step at Llama-3-8B dimensions (32 layers, dummy weights, bfloat16, 1024-token contexts) on graph replay
-      at batch 1, 8, 32 and 128: host wall time per forward() — which ends in the copy of the sampled tokens to the host, so
-      the clock stops behind the step's last kernel — the bf16 model first, then the FP8 one, in one process.
+      at batch 1, 8, 32 and 128 (--batches): host wall time per forward() — which ends in the copy of the sampled tokens to the host, so
+      the clock stops behind the step's last kernel — the bf16 model first, then the FP8 one, then the FP8 one with
+      dense_fp8_wide (`fp8_block_wide`), in one process.
 Each kernel figure is the median of `--repeats` runs of `--iters` back-to-back launches between two device events, with the
 range [min, max]; the forms alternate inside every repeat.
 """
@@ -55,7 +60,7 @@ def _summary(runs):
     return {"median_us": round(statistics.median(runs), 2), "min_us": round(min(runs), 2), "max_us": round(max(runs), 2)}
 
 
-def gemm_section(iters, repeats):
+def gemm_section(iters, repeats, ms=(1, 8, 32, 64, 128)):
     from swiftllm_amd.worker.kernels import linear_fp8 as L
     from swiftllm_amd.worker.kernels.linear import linear, linear_silu_gate, pack_weight
     dt, dev = torch.bfloat16, "cuda"
@@ -68,7 +73,7 @@ def gemm_section(iters, repeats):
         codes = torch.empty((n, k), dtype=dt, device=dev).uniform_(-1.0, 1.0, generator=g).to(L.FP8)
         bscale = torch.full((L.scale_rows(segments), L.blocks(k)), 1e-3, dtype=torch.float32, device=dev)
         silu = name == "up_gate_silu"
-        for m in (1, 8, 32, 64, 128):
+        for m in ms:
             x = torch.randn((m, k), device=dev, generator=g).to(dt)
             forms = {}
 
@@ -87,6 +92,9 @@ def gemm_section(iters, repeats):
                         L.silu_and_mul_inplace(y)
                 forms["dequant"] = dequant
                 forms.setdefault("bf16", bf16)
+            if L.MAX_M < m <= L.WIDE_MAX_M:
+                forms["wide"] = ((lambda: L.linear_silu_gate_fp8_block(x, codes, bscale, segments[0], wide=True)) if silu else
+                                 (lambda: L.linear_fp8_block(x, codes, bscale, segments, wide=True)))
             runs = {f: [] for f in forms}
             for _ in range(repeats):
                 for f, fn in forms.items():
@@ -96,27 +104,33 @@ def gemm_section(iters, repeats):
                 res["fp8"]["codes_tb_s"] = round(n * k / res["fp8"]["median_us"] / 1e6, 3)
                 res["fp8_over_16"] = round(res["fp8"]["median_us"] / res["bf16"]["median_us"], 3)
                 res["k_splits"] = L.choose_splits(segments[0] if silu else n, k)
+            if "wide" in res:
+                res["wide"]["codes_tb_s"] = round(n * k / res["wide"]["median_us"] / 1e6, 3)
+                res["wide_over_dequant"] = round(res["wide"]["median_us"] / res["dequant"]["median_us"], 3)
+                res["wide_over_16"] = round(res["wide"]["median_us"] / res["bf16"]["median_us"], 3)
+                res["wide_wins"] = res["wide"]["max_us"] < res["dequant"]["min_us"]
+                res["wide_k_splits"] = L.choose_splits_wide(n, k)
             out[f"{name}_m{m}"] = res
     return out
 
 
-def step_section():
+def step_section(batches=(1, 8, 32, 128)):
     from swiftllm_amd import EngineConfig, LlamaModel
-    S, steps, batch_max, out = 1024, 32, 128, {}
-    for mode in ("bf16", "fp8_block"):
+    S, steps, batch_max, out = 1024, 32, max(batches), {}
+    for mode in ("bf16", "fp8_block", "fp8_block_wide"):
         path = tempfile.mkdtemp(prefix="swl_dense_fp8_micro_")
         with open(os.path.join(path, "config.json"), "w", encoding="utf-8") as f:
-            json.dump(dict(LLAMA3_8B, **({"quantization_config": QUANT} if mode == "fp8_block" else {})), f)
+            json.dump(dict(LLAMA3_8B, **({"quantization_config": QUANT} if mode != "bf16" else {})), f)
         max_len = S + steps + 80
         ec = EngineConfig(model_path=path, use_dummy=True, block_size=16, gpu_mem_utilization=0.9, num_cpu_blocks=0,
                           max_seqs_in_block_table=batch_max + 64, max_blocks_per_seq=max_len // 16 + 8, max_batch_size=batch_max,
                           max_tokens_in_batch=4096, dtype="bfloat16", use_hip_graph=True,
-                          dense_weight_dtype="fp8_block" if mode == "fp8_block" else "auto")
+                          dense_weight_dtype="fp8_block" if mode != "bf16" else "auto", dense_fp8_wide=mode == "fp8_block_wide")
         model = LlamaModel(ec)
         model.load_weights()
         model.init_kvcache_and_swap(batch_max * (max_len // 16 + 2) + 64)
         g = torch.Generator().manual_seed(1)
-        for batch in (1, 8, 32, 128):
+        for batch in batches:
             seqs, toks = list(range(batch)), []
             for s0 in range(0, batch, 4):                   # prompts in steps of 4 x 1024 tokens
                 part = seqs[s0:s0 + 4]
@@ -143,17 +157,20 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sections", default="gemm,step")
+    ap.add_argument("--ms", default="1,8,32,64,128", help="token counts of the gemm section")
+    ap.add_argument("--batches", default="1,8,32,128", help="batch sizes of the step section")
     ap.add_argument("--child", default="", help="(internal) run one section in this process")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if a.child:
         assert torch.cuda.is_available(), "needs a HIP device"
-        print("RESULT " + json.dumps(gemm_section(a.iters, a.repeats) if a.child == "gemm" else step_section()), flush=True)
+        ms, batches = [int(v) for v in a.ms.split(",")], [int(v) for v in a.batches.split(",")]
+        print("RESULT " + json.dumps(gemm_section(a.iters, a.repeats, ms) if a.child == "gemm" else step_section(batches)), flush=True)
         return 0
     merged = {"iters": a.iters, "repeats": a.repeats}
     for section in [s for s in a.sections.split(",") if s]:
         cmd = ["timeout", "-k", "10", str(SECTION_TIMEOUT_S[section]), sys.executable, os.path.abspath(__file__), "--child",
-               section, "--iters", str(a.iters), "--repeats", str(a.repeats)]
+               section, "--iters", str(a.iters), "--repeats", str(a.repeats), "--ms", a.ms, "--batches", a.batches]
         r = subprocess.run(cmd, capture_output=True, text=True)
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
         if r.returncode != 0 or not lines:
