@@ -934,6 +934,38 @@ int swl_gemm_fp8_block_wide_silu_gate(void *act, const void *x, const void *code
                                       int32_t scale_rows, int32_t k_blocks, int64_t x_row_stride, int32_t k_splits,
                                       int32_t dtype, swl_stream_t stream);
 
+/* ---- dense projections of a 16-bit checkpoint on per-row FP8 (e4m3fn) weights, quantised at load into PACKED codes
+ * (csrc/gemm_fp8_row.hip; the contract, the packed order, the work split and the chain of one output element:
+ * csrc/gemm_fp8_row.h). A projection is codes (N x K bytes: 16-row x 64-k tiles of 1 KiB, tile (nt, kt) at byte
+ * 1024 * (nt * K / 64 + kt), lane i16 + 16 q's 16 codes at byte 16 * lane) and scale fp32 [N] (16-byte aligned); the weight
+ * means fp32(code) * scale[row]. N % 16 == 0 and K % 64 == 0 (anything else: SWL_ERR_UNSUPPORTED). x and the outputs are
+ * `dtype`; outputs are contiguous.
+ *   swl_gemm_fp8_row_supported: n % 16 == 0, k % 64 == 0, dtype f16 / bf16. Host only.
+ *   swl_gemm_fp8_row_choose_splits: the k slices the GEMMs cut (n output columns, k) into: a function of (n, k) alone, a power
+ *     of two <= 8 that leaves a slice at least 512 k; 0 for a shape that is not taken. Host only.
+ *   swl_gemm_fp8_row_quantise_pack: codes = pack(RNE_e4m3(clamp(fp32(w) * inv_scale[row], -448, 448))) from the 16-bit
+ *     row-major w[n, k], one launch.
+ *   swl_gemm_fp8_row: y[num_tokens, N] = T((x . codes^T) *_fp32 scale), 1 <= num_tokens <= 64 (more: SWL_ERR_UNSUPPORTED).
+ *     k_splits 0: the chooser's; else a power of two <= 8 and <= K / 64. With k_splits > 1 the workspace (16-byte aligned)
+ *     holds k_splits * num_tokens * N floats and a finishing kernel follows on the stream. No host synchronisation, no
+ *     atomics. A row's bits depend on that row of x and the weights only; a (shape, split) is run-to-run deterministic.
+ *   swl_gemm_fp8_row_silu_gate: act[num_tokens, inter] = up *_T silu(gate) over codes of [2 inter, K] = [up ; gate]; the
+ *     workspace holds k_splits * num_tokens * 2 inter floats.
+ *   swl_fp8_row_dequant: out[N, K] = T(fp32(code) *_fp32 scale[row]), row-major, one launch: the unpacking kernel, for steps
+ *     of more than 64 tokens. */
+int swl_gemm_fp8_row_supported(int32_t n, int32_t k, int32_t dtype);
+int swl_gemm_fp8_row_choose_splits(int32_t n, int32_t k);
+int swl_gemm_fp8_row_quantise_pack(void *codes, const void *w, const float *inv_scale, int32_t n, int32_t k, int32_t dtype,
+                                   swl_stream_t stream);
+int swl_gemm_fp8_row(void *y, const void *x, const void *codes, const float *scale, void *workspace, int64_t workspace_bytes,
+                     int32_t num_tokens, int32_t n, int32_t k, int64_t x_row_stride, int32_t k_splits, int32_t dtype,
+                     swl_stream_t stream);
+int swl_gemm_fp8_row_silu_gate(void *act, const void *x, const void *codes, const float *scale, void *workspace,
+                               int64_t workspace_bytes, int32_t num_tokens, int32_t inter, int32_t k, int64_t x_row_stride,
+                               int32_t k_splits, int32_t dtype, swl_stream_t stream);
+int swl_fp8_row_dequant(void *out, const void *codes, const float *scale, int32_t n, int32_t k, int32_t dtype,
+                        swl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,6 +200,15 @@ _SPECIAL = {
     "swl_gemm_fp8_block_wide_choose_splits": ([_I32, _I32], _I32),
     "swl_gemm_fp8_block_wide": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
     "swl_gemm_fp8_block_wide_silu_gate": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
+    # Per-row FP8 DENSE projections of a 16-bit checkpoint, packed codes (csrc/gemm_fp8_row.hip; the contract:
+    # csrc/gemm_fp8_row.h; their own tests: tests/test_gemm_fp8_row_host.py): host arithmetic, the quantising packer, the two
+    # weight-streaming GEMMs and the unpacking dequantiser
+    "swl_gemm_fp8_row_supported": ([_I32, _I32, _I32], _I32),
+    "swl_gemm_fp8_row_choose_splits": ([_I32, _I32], _I32),
+    "swl_gemm_fp8_row_quantise_pack": ([_P, _P, _P, _I32, _I32, _I32, _P], _I32),
+    "swl_gemm_fp8_row": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
+    "swl_gemm_fp8_row_silu_gate": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
+    "swl_fp8_row_dequant": ([_P, _P, _P, _I32, _I32, _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

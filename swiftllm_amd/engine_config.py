@@ -98,6 +98,11 @@ class EngineConfig:
     # layer's q/k/v, o, up/gate and down projections stay the checkpoint's own e4m3 codes and scales — one copy, no 16-bit
     # twin — and every step runs the FP8 layer body (csrc/gemm_fp8_block.h). Refused for a 16-bit
     # checkpoint, a mixture-of-experts model, with tuning={'decode_engine': True} and with max_loras > 0.
+    # "fp8_e4m3": a 16-BIT dense checkpoint's layer projections are quantised at load, per output row, into packed e4m3 codes
+    # (csrc/gemm_fp8_row.h) — half the weight bytes, the same FP8 layer body; embedding, lm_head and
+    # norms stay 16-bit. Refused for a checkpoint that has a quantization_config (serve it with "fp8_block"), a
+    # mixture-of-experts model (moe_weight_dtype), with tuning={'decode_engine': True}, with max_loras > 0 and with
+    # dense_fp8_wide.
     dense_weight_dtype: str = "auto"
     # With dense_weight_dtype "fp8_block": steps of 65..192 tokens run the wide FP8 weight-streaming kernels
     # (csrc/gemm_fp8_block_wide.hip) in place of dequantise + the library GEMM. False (default): every step launches what it
@@ -160,7 +165,7 @@ class EngineConfig:
     LORA_RANKS = (8, 16, 32, 64)
     MOE_WIDE_TILES = (-1, 0, 2, 4)
     MOE_WEIGHT_DTYPES = ("auto", "fp8_e4m3")
-    DENSE_WEIGHT_DTYPES = ("auto", "fp8_block")
+    DENSE_WEIGHT_DTYPES = ("auto", "fp8_block", "fp8_e4m3")
 
     def __post_init__(self):
         # The reference takes block_size as a Triton constexpr (paged_attn.py:27) and its CLI default is 16
@@ -229,11 +234,11 @@ class EngineConfig:
         if self.dense_fp8_wide and self.dense_weight_dtype != "fp8_block":
             raise ValueError("dense_fp8_wide=True needs dense_weight_dtype='fp8_block': the wide FP8 kernels multiply a "
                              "block-scaled FP8 checkpoint's codes, and no other model holds any")
-        if self.dense_weight_dtype == "fp8_block" and self.decode_engine:
-            raise ValueError("dense_weight_dtype='fp8_block' cannot be combined with tuning={'decode_engine': True}: the "
+        if self.dense_weight_dtype != "auto" and self.decode_engine:
+            raise ValueError(f"dense_weight_dtype={self.dense_weight_dtype!r} cannot be combined with tuning={{'decode_engine': True}}: the "
                              "persistent one-sequence decode step streams 16-bit weights only")
-        if self.dense_weight_dtype == "fp8_block" and int(self.max_loras) > 0:
-            raise ValueError("dense_weight_dtype='fp8_block' cannot be combined with max_loras > 0: the LoRA layer path "
+        if self.dense_weight_dtype != "auto" and int(self.max_loras) > 0:
+            raise ValueError(f"dense_weight_dtype={self.dense_weight_dtype!r} cannot be combined with max_loras > 0: the LoRA layer path "
                              "multiplies 16-bit base weights only")
         if int(self.speculative_ngram) > 0 and self.kv_cache_dtype == "fp8_e4m3":
             raise ValueError("speculative_ngram > 0 cannot be combined with kv_cache_dtype='fp8_e4m3': the verify "
@@ -278,7 +283,8 @@ class EngineConfig:
                             "fp8_e4m3 = 1 byte per element + one fp32 scale per output row, quantised at load")
         g.add_argument("--dense-weight-dtype", type=str, default="auto", choices=list(EngineConfig.DENSE_WEIGHT_DTYPES),
                        help="A dense block-scaled FP8 checkpoint: auto = refused, fp8_block = served from its own e4m3 codes "
-                            "and 128 x 128 block scales")
+                            "and 128 x 128 block scales. A dense 16-bit checkpoint: fp8_e4m3 = layer projections quantised at "
+                            "load, 1 byte per element + one fp32 scale per output row")
         g.add_argument("--dense-fp8-wide", action="store_true",
                        help="With --dense-weight-dtype fp8_block: steps of 65..192 tokens run the wide FP8 kernels instead "
                             "of dequantise + the library GEMM")

@@ -56,6 +56,7 @@ from ..kernels.paged_attn import paged_attention, paged_attention_from_qkv_split
 from ..kernels.silu_and_mul import silu_and_mul_inplace
 from ..kernels.lora import lora_apply
 from ..kernels.linear_fp8 import WIDE_ROUTED_MAX_M, linear_fp8_block, linear_silu_gate_fp8_block
+from ..kernels.linear_fp8_row import linear_fp8_row, linear_silu_gate_fp8_row
 from ..kernels.moe import moe_ffn
 
 # Where the row-owned projections win on MI355X (tools/gemm_rows_micro.py --layer, tools/rows_kernel_us.py): every
@@ -121,7 +122,7 @@ class LayerRoute(NamedTuple):
     o_ffn: OFfn
     down: Down
     lora: bool                  # the LoRA body: plain operators, an adapter update after every projection
-    dense_fp8: bool = False     # the block-scaled FP8 body: plain operators over the FP8 projections (kernels/linear_fp8.py)
+    dense_fp8: bool = False     # the FP8 body (block-scaled or per-row codes): plain operators over the FP8 projections (kernels/linear_fp8.py)
 
 
 class StepFacts(NamedTuple):
@@ -267,7 +268,9 @@ class LlamaTransformerLayer:
         the packed twins of the weights are rebuilt (LlamaModel.repack_decode_weights)."""
         cfg, w = self.model_config, self.weight
         self.moe = getattr(w, "expert_up_gate", None) is not None
-        self.dense_fp8 = bool(getattr(w, "dense_fp8", False))
+        # the FP8 layer body: a block-scaled checkpoint's own codes, or a 16-bit checkpoint's packed per-row codes
+        self.dense_fp8_row = bool(getattr(w, "dense_fp8_row", False))
+        self.dense_fp8 = bool(getattr(w, "dense_fp8", False)) or self.dense_fp8_row
         named = dict(qkv=w.qkv_proj, o=w.o_proj, up_gate=getattr(w, "up_gate_proj", None), down=getattr(w, "down_proj", None))
         # bias + QK-norm + rotary in one launch where the model has either (Qwen2 / Qwen3); otherwise swl_rotary
         self.qk_prep = getattr(w, "q_norm", None) is not None or getattr(w, "q_bias", None) is not None
@@ -507,22 +510,32 @@ class LlamaTransformerLayer:
         return down
 
     def _forward_dense_fp8(self, route, x, residual_buf, k_cache, v_cache, block_table, st):
-        """The layer of a dense block-scaled FP8 model: norm, qkv, rotary (or bias + QK-norm + rotary), KV store, attention,
+        """The layer of a dense FP8 model — a block-scaled checkpoint's own codes, or a 16-bit checkpoint's packed per-row
+        codes (kernels/linear_fp8_row.py: the FP8 kernel up to 64 rows, dequantise + the library GEMM beyond) —: norm, qkv, rotary (or bias + QK-norm + rotary), KV store, attention,
         o, norm, up/gate + SiLU, down — every projection on the checkpoint's own codes (kernels/linear_fp8.py: the FP8 kernel
         up to 64 rows, dequantise + the library GEMM beyond; with EngineConfig.dense_fp8_wide the wide FP8 kernel up to
         WIDE_ROUTED_MAX_M rows, the largest measured step at which all four projections beat that route). Plain tensors in and out; no fused form runs here."""
         cfg, ecfg, w = self.model_config, self.engine_config, self.weight
         wide = ecfg.dense_fp8_wide and x.shape[0] <= WIDE_ROUTED_MAX_M
         kv = cfg.num_kv_heads * cfg.head_dim
+        if self.dense_fp8_row:      # the projections by the kind of weights the layer holds: packed per-row codes
+            qkv = lambda a: linear_fp8_row(a, w.qkv_proj, w.qkv_scale)                          # noqa: E731
+            o = lambda a: linear_fp8_row(a, w.o_proj, w.o_scale)                                # noqa: E731
+            up_gate = lambda a: linear_silu_gate_fp8_row(a, w.up_gate_proj, w.up_gate_scale)    # noqa: E731
+            down = lambda a: linear_fp8_row(a, w.down_proj, w.down_scale)                       # noqa: E731
+        else:                       # ... or a block-scaled checkpoint's own codes
+            qkv = lambda a: linear_fp8_block(a, w.qkv_proj, w.qkv_bscale, (cfg.q_size, kv, kv), wide=wide)              # noqa: E731
+            o = lambda a: linear_fp8_block(a, w.o_proj, w.o_bscale, (cfg.hidden_size,), wide=wide)                      # noqa: E731
+            up_gate = lambda a: linear_silu_gate_fp8_block(a, w.up_gate_proj, w.up_gate_bscale, cfg.ffn_inter_dim, wide=wide)   # noqa: E731
+            down = lambda a: linear_fp8_block(a, w.down_proj, w.down_bscale, (cfg.hidden_size,), wide=wide)             # noqa: E731
         fused_add_rmsnorm_inplace(x, residual_buf, w.attn_norm, cfg.rms_norm_eps)
-        q, k, v = self._split_qkv(linear_fp8_block(x, w.qkv_proj, w.qkv_bscale, (cfg.q_size, kv, kv), wide=wide))
+        q, k, v = self._split_qkv(qkv(x))
         self._rotary(q, k, v, st)
         if route.qkv is QKV.ROTARY_THEN_STORE:
             store_kvcache(k, v, k_cache, v_cache, block_table, cfg, ecfg, st, self.layer_id)
         x = self._attn_out_like(x)
         self._attention(route, q, k, v, x.view(-1, cfg.num_q_heads, cfg.head_dim), k_cache, v_cache, block_table, st)
         q = k = v = None
-        attn_out = linear_fp8_block(x, w.o_proj, w.o_bscale, (cfg.hidden_size,), wide=wide)
+        attn_out = o(x)
         fused_add_rmsnorm_inplace(attn_out, residual_buf, w.ffn_norm, cfg.rms_norm_eps)
-        act = linear_silu_gate_fp8_block(attn_out, w.up_gate_proj, w.up_gate_bscale, cfg.ffn_inter_dim, wide=wide)
-        return linear_fp8_block(act, w.down_proj, w.down_bscale, (cfg.hidden_size,), wide=wide)
+        return down(up_gate(attn_out))

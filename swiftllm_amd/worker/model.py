@@ -53,7 +53,7 @@ from .layers.transformer_layer import LlamaTransformerLayer
 from .layers.post_layer import LlamaPostLayer
 from .step_logits import PLAIN, LogitsStage, StagedInts, StepLogits
 from .token_history import TokenHistory, row_entries
-from .weight import load_weights, pack_decode_weights
+from .weight import dense_fp8_row_refusal, load_weights, pack_decode_weights
 
 _DTYPES = {"float16": torch.float16, "fp16": torch.float16, "half": torch.float16,
            "bfloat16": torch.bfloat16, "bf16": torch.bfloat16}
@@ -77,6 +77,13 @@ class LlamaModel:
         # csrc/gemm_fp8_block.h); the config refuses what that mode does not serve
         self.dense_fp8 = getattr(engine_config, "dense_weight_dtype", "auto") == "fp8_block"
         self.model_config = LlamaModelConfig.load_from_model_path(engine_config.model_path, dense_fp8=self.dense_fp8)
+        # ... and a dense 16-BIT checkpoint's layer projections are quantised per row at load (dense_weight_dtype =
+        # "fp8_e4m3"; csrc/gemm_fp8_row.h): the model config is the 16-bit one, the layers hold packed codes
+        self.dense_fp8_row = getattr(engine_config, "dense_weight_dtype", "auto") == "fp8_e4m3"
+        if self.dense_fp8_row:
+            why = dense_fp8_row_refusal(self.model_config)
+            if why:
+                raise ValueError(f"dense_weight_dtype='fp8_e4m3' cannot serve this {self.model_config.model_type} model: {why}")
         self.dtype = _DTYPES[getattr(engine_config, "dtype", "float16")]
         self.device = torch.device("cuda")
         cfg = self.model_config
@@ -193,8 +200,9 @@ class LlamaModel:
         self.weight = load_weights(self.model_config, self.dtype, self.engine_config.model_path,
                                    self.engine_config.use_dummy, device=self.device,
                                    fuse_qkv=getattr(self.engine_config, "fuse_qkv", False),
-                                   moe_weight_dtype="fp8_e4m3" if self.moe_fp8 else "auto")
-        if self.dense_fp8:
+                                   moe_weight_dtype="fp8_e4m3" if self.moe_fp8 else "auto",
+                                   dense_weight_dtype="fp8_e4m3" if self.dense_fp8_row else "auto")
+        if self.dense_fp8 or self.dense_fp8_row:
             # steps of more than 64 tokens multiply a 16-bit image of one projection at a time: ONE scratch tensor, sized for
             # the largest projection, allocated here so that profile_num_blocks counts it
             from .kernels.linear_fp8 import reserve_scratch

@@ -122,6 +122,28 @@ def dense_fp8_plan(cfg, layer_id: int) -> List[tuple]:
     return out
 
 
+# A dense 16-bit checkpoint served with dense_weight_dtype "fp8_e4m3" (csrc/gemm_fp8_row.h): the same four projections,
+# quantised per output row at load into PACKED codes — (attribute of the codes, attribute of the row scales, the checkpoint
+# tensors concatenated row-wise)
+DENSE_FP8_ROW_PROJECTIONS = tuple((attr, attr[:-len("proj")] + "scale", parts) for attr, _, parts in DENSE_FP8_PROJECTIONS)
+
+
+def dense_fp8_row_refusal(cfg) -> str:
+    """Why dense_weight_dtype "fp8_e4m3" cannot serve this model ('' when it can). Every checkpoint tensor must be a multiple of
+    16 rows (its codes start at a tile of the fused projection) and of 64 columns (swl_gemm_fp8_row_supported)."""
+    if getattr(cfg, "num_experts", 0):
+        return ("a mixture-of-experts model; FP8 expert stacks are moe_weight_dtype='fp8_e4m3' (--moe-weight-dtype), and its "
+                "attention projections stay 16-bit")
+    if getattr(cfg, "fp8_block", False):
+        return ("the checkpoint has a quantization_config; a block-scaled FP8 checkpoint is served from its own codes with "
+                "dense_weight_dtype='fp8_block'")
+    for spec in layer_weight_specs(cfg, 0):
+        if spec.attr.endswith("_proj") and (spec.shape[0] % 16 or spec.shape[1] % 64):
+            return (f"{spec.attr} is {spec.shape[0]} x {spec.shape[1]}; the packed per-row FP8 projections (csrc/gemm_fp8_row.h) "
+                    "take multiples of 16 rows and of 64 columns")
+    return ""
+
+
 def dequantise_blocks(codes: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
     """round_T(fp32(code) * scale[row // 128][col // 128]): one fp32 multiply, one rounding to `dtype`, in plain torch. What
     a block-scaled FP8 checkpoint's NON-expert tensors (q/k/v/o_proj, a quantised router) become at load."""
@@ -186,7 +208,7 @@ class LlamaTransformerLayerWeight:
     (and qkv_proj = [q ; k ; v] when fused). Qwen3: q_norm, k_norm [head_dim]. Qwen2: q_bias, k_bias, v_bias — with the
     fused projection they are three slices of one qkv_bias = [q ; k ; v]."""
 
-    def __init__(self, layer_id: int, model_config, dtype: torch.dtype, moe_fp8: bool = False):
+    def __init__(self, layer_id: int, model_config, dtype: torch.dtype, moe_fp8: bool = False, dense_fp8_row: bool = False):
         self.layer_id = layer_id
         self.model_config = model_config
         self.dtype = dtype
@@ -212,6 +234,36 @@ class LlamaTransformerLayerWeight:
         self.expert_up_gate_bscale = self.expert_down_bscale = None
         # fp32 [sum of ceil(segment rows / 128), ceil(K / 128)]: a dense block-scaled FP8 model only
         self.qkv_bscale = self.o_bscale = self.up_gate_bscale = self.down_bscale = None
+        # a dense 16-bit checkpoint served with dense_weight_dtype "fp8_e4m3" (csrc/gemm_fp8_row.h): the four projections are
+        # PACKED e4m3fn codes quantised at load, each with one fp32 scale per output row [N]
+        self.dense_fp8_row = bool(dense_fp8_row)
+        assert not (self.dense_fp8_row and self.dense_fp8), "a block-scaled checkpoint is not re-quantised per row"
+        self.qkv_scale = self.o_scale = self.up_gate_scale = self.down_scale = None
+
+    def load_dense_fp8_row(self, getter: Getter, device: torch.device):
+        """Each checkpoint tensor is uploaded in 16 bits, quantised straight into its rows of the fused projection's packed
+        codes (kernels/linear_fp8_row.py: quantise_pack_rows) and dropped before the next one: there is never a 16-bit and an
+        8-bit copy of more than one tensor."""
+        from .kernels.linear_fp8_row import quantise_pack_rows
+        specs = {s.attr: s for s in layer_weight_specs(self.model_config, self.layer_id)}
+        for attr, sattr, parts in DENSE_FP8_ROW_PROJECTIONS:
+            n, k = sum(specs[p].shape[0] for p in parts), specs[parts[0]].shape[1]
+            codes = torch.empty((n, k), dtype=FP8, device=device)
+            scale = torch.empty((n,), dtype=torch.float32, device=device)
+            row = 0
+            for part in parts:
+                spec = specs[part]
+                t = getter(spec)
+                assert isinstance(t, torch.Tensor) and tuple(t.shape) == tuple(spec.shape), \
+                    f"Shape of weight {spec.key} does not match: {tuple(getattr(t, 'shape', ()))} vs {spec.shape}"
+                assert t.dtype != FP8, f"Weight {spec.key} is FP8 codes, but config.json has no quantization_config"
+                t = t.to(device=device, dtype=self.dtype).contiguous()
+                rows = spec.shape[0]
+                scale[row:row + rows].copy_(quantise_pack_rows(t, codes.view(-1)[row * k:(row + rows) * k]))
+                row += rows
+                del t
+            setattr(self, attr, codes)
+            setattr(self, sattr, scale)
 
     def alloc_dense_fp8(self, device: torch.device) -> List[tuple]:
         """The code and scale tensors of the four projections; returns dense_fp8_plan."""
@@ -287,10 +339,10 @@ class LlamaTransformerLayerWeight:
         self.q_bias, self.k_bias, self.v_bias = self.qkv_bias[:qs], self.qkv_bias[qs:qs + kv], self.qkv_bias[qs + kv:]
 
     def load(self, getter: Getter, device: torch.device, fuse_qkv: bool):
-        if self.dense_fp8:
+        if self.dense_fp8 or self.dense_fp8_row:
             _fill(self, [s for s in layer_weight_specs(self.model_config, self.layer_id) if not s.attr.endswith("_proj")],
                   getter, self.dtype, device)
-            self.load_dense_fp8(getter, device)
+            (self.load_dense_fp8 if self.dense_fp8 else self.load_dense_fp8_row)(getter, device)
             if self.q_bias is not None:
                 self.qkv_bias = torch.cat((self.q_bias, self.k_bias, self.v_bias), dim=0).contiguous()
                 self.slice_qkv_bias()
@@ -312,12 +364,14 @@ class LlamaTransformerLayerWeight:
 class LlamaWeight:
     """All weights of the model: wte, lm_head, final_norm and `layers`."""
 
-    def __init__(self, model_config, dtype: torch.dtype, model_version: str = "llama", moe_fp8: bool = False):
+    def __init__(self, model_config, dtype: torch.dtype, model_version: str = "llama", moe_fp8: bool = False,
+                 dense_fp8_row: bool = False):
         self.model_config = model_config
         self.dtype = dtype
         self.model_version = model_version
         self.moe_fp8 = bool(moe_fp8)
-        self.layers = [LlamaTransformerLayerWeight(i, model_config, dtype, moe_fp8)
+        self.dense_fp8_row = bool(dense_fp8_row)
+        self.layers = [LlamaTransformerLayerWeight(i, model_config, dtype, moe_fp8, dense_fp8_row)
                        for i in range(model_config.num_layers)]
 
     def load(self, getter: Getter, device: torch.device, fuse_qkv: bool = False):
@@ -446,10 +500,11 @@ def _stream_safetensors(weight: "LlamaWeight", model_path: str, files: List[str]
     for layer in weight.layers:
         specs = {s.attr: s for s in layer_weight_specs(cfg, layer.layer_id)}
         moe = "router" in specs
-        if layer.dense_fp8:
+        if layer.dense_fp8 or layer.dense_fp8_row:
             # a dense block-scaled FP8 layer: the four projections' codes and scales, each at its final rows of the fused
             # tensors, and the 16-bit rest — norms, Qwen3's QK-norms, Qwen2's biases fused as the FP8 layer body takes them
-            for attr, sattr, _, _, placed in layer.alloc_dense_fp8(device):
+            # (a per-row FP8 layer: the rest only; its projections are quantised tensor by tensor behind the stream)
+            for attr, sattr, _, _, placed in layer.alloc_dense_fp8(device) if layer.dense_fp8 else ():
                 for spec, row, sspec, srow in placed:
                     plan.append((spec.key, spec.shape, getattr(layer, attr), row))
                     plan.append((sspec.key, sspec.shape, getattr(layer, sattr), srow))
@@ -619,20 +674,27 @@ def detect_model_version(model_path: str) -> str:
 
 def load_weights(model_config, dtype: torch.dtype, model_path: str, use_dummy: bool = False,
                  model_version: str = "auto", device="cuda", fuse_qkv: bool = False,
-                 streaming: bool = True, moe_weight_dtype: str = "auto") -> LlamaWeight:
+                 streaming: bool = True, moe_weight_dtype: str = "auto", dense_weight_dtype: str = "auto") -> LlamaWeight:
     """Read (or synthesise) every weight of the model onto `device` in `dtype`. `streaming=False` forces the
     reference's tensor-by-tensor safetensors path. `moe_weight_dtype="fp8_e4m3"` (mixture-of-experts models): the expert
     stacks are quantised per output row as they load (csrc/moe_fp8.h); everything else stays `dtype`. A block-scaled FP8
     checkpoint (model_config.fp8_block; csrc/moe_fp8_block.h) is served with its own codes and scales under either value:
-    the expert codes and scales go to their stacks as they are, every other quantised tensor is dequantised once to `dtype`."""
+    the expert codes and scales go to their stacks as they are, every other quantised tensor is dequantised once to `dtype`.
+    `dense_weight_dtype="fp8_e4m3"` (dense 16-bit checkpoints): every layer projection is quantised per output row into
+    packed codes as it loads (csrc/gemm_fp8_row.h); the embedding, lm_head and the norms stay `dtype`."""
     device = torch.device(device)
     moe_fp8 = moe_weight_dtype == "fp8_e4m3" and not getattr(model_config, "fp8_block", False)
+    fp8_row = dense_weight_dtype == "fp8_e4m3"
+    if fp8_row:
+        why = dense_fp8_row_refusal(model_config)
+        if why:
+            raise ValueError(f"dense_weight_dtype='fp8_e4m3' cannot serve this model: {why}")
     if model_version == "auto":
         if getattr(model_config, "model_type", "llama") != "llama":
             model_version = "llama3.2" if model_config.tie_word_embeddings else "llama"
         else:
             model_version = detect_model_version(model_path)
-    weight = LlamaWeight(model_config, dtype, model_version, moe_fp8)
+    weight = LlamaWeight(model_config, dtype, model_version, moe_fp8, fp8_row)
     if use_dummy:
         getter = _dummy_getter(dtype, device, bool(getattr(model_config, "fp8_block", False)),
                                bool(getattr(model_config, "dense_fp8", False)))
@@ -647,8 +709,12 @@ def load_weights(model_config, dtype: torch.dtype, model_path: str, use_dummy: b
                     getter = _safetensors_getter(model_path, st_files, device)
                     for layer in weight.layers:
                         layer.load_experts(getter, device)
+                if fp8_row:                                 # the projections: one 16-bit tensor at a time, quantised into place
+                    getter = _safetensors_getter(model_path, st_files, device)
+                    for layer in weight.layers:
+                        layer.load_dense_fp8_row(getter, device)
                 return weight
-            weight = LlamaWeight(model_config, dtype, model_version, moe_fp8)    # start over on the per-tensor path
+            weight = LlamaWeight(model_config, dtype, model_version, moe_fp8, fp8_row)    # start over on the per-tensor path
         getter = (_safetensors_getter(model_path, st_files, device) if st_files
                   else _torch_bin_getter(model_path, device))
     weight.load(getter, device, fuse_qkv)
