@@ -29,8 +29,9 @@ def main():
     ap.add_argument("--kv-cache-dtype", default="auto", choices=["auto", "fp8_e4m3"])
     ap.add_argument("--moe-weight-dtype", default="auto", choices=["auto", "fp8_e4m3"],
                     help="mixture-of-experts models: fp8_e4m3 quantises the expert stacks per output row at load")
-    ap.add_argument("--dense-weight-dtype", default="auto", choices=["auto", "fp8_block"],
-                    help="dense block-scaled FP8 checkpoints: fp8_block serves the checkpoint's own codes and scales")
+    ap.add_argument("--dense-weight-dtype", default="auto", choices=["auto", "fp8_block", "fp8_e4m3", "mxfp4"],
+                    help="dense block-scaled FP8 checkpoints: fp8_block serves the checkpoint's own codes and scales; dense "
+                         "16-bit checkpoints: fp8_e4m3 / mxfp4 (with --dtype bfloat16) quantise the layer projections at load")
     ap.add_argument("--dense-fp8-wide", action="store_true",
                     help="with --dense-weight-dtype fp8_block: steps of 65..192 tokens run the wide FP8 kernels")
     ap.add_argument("--speculative-ngram", type=int, default=0,

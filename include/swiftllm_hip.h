@@ -966,6 +966,41 @@ int swl_gemm_fp8_row_silu_gate(void *act, const void *x, const void *codes, cons
 int swl_fp8_row_dequant(void *out, const void *codes, const float *scale, int32_t n, int32_t k, int32_t dtype,
                         swl_stream_t stream);
 
+/* ---- dense projections of a 16-bit checkpoint on MXFP4 weights (OCP Microscaling v1.0: e2m1 codes, one e8m0 scale per 32
+ * k), quantised at load into PACKED codes and scales (csrc/gemm_mxfp4.hip; the contract, both packed orders, the walk and
+ * the chain of one output element: csrc/gemm_mxfp4.h). A projection is codes (N * K / 2 bytes: 16-row x 128-k tiles of
+ * 1 KiB, tile (nt, kt) at byte 1024 * (nt * K / 128 + kt), lane i16 + 16 q's 32 codes — one MX block, the lower k in the
+ * low nibble — at byte 16 * lane) and scales (N / 16 * ceil(K / 512) * 256 bytes: the four k tiles 4 kg .. + 3 of row
+ * group nt at byte 256 * (nt * ceil(K / 512) + kg), lane's four bytes at 4 * lane; a byte is e + 127, past K: 127), both
+ * 16-byte aligned; the weight means e2m1(code) * 2^e, exact in bfloat16. N % 16 == 0 and K % 128 == 0 (anything else:
+ * SWL_ERR_UNSUPPORTED). x and the outputs are bfloat16 (float16: SWL_ERR_UNSUPPORTED — 2^e leaves its range; any other
+ * code: SWL_ERR_BAD_ARG); outputs are contiguous.
+ *   swl_gemm_mxfp4_supported: n % 16 == 0, k % 128 == 0, dtype bf16. Host only.
+ *   swl_gemm_mxfp4_choose_splits: the k slices the GEMMs cut (n output columns, k) into: a function of (n, k) alone, a power
+ *     of two <= 8 that leaves a slice at least 1024 k; 0 for a shape that is not taken. Host only.
+ *   swl_gemm_mxfp4_quantise_pack: codes and scales of the 16-bit (f16 or bf16) row-major w[n, k], one launch: per block
+ *     e = clamp(floor(log2 max|w|) - 2, -126, 127) (a zero block: 0), code = e2m1 nearest-even of w * 2^-e, saturating at 6.
+ *   swl_gemm_mxfp4: y[num_tokens, N] = T(x . W^T), 1 <= num_tokens <= 64 (more: SWL_ERR_UNSUPPORTED). k_splits 0: the
+ *     chooser's; else a power of two <= 8 and <= K / 128. With k_splits > 1 the workspace (16-byte aligned) holds
+ *     k_splits * num_tokens * N floats and a finishing kernel follows on the stream. No host synchronisation, no atomics.
+ *     A row's bits depend on that row of x and the weights only; a (shape, split) is run-to-run deterministic.
+ *   swl_gemm_mxfp4_silu_gate: act[num_tokens, inter] = up *_T silu(gate) over codes of [2 inter, K] = [up ; gate]; the
+ *     workspace holds k_splits * num_tokens * 2 inter floats.
+ *   swl_mxfp4_dequant: out[N, K] = bf16(e2m1(code) * 2^e), row-major, one launch: the unpacking kernel, for steps of more
+ *     than 64 tokens. */
+int swl_gemm_mxfp4_supported(int32_t n, int32_t k, int32_t dtype);
+int swl_gemm_mxfp4_choose_splits(int32_t n, int32_t k);
+int swl_gemm_mxfp4_quantise_pack(void *codes, void *scales, const void *w, int32_t n, int32_t k, int32_t dtype,
+                                 swl_stream_t stream);
+int swl_gemm_mxfp4(void *y, const void *x, const void *codes, const void *scales, void *workspace, int64_t workspace_bytes,
+                   int32_t num_tokens, int32_t n, int32_t k, int64_t x_row_stride, int32_t k_splits, int32_t dtype,
+                   swl_stream_t stream);
+int swl_gemm_mxfp4_silu_gate(void *act, const void *x, const void *codes, const void *scales, void *workspace,
+                             int64_t workspace_bytes, int32_t num_tokens, int32_t inter, int32_t k, int64_t x_row_stride,
+                             int32_t k_splits, int32_t dtype, swl_stream_t stream);
+int swl_mxfp4_dequant(void *out, const void *codes, const void *scales, int32_t n, int32_t k, int32_t dtype,
+                      swl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,14 @@ _SPECIAL = {
     "swl_gemm_fp8_row": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
     "swl_gemm_fp8_row_silu_gate": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
     "swl_fp8_row_dequant": ([_P, _P, _P, _I32, _I32, _I32, _P], _I32),
+    # MXFP4 DENSE projections of a 16-bit checkpoint, packed codes and scales (csrc/gemm_mxfp4.hip; the contract:
+    # csrc/gemm_mxfp4.h; their own tests: tests/test_gemm_mxfp4_host.py): the same six entries
+    "swl_gemm_mxfp4_supported": ([_I32, _I32, _I32], _I32),
+    "swl_gemm_mxfp4_choose_splits": ([_I32, _I32], _I32),
+    "swl_gemm_mxfp4_quantise_pack": ([_P, _P, _P, _I32, _I32, _I32, _P], _I32),
+    "swl_gemm_mxfp4": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
+    "swl_gemm_mxfp4_silu_gate": ([_P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _I64, _I32, _I32, _P], _I32),
+    "swl_mxfp4_dequant": ([_P, _P, _P, _I32, _I32, _I32, _P], _I32),
 }
 
 _lock = threading.Lock()

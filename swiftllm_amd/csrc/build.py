@@ -47,9 +47,10 @@ SOURCES = [
     "gemm_fp8_block.hip",
     "gemm_fp8_block_wide.hip",
     "gemm_fp8_row.hip",
+    "gemm_mxfp4.hip",
     "decode_engine.hip",
 ]
-HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "decode_attn.h", "prefill_tile.h", "fp8_kv.h", "kv_store.h", "gemm_host.h", "moe_common.h", "moe_fp8.h", "moe_fp8_block.h", "gemm_fp8_block.h", "gemm_fp8_row.h", "logits_keys.h", "logits_bits.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
+HEADERS = ["swl_common.h", "attend_block.h", "attn_mfma.h", "decode_attn.h", "prefill_tile.h", "fp8_kv.h", "kv_store.h", "gemm_host.h", "moe_common.h", "moe_fp8.h", "moe_fp8_block.h", "gemm_fp8_block.h", "gemm_fp8_row.h", "gemm_mxfp4.h", "logits_keys.h", "logits_bits.h", os.path.join(ROOT, "include", "swiftllm_hip.h")]
 LIB = os.path.join(HERE, "libswiftllm_hip.so")
 OBJ_DIR = os.path.join(HERE, "build")
 ARCH = "gfx950"
@@ -61,7 +62,7 @@ CXXFLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contra
 # folds).
 SOURCE_FLAGS = {src: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
                 for src in ("moe_fp8.hip", "moe_fp8_wide.hip", "moe_fp8_block.hip", "moe_fp8_block_wide.hip",
-                            "gemm_fp8_block.hip", "gemm_fp8_block_wide.hip", "gemm_fp8_row.hip")}
+                            "gemm_fp8_block.hip", "gemm_fp8_block_wide.hip", "gemm_fp8_row.hip", "gemm_mxfp4.hip")}
 
 
 def _hipcc() -> str:

@@ -70,4 +70,33 @@ inline bool fp8_row_splits_ok(int ks, int k) {
     return ks >= 1 && ks <= kFp8RowMaxSplits && !(ks & (ks - 1)) && ks <= k / kFp8KStep;
 }
 
+// The finishing kernel of a split launch: four neighbouring columns a thread, the slabs added in slice order, then the
+// scale and the epilogue of the unsplit kernel. SCALED = false (gemm_mxfp4.hip: the weights carry their scales): `scale` is
+// not read and every scale is 1.
+template <typename T, bool SILU, bool SCALED = true>
+__global__ __launch_bounds__(256) void gemm_fp8_row_finish_kernel(T *__restrict__ out, const float *__restrict__ slabs,
+                                                                  const float *__restrict__ scale, int ks, int M, int n_out,
+                                                                  int n_w) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int per_row = n_out / 4;
+    if (i >= static_cast<int64_t>(M) * per_row) return;
+    const int row = static_cast<int>(i / per_row), col = 4 * static_cast<int>(i % per_row);
+    const float *p = slabs + static_cast<int64_t>(row) * n_w + col;
+    const int64_t slab = static_cast<int64_t>(M) * n_w;
+    float4_t a = *reinterpret_cast<const float4_t *>(p), g = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (SILU) g = *reinterpret_cast<const float4_t *>(p + n_out);
+    for (int j = 1; j < ks; ++j) {
+        a += *reinterpret_cast<const float4_t *>(p + j * slab);
+        if constexpr (SILU) g += *reinterpret_cast<const float4_t *>(p + j * slab + n_out);
+    }
+    float4_t sa = {1.f, 1.f, 1.f, 1.f}, sg = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (SCALED) sa = *reinterpret_cast<const float4_t *>(scale + col);
+    if constexpr (SILU && SCALED) sg = *reinterpret_cast<const float4_t *>(scale + n_out + col);
+    typedef T T4 __attribute__((ext_vector_type(4)));
+    T4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = SILU ? fp8_up_gate_act<T>(a[e], g[e], sa[e], sg[e]) : to_t<T>(__fmul_rn(a[e], sa[e]));
+    *reinterpret_cast<T4 *>(out + static_cast<int64_t>(row) * n_out + col) = o;
+}
+
 } // namespace swl

@@ -103,6 +103,9 @@ class EngineConfig:
     # norms stay 16-bit. Refused for a checkpoint that has a quantization_config (serve it with "fp8_block"), a
     # mixture-of-experts model (moe_weight_dtype), with tuning={'decode_engine': True}, with max_loras > 0 and with
     # dense_fp8_wide.
+    # "mxfp4": the 4-bit twin of "fp8_e4m3" — OCP MXFP4, e2m1 codes with one power-of-two scale per 32 k, packed codes and
+    # scales (csrc/gemm_mxfp4.h): 4.25 bits per weight. The same refusals, and dtype must be
+    # bfloat16.
     dense_weight_dtype: str = "auto"
     # With dense_weight_dtype "fp8_block": steps of 65..192 tokens run the wide FP8 weight-streaming kernels
     # (csrc/gemm_fp8_block_wide.hip) in place of dequantise + the library GEMM. False (default): every step launches what it
@@ -165,7 +168,7 @@ class EngineConfig:
     LORA_RANKS = (8, 16, 32, 64)
     MOE_WIDE_TILES = (-1, 0, 2, 4)
     MOE_WEIGHT_DTYPES = ("auto", "fp8_e4m3")
-    DENSE_WEIGHT_DTYPES = ("auto", "fp8_block", "fp8_e4m3")
+    DENSE_WEIGHT_DTYPES = ("auto", "fp8_block", "fp8_e4m3", "mxfp4")
 
     def __post_init__(self):
         # The reference takes block_size as a Triton constexpr (paged_attn.py:27) and its CLI default is 16
@@ -234,6 +237,9 @@ class EngineConfig:
         if self.dense_fp8_wide and self.dense_weight_dtype != "fp8_block":
             raise ValueError("dense_fp8_wide=True needs dense_weight_dtype='fp8_block': the wide FP8 kernels multiply a "
                              "block-scaled FP8 checkpoint's codes, and no other model holds any")
+        if self.dense_weight_dtype == "mxfp4" and self.dtype not in ("bfloat16", "bf16"):
+            raise ValueError(f"dense_weight_dtype='mxfp4' needs dtype='bfloat16', got {self.dtype!r}: a block scale applied "
+                             "inside the convert can leave float16's range, so the dequantisation would not be exact")
         if self.dense_weight_dtype != "auto" and self.decode_engine:
             raise ValueError(f"dense_weight_dtype={self.dense_weight_dtype!r} cannot be combined with tuning={{'decode_engine': True}}: the "
                              "persistent one-sequence decode step streams 16-bit weights only")
@@ -284,7 +290,8 @@ class EngineConfig:
         g.add_argument("--dense-weight-dtype", type=str, default="auto", choices=list(EngineConfig.DENSE_WEIGHT_DTYPES),
                        help="A dense block-scaled FP8 checkpoint: auto = refused, fp8_block = served from its own e4m3 codes "
                             "and 128 x 128 block scales. A dense 16-bit checkpoint: fp8_e4m3 = layer projections quantised at "
-                            "load, 1 byte per element + one fp32 scale per output row")
+                            "load, 1 byte per element + one fp32 scale per output row; mxfp4 = 4-bit e2m1 codes + one "
+                            "power-of-two scale per 32 elements (needs --dtype bfloat16)")
         g.add_argument("--dense-fp8-wide", action="store_true",
                        help="With --dense-weight-dtype fp8_block: steps of 65..192 tokens run the wide FP8 kernels instead "
                             "of dequantise + the library GEMM")

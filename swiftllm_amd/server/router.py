@@ -144,9 +144,9 @@ def main():
                     help="element type of every replica's KV pools (api_server --kv-cache-dtype)")
     ap.add_argument("--moe-weight-dtype", default=None, choices=["auto", "fp8_e4m3"],
                     help="element type of every replica's expert stacks (api_server --moe-weight-dtype)")
-    ap.add_argument("--dense-weight-dtype", default=None, choices=["auto", "fp8_block", "fp8_e4m3"],
+    ap.add_argument("--dense-weight-dtype", default=None, choices=["auto", "fp8_block", "fp8_e4m3", "mxfp4"],
                     help="every replica serves a dense block-scaled FP8 checkpoint from its codes (fp8_block) or quantises a "
-                         "16-bit one at load (fp8_e4m3) (api_server --dense-weight-dtype)")
+                         "16-bit one at load (fp8_e4m3, mxfp4) (api_server --dense-weight-dtype)")
     ap.add_argument("--dense-fp8-wide", action="store_true",
                     help="every replica runs the wide FP8 kernels at 65..192 tokens (api_server --dense-fp8-wide)")
     # multi-LoRA serving: every replica loads the same adapters (a request's "lora" field is relayed like every field)

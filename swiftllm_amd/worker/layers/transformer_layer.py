@@ -57,6 +57,7 @@ from ..kernels.silu_and_mul import silu_and_mul_inplace
 from ..kernels.lora import lora_apply
 from ..kernels.linear_fp8 import WIDE_ROUTED_MAX_M, linear_fp8_block, linear_silu_gate_fp8_block
 from ..kernels.linear_fp8_row import linear_fp8_row, linear_silu_gate_fp8_row
+from ..kernels.linear_mxfp4 import linear_mxfp4, linear_silu_gate_mxfp4
 from ..kernels.moe import moe_ffn
 
 # Where the row-owned projections win on MI355X (tools/gemm_rows_micro.py --layer, tools/rows_kernel_us.py): every
@@ -518,7 +519,12 @@ class LlamaTransformerLayer:
         cfg, ecfg, w = self.model_config, self.engine_config, self.weight
         wide = ecfg.dense_fp8_wide and x.shape[0] <= WIDE_ROUTED_MAX_M
         kv = cfg.num_kv_heads * cfg.head_dim
-        if self.dense_fp8_row:      # the projections by the kind of weights the layer holds: packed per-row codes
+        if getattr(w, "dense_mxfp4", False):    # the projections by the kind of weights the layer holds: packed MXFP4 codes
+            qkv = lambda a: linear_mxfp4(a, w.qkv_proj, w.qkv_scale)                            # noqa: E731
+            o = lambda a: linear_mxfp4(a, w.o_proj, w.o_scale)                                  # noqa: E731
+            up_gate = lambda a: linear_silu_gate_mxfp4(a, w.up_gate_proj, w.up_gate_scale)      # noqa: E731
+            down = lambda a: linear_mxfp4(a, w.down_proj, w.down_scale)                         # noqa: E731
+        elif self.dense_fp8_row:    # ... packed per-row FP8 codes
             qkv = lambda a: linear_fp8_row(a, w.qkv_proj, w.qkv_scale)                          # noqa: E731
             o = lambda a: linear_fp8_row(a, w.o_proj, w.o_scale)                                # noqa: E731
             up_gate = lambda a: linear_silu_gate_fp8_row(a, w.up_gate_proj, w.up_gate_scale)    # noqa: E731

@@ -79,11 +79,14 @@ class LlamaModel:
         self.model_config = LlamaModelConfig.load_from_model_path(engine_config.model_path, dense_fp8=self.dense_fp8)
         # ... and a dense 16-BIT checkpoint's layer projections are quantised per row at load (dense_weight_dtype =
         # "fp8_e4m3"; csrc/gemm_fp8_row.h): the model config is the 16-bit one, the layers hold packed codes
-        self.dense_fp8_row = getattr(engine_config, "dense_weight_dtype", "auto") == "fp8_e4m3"
+        # ("mxfp4": into MXFP4 codes and block scales, csrc/gemm_mxfp4.h — loaded and routed like the per-row kind)
+        self.dense_mxfp4 = getattr(engine_config, "dense_weight_dtype", "auto") == "mxfp4"
+        self.dense_fp8_row = getattr(engine_config, "dense_weight_dtype", "auto") == "fp8_e4m3" or self.dense_mxfp4
         if self.dense_fp8_row:
-            why = dense_fp8_row_refusal(self.model_config)
+            why = dense_fp8_row_refusal(self.model_config, self.dense_mxfp4)
             if why:
-                raise ValueError(f"dense_weight_dtype='fp8_e4m3' cannot serve this {self.model_config.model_type} model: {why}")
+                raise ValueError(f"dense_weight_dtype={engine_config.dense_weight_dtype!r} cannot serve this "
+                                 f"{self.model_config.model_type} model: {why}")
         self.dtype = _DTYPES[getattr(engine_config, "dtype", "float16")]
         self.device = torch.device("cuda")
         cfg = self.model_config
@@ -201,14 +204,15 @@ class LlamaModel:
                                    self.engine_config.use_dummy, device=self.device,
                                    fuse_qkv=getattr(self.engine_config, "fuse_qkv", False),
                                    moe_weight_dtype="fp8_e4m3" if self.moe_fp8 else "auto",
-                                   dense_weight_dtype="fp8_e4m3" if self.dense_fp8_row else "auto")
+                                   dense_weight_dtype="mxfp4" if self.dense_mxfp4 else "fp8_e4m3" if self.dense_fp8_row else "auto")
         if self.dense_fp8 or self.dense_fp8_row:
             # steps of more than 64 tokens multiply a 16-bit image of one projection at a time: ONE scratch tensor, sized for
             # the largest projection, allocated here so that profile_num_blocks counts it
             from .kernels.linear_fp8 import reserve_scratch
             lw = self.weight.layers[0]
             reserve_scratch(lw.o_proj.device, self.dtype,
-                            max(t.numel() for t in (lw.qkv_proj, lw.o_proj, lw.up_gate_proj, lw.down_proj)))
+                            max(t.numel() for t in (lw.qkv_proj, lw.o_proj, lw.up_gate_proj, lw.down_proj))
+                            * (2 if self.dense_mxfp4 else 1))               # (two MXFP4 codes a byte)
         self.repack_decode_weights()
         self._tune_routes()
         self._init_to_get_rotary()

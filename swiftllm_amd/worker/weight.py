@@ -128,19 +128,21 @@ def dense_fp8_plan(cfg, layer_id: int) -> List[tuple]:
 DENSE_FP8_ROW_PROJECTIONS = tuple((attr, attr[:-len("proj")] + "scale", parts) for attr, _, parts in DENSE_FP8_PROJECTIONS)
 
 
-def dense_fp8_row_refusal(cfg) -> str:
-    """Why dense_weight_dtype "fp8_e4m3" cannot serve this model ('' when it can). Every checkpoint tensor must be a multiple of
-    16 rows (its codes start at a tile of the fused projection) and of 64 columns (swl_gemm_fp8_row_supported)."""
+def dense_fp8_row_refusal(cfg, mxfp4: bool = False) -> str:
+    """Why dense_weight_dtype "fp8_e4m3" (`mxfp4`: "mxfp4") cannot serve this model ('' when it can). Every checkpoint tensor
+    must be a multiple of 16 rows (its codes start at a tile of the fused projection) and of 64 columns
+    (swl_gemm_fp8_row_supported; MXFP4: 128, swl_gemm_mxfp4_supported)."""
     if getattr(cfg, "num_experts", 0):
         return ("a mixture-of-experts model; FP8 expert stacks are moe_weight_dtype='fp8_e4m3' (--moe-weight-dtype), and its "
                 "attention projections stay 16-bit")
     if getattr(cfg, "fp8_block", False):
         return ("the checkpoint has a quantization_config; a block-scaled FP8 checkpoint is served from its own codes with "
                 "dense_weight_dtype='fp8_block'")
+    cols, what = (128, "MXFP4 projections (csrc/gemm_mxfp4.h)") if mxfp4 else (64, "per-row FP8 projections (csrc/gemm_fp8_row.h)")
     for spec in layer_weight_specs(cfg, 0):
-        if spec.attr.endswith("_proj") and (spec.shape[0] % 16 or spec.shape[1] % 64):
-            return (f"{spec.attr} is {spec.shape[0]} x {spec.shape[1]}; the packed per-row FP8 projections (csrc/gemm_fp8_row.h) "
-                    "take multiples of 16 rows and of 64 columns")
+        if spec.attr.endswith("_proj") and (spec.shape[0] % 16 or spec.shape[1] % cols):
+            return (f"{spec.attr} is {spec.shape[0]} x {spec.shape[1]}; the packed {what} "
+                    f"take multiples of 16 rows and of {cols} columns")
     return ""
 
 
@@ -208,7 +210,8 @@ class LlamaTransformerLayerWeight:
     (and qkv_proj = [q ; k ; v] when fused). Qwen3: q_norm, k_norm [head_dim]. Qwen2: q_bias, k_bias, v_bias — with the
     fused projection they are three slices of one qkv_bias = [q ; k ; v]."""
 
-    def __init__(self, layer_id: int, model_config, dtype: torch.dtype, moe_fp8: bool = False, dense_fp8_row: bool = False):
+    def __init__(self, layer_id: int, model_config, dtype: torch.dtype, moe_fp8: bool = False, dense_fp8_row: bool = False,
+                 dense_mxfp4: bool = False):
         self.layer_id = layer_id
         self.model_config = model_config
         self.dtype = dtype
@@ -236,20 +239,28 @@ class LlamaTransformerLayerWeight:
         self.qkv_bscale = self.o_bscale = self.up_gate_bscale = self.down_bscale = None
         # a dense 16-bit checkpoint served with dense_weight_dtype "fp8_e4m3" (csrc/gemm_fp8_row.h): the four projections are
         # PACKED e4m3fn codes quantised at load, each with one fp32 scale per output row [N]
-        self.dense_fp8_row = bool(dense_fp8_row)
+        # ... or with "mxfp4" (csrc/gemm_mxfp4.h), the third kind of dense FP weights: PACKED e2m1 codes, uint8 [N, K / 2],
+        # and the same *_scale attributes hold the packed e8m0 block scales, uint8 [N / 16 * ceil(K / 512) * 256]. Such a
+        # layer is loaded, streamed and routed like a per-row one (dense_fp8_row is set too); the kernels differ.
+        self.dense_mxfp4 = bool(dense_mxfp4)
+        self.dense_fp8_row = bool(dense_fp8_row) or self.dense_mxfp4
         assert not (self.dense_fp8_row and self.dense_fp8), "a block-scaled checkpoint is not re-quantised per row"
         self.qkv_scale = self.o_scale = self.up_gate_scale = self.down_scale = None
 
     def load_dense_fp8_row(self, getter: Getter, device: torch.device):
         """Each checkpoint tensor is uploaded in 16 bits, quantised straight into its rows of the fused projection's packed
-        codes (kernels/linear_fp8_row.py: quantise_pack_rows) and dropped before the next one: there is never a 16-bit and an
-        8-bit copy of more than one tensor."""
-        from .kernels.linear_fp8_row import quantise_pack_rows
+        codes (kernels/linear_fp8_row.py, kernels/linear_mxfp4.py: quantise_pack_rows) and dropped before the next one: there
+        is never a 16-bit and a quantised copy of more than one tensor."""
+        from .kernels import linear_fp8_row, linear_mxfp4
         specs = {s.attr: s for s in layer_weight_specs(self.model_config, self.layer_id)}
         for attr, sattr, parts in DENSE_FP8_ROW_PROJECTIONS:
             n, k = sum(specs[p].shape[0] for p in parts), specs[parts[0]].shape[1]
-            codes = torch.empty((n, k), dtype=FP8, device=device)
-            scale = torch.empty((n,), dtype=torch.float32, device=device)
+            if self.dense_mxfp4:
+                codes = torch.empty((n, k // 2), dtype=torch.uint8, device=device)
+                scale = torch.empty((linear_mxfp4.scale_bytes(n, k),), dtype=torch.uint8, device=device)
+            else:
+                codes = torch.empty((n, k), dtype=FP8, device=device)
+                scale = torch.empty((n,), dtype=torch.float32, device=device)
             row = 0
             for part in parts:
                 spec = specs[part]
@@ -259,7 +270,12 @@ class LlamaTransformerLayerWeight:
                 assert t.dtype != FP8, f"Weight {spec.key} is FP8 codes, but config.json has no quantization_config"
                 t = t.to(device=device, dtype=self.dtype).contiguous()
                 rows = spec.shape[0]
-                scale[row:row + rows].copy_(quantise_pack_rows(t, codes.view(-1)[row * k:(row + rows) * k]))
+                if self.dense_mxfp4:
+                    sb = linear_mxfp4.scale_bytes
+                    linear_mxfp4.quantise_pack_rows(t, codes.view(-1)[row * k // 2:(row + rows) * k // 2],
+                                                    scale[sb(row, k):sb(row + rows, k)])
+                else:
+                    scale[row:row + rows].copy_(linear_fp8_row.quantise_pack_rows(t, codes.view(-1)[row * k:(row + rows) * k]))
                 row += rows
                 del t
             setattr(self, attr, codes)
@@ -365,13 +381,14 @@ class LlamaWeight:
     """All weights of the model: wte, lm_head, final_norm and `layers`."""
 
     def __init__(self, model_config, dtype: torch.dtype, model_version: str = "llama", moe_fp8: bool = False,
-                 dense_fp8_row: bool = False):
+                 dense_fp8_row: bool = False, dense_mxfp4: bool = False):
         self.model_config = model_config
         self.dtype = dtype
         self.model_version = model_version
         self.moe_fp8 = bool(moe_fp8)
-        self.dense_fp8_row = bool(dense_fp8_row)
-        self.layers = [LlamaTransformerLayerWeight(i, model_config, dtype, moe_fp8, dense_fp8_row)
+        self.dense_mxfp4 = bool(dense_mxfp4)
+        self.dense_fp8_row = bool(dense_fp8_row) or self.dense_mxfp4
+        self.layers = [LlamaTransformerLayerWeight(i, model_config, dtype, moe_fp8, dense_fp8_row, dense_mxfp4)
                        for i in range(model_config.num_layers)]
 
     def load(self, getter: Getter, device: torch.device, fuse_qkv: bool = False):
@@ -684,17 +701,20 @@ def load_weights(model_config, dtype: torch.dtype, model_path: str, use_dummy: b
     packed codes as it loads (csrc/gemm_fp8_row.h); the embedding, lm_head and the norms stay `dtype`."""
     device = torch.device(device)
     moe_fp8 = moe_weight_dtype == "fp8_e4m3" and not getattr(model_config, "fp8_block", False)
-    fp8_row = dense_weight_dtype == "fp8_e4m3"
+    mxfp4 = dense_weight_dtype == "mxfp4"                   # ... or into packed MXFP4 codes and scales (csrc/gemm_mxfp4.h)
+    fp8_row = dense_weight_dtype == "fp8_e4m3" or mxfp4
     if fp8_row:
-        why = dense_fp8_row_refusal(model_config)
+        why = dense_fp8_row_refusal(model_config, mxfp4)
+        if not why and mxfp4 and dtype != torch.bfloat16:
+            why = f"dtype is {dtype}; a block scale can leave float16's range, MXFP4 projections are served in bfloat16"
         if why:
-            raise ValueError(f"dense_weight_dtype='fp8_e4m3' cannot serve this model: {why}")
+            raise ValueError(f"dense_weight_dtype={dense_weight_dtype!r} cannot serve this model: {why}")
     if model_version == "auto":
         if getattr(model_config, "model_type", "llama") != "llama":
             model_version = "llama3.2" if model_config.tie_word_embeddings else "llama"
         else:
             model_version = detect_model_version(model_path)
-    weight = LlamaWeight(model_config, dtype, model_version, moe_fp8, fp8_row)
+    weight = LlamaWeight(model_config, dtype, model_version, moe_fp8, fp8_row, mxfp4)
     if use_dummy:
         getter = _dummy_getter(dtype, device, bool(getattr(model_config, "fp8_block", False)),
                                bool(getattr(model_config, "dense_fp8", False)))
@@ -714,7 +734,7 @@ def load_weights(model_config, dtype: torch.dtype, model_path: str, use_dummy: b
                     for layer in weight.layers:
                         layer.load_dense_fp8_row(getter, device)
                 return weight
-            weight = LlamaWeight(model_config, dtype, model_version, moe_fp8, fp8_row)    # start over on the per-tensor path
+            weight = LlamaWeight(model_config, dtype, model_version, moe_fp8, fp8_row, mxfp4)    # start over on the per-tensor path
         getter = (_safetensors_getter(model_path, st_files, device) if st_files
                   else _torch_bin_getter(model_path, device))
     weight.load(getter, device, fuse_qkv)

@@ -22,6 +22,10 @@ row_gemm  The same four shapes at M = 1, 8, 32, 64, three forms alternating in o
       block-scaled FP8 GEMM (`fp8_block`) and the per-row FP8 GEMM on packed codes (`fp8_row`, csrc/gemm_fp8_row.hip), with
       `row_over_16` and `row_over_block` (medians).
 row_step  The decode step of `step` at batch 1, 8, 32: the bf16 model, then the model with dense_weight_dtype "fp8_e4m3".
+mx_gemm   The same four shapes at M = 1, 8, 32, 64, three forms alternating in one run: the packed bf16 GEMM (`bf16`), the
+      per-row FP8 GEMM (`fp8_row`) and the MXFP4 GEMM (`mxfp4`, csrc/gemm_mxfp4.hip), with `mx_over_16` and `mx_over_row`
+      (medians). Repeated launches on one weight read partly from the last-level cache, all three forms alike.
+mx_step   The decode step at batch 1, 8, 32: the bf16 model, the "fp8_e4m3" model, then the "mxfp4" model, in one process.
 Each kernel figure is the median of `--repeats` runs of `--iters` back-to-back launches between two device events, with the
 range [min, max]; the forms alternate inside every repeat.
 """
@@ -45,7 +49,7 @@ LLAMA3_8B = dict(model_type="llama", hidden_act="silu", hidden_size=4096, interm
                  num_attention_heads=32, num_key_value_heads=8, vocab_size=128256, max_position_embeddings=8192,
                  rms_norm_eps=1e-5, rope_theta=500000.0, tie_word_embeddings=False)
 QUANT = {"quant_method": "fp8", "fmt": "e4m3", "activation_scheme": "dynamic", "weight_block_size": [128, 128]}
-SECTION_TIMEOUT_S = {"gemm": 400, "step": 500, "row_gemm": 400, "row_step": 500}
+SECTION_TIMEOUT_S = {"gemm": 400, "step": 500, "row_gemm": 400, "row_step": 500, "mx_gemm": 400, "mx_step": 700}
 
 
 def _timed(fn, iters):
@@ -159,6 +163,49 @@ def row_gemm_section(iters, repeats, ms=(1, 8, 32, 64)):
     return out
 
 
+def mx_gemm_section(iters, repeats, ms=(1, 8, 32, 64)):
+    from swiftllm_amd.worker.kernels import linear_fp8 as L
+    from swiftllm_amd.worker.kernels import linear_fp8_row as LR
+    from swiftllm_amd.worker.kernels import linear_mxfp4 as LM
+    from swiftllm_amd.worker.kernels.linear import linear, linear_silu_gate, pack_weight
+    dt, dev = torch.bfloat16, "cuda"
+    g = torch.Generator(device=dev).manual_seed(0)
+    out = {}
+    for name, (segments, k) in SHAPES.items():
+        n = sum(segments)
+        w16 = torch.empty((n, k), dtype=dt, device=dev).uniform_(-1e-3, 1e-3, generator=g)
+        pack_weight(w16)
+        rcodes = torch.empty((n, k), dtype=L.FP8, device=dev)
+        rscale = LR.quantise_pack_rows(w16, rcodes)
+        mcodes = torch.empty((n, k // 2), dtype=torch.uint8, device=dev)
+        mscales = torch.empty((LM.scale_bytes(n, k),), dtype=torch.uint8, device=dev)
+        LM.quantise_pack_rows(w16, mcodes, mscales)
+        silu = name == "up_gate_silu"
+        for m in [m for m in ms if m <= LM.MAX_M]:
+            x = torch.randn((m, k), device=dev, generator=g).to(dt)
+
+            def bf16():
+                y = linear_silu_gate(x, w16) if silu else linear(x, w16, True)
+                if y is None:
+                    L.silu_and_mul_inplace(linear(x, w16, True))
+            forms = {"bf16": bf16,
+                     "fp8_row": ((lambda: LR.linear_silu_gate_fp8_row(x, rcodes, rscale)) if silu else
+                                 (lambda: LR.linear_fp8_row(x, rcodes, rscale))),
+                     "mxfp4": ((lambda: LM.linear_silu_gate_mxfp4(x, mcodes, mscales)) if silu else
+                               (lambda: LM.linear_mxfp4(x, mcodes, mscales)))}
+            runs = {f: [] for f in forms}
+            for _ in range(repeats):
+                for f, fn in forms.items():
+                    runs[f].append(_timed(fn, iters))
+            res = {f: _summary(r) for f, r in runs.items()}
+            res["mxfp4"]["codes_tb_s"] = round((mcodes.numel() + mscales.numel()) / res["mxfp4"]["median_us"] / 1e6, 3)
+            res["mx_over_16"] = round(res["mxfp4"]["median_us"] / res["bf16"]["median_us"], 3)
+            res["mx_over_row"] = round(res["mxfp4"]["median_us"] / res["fp8_row"]["median_us"], 3)
+            res["k_splits"] = LM.choose_splits(segments[0] if silu else n, k)
+            out[f"mx_{name}_m{m}"] = res
+    return out
+
+
 def step_section(batches=(1, 8, 32, 128), modes=("bf16", "fp8_block", "fp8_block_wide")):
     from swiftllm_amd import EngineConfig, LlamaModel
     S, steps, batch_max, out = 1024, 32, max(batches), {}
@@ -170,7 +217,8 @@ def step_section(batches=(1, 8, 32, 128), modes=("bf16", "fp8_block", "fp8_block
         ec = EngineConfig(model_path=path, use_dummy=True, block_size=16, gpu_mem_utilization=0.9, num_cpu_blocks=0,
                           max_seqs_in_block_table=batch_max + 64, max_blocks_per_seq=max_len // 16 + 8, max_batch_size=batch_max,
                           max_tokens_in_batch=4096, dtype="bfloat16", use_hip_graph=True,
-                          dense_weight_dtype={"bf16": "auto", "fp8_row": "fp8_e4m3"}.get(mode, "fp8_block"), dense_fp8_wide=mode == "fp8_block_wide")
+                          dense_weight_dtype={"bf16": "auto", "fp8_row": "fp8_e4m3", "mxfp4": "mxfp4"}.get(mode, "fp8_block"),
+                          dense_fp8_wide=mode == "fp8_block_wide")
         model = LlamaModel(ec)
         model.load_weights()
         model.init_kvcache_and_swap(batch_max * (max_len // 16 + 2) + 64)
@@ -212,7 +260,9 @@ def main():
         ms, batches = [int(v) for v in a.ms.split(",")], [int(v) for v in a.batches.split(",")]
         run = {"gemm": lambda: gemm_section(a.iters, a.repeats, ms), "step": lambda: step_section(batches),
                "row_gemm": lambda: row_gemm_section(a.iters, a.repeats, ms),
-               "row_step": lambda: step_section([b for b in batches if b <= 32], ("bf16", "fp8_row"))}[a.child]
+               "row_step": lambda: step_section([b for b in batches if b <= 32], ("bf16", "fp8_row")),
+               "mx_gemm": lambda: mx_gemm_section(a.iters, a.repeats, ms),
+               "mx_step": lambda: step_section([b for b in batches if b <= 32], ("bf16", "fp8_row", "mxfp4"))}[a.child]
         print("RESULT " + json.dumps(run()), flush=True)
         return 0
     merged = {"iters": a.iters, "repeats": a.repeats}
